@@ -67,6 +67,7 @@ _EAGER_ATTNGAN = "--graph" not in sys.argv and not any(a.startswith("--workload"
 if _EAGER_ATTNGAN:
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "4")
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -99,6 +100,43 @@ def mfma_peak():
         return PEAK_BF16_MFMA_TFLOPS / 6.0, "split-bf16: 3 bf16 pieces per fp32 operand, 6 v_mfma_f32_32x32x16_bf16 partial " \
                                             "products per fp32 product (2500 TFLOP/s dense bf16 / 6)"
     return PEAK_F32_MFMA_TFLOPS, "native v_mfma_f32_32x32x2_f32"
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_outputs(logs):
+    """Host copy of every tensor a step returned (taken right after the timed region, before later legs reuse the buffers):
+    floating point as float32, anything else as float64."""
+    return {k: v.detach().cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64)
+            for k, v in logs.items() if torch.is_tensor(v)}
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: `arrays` (host_outputs of the last timed step) as out_dir/<name>.npy.  The inputs of a run are seeded
+    (networks, synthetic batch, z / eps) and the step's kernels add in a fixed order, so two runs with the same arguments
+    write the same arrays and two builds can be compared output by output.  The arrays share DUMP_LIMIT_BYTES smallest
+    first: one larger than an even share of what is left is replaced by a fixed sample of its flattened elements (indices
+    drawn from a RandomState seeded by the name, sorted).  Returns {name: description}."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = DUMP_LIMIT_BYTES, {}
+    order = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    for i, name in enumerate(order):
+        a = arrays[name]
+        desc = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            rng = np.random.RandomState(zlib.crc32(name.encode()) & 0x7FFFFFFF)
+            idx = np.unique(rng.randint(0, a.size, size=max(1, share // a.itemsize)))
+            a = a.reshape(-1)[idx]
+            desc["sampled_elements"] = int(a.size)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = desc
+    return written
+
+
 MODES = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bmm", "dconv_fwd", "dconv_dgrad", "dconv_wgrad")
 TILES = ("128x128", "96x128", "128x32", "32x128", "64x64", "128x64", "64x128")
 
@@ -382,6 +420,8 @@ def run_family(name, args, device):
         logs = run_step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dump_dir = getattr(args, "dump_outputs", None)       # callers that build their own args (tests) may leave it out
+    outputs = host_outputs(logs) if dump_dir else None
     ms = elapsed / args.steps * 1e3
     out = {"metric": "images/sec per G+D train step, %s" % name, "value": B * args.steps / elapsed,
            "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
@@ -390,6 +430,8 @@ def run_family(name, args, device):
                       "batch_per_gpu": B, "global_batch": B, "parallelism": "dp1",
                       "launch": "hipGraph" if engine.use_graph else "eager"},
            "losses": {k: float(v) for k, v in logs.items() if torch.is_tensor(v) and v.dim() == 0}}
+    if outputs is not None:
+        out["dump_outputs"] = {"dir": dump_dir, "arrays": dump_outputs(outputs, dump_dir)}
     if not args.no_roofline:
         rows, eager_ms = roofline_leg(engine, run_step)
         tot_ms = sum(r["ms_per_step"] for r in rows)
@@ -442,6 +484,8 @@ def main():
                     help="attngan = the headline metric (default); the others are the secondary BASELINE configs "
                          "(SURVEY.md §8(d): per-config numbers), single GPU")
     ap.add_argument("--family-batch", type=int, default=None, help="override the batch of a secondary workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed "
+                    "step returned (losses, generated images) as DIR/<name>.npy, float32, at most 64 MB in all")
     args = ap.parse_args()
     if args.workload != "attngan":
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -569,6 +613,7 @@ def main():
         elapsed, host_elapsed, logs, comm = timed_region(engine, run_step)
         lap("warm-up + timed region")
         results[mode] = dict(elapsed=elapsed, host_elapsed=host_elapsed, logs=logs, comm=comm,
+                             outputs=host_outputs(logs) if args.dump_outputs and rank == 0 else None,
                              launch="hipGraph" if engine.use_graph else "%s, %d streams + wgrad side streams" % (
                                  "generator eager + discriminator branches as hipGraphs" if engine.branch_graphs else "eager",
                                  1 + (len(engine.side) if engine.multi_stream else 0)))
@@ -591,6 +636,8 @@ def main():
                    "parallelism": "dp%d" % world, "launch": results[best]["launch"]},
         "losses": {k: float(v) for k, v in logs.items() if torch.is_tensor(v) and v.dim() == 0},
     }
+    if results[best]["outputs"] is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(results[best]["outputs"], args.dump_outputs)}
     if dist_on:
         # per launch mode: throughput and, per gradient bucket, what its all-reduce cost and how much of it the consumer saw
         out["dp"] = {"backend": dist.get_backend(), "world_size_seen": dist.get_world_size(), "mode_reported": best,

@@ -433,11 +433,10 @@ int mogan_stn_bwd(const float* dy, const float* theta, float* dx, int B, int C, 
  *            reference first .repeat()s over 16 x 16 (model.py:109-111); dx is (xB, C);
  *   theta_G  > 0: theta is stored (B / theta_G, theta_G, 2, 3) -- the loader's (image, object) order -- while the batch is
  *            object-major, sample b = g (B / theta_G) + b' using theta[b'][g] (the batched object loops); 0: theta[b].
- * Determinism: mogan_stn_bwd (like torch's grid_sample backward) scatters with fp32 atomicAdd, so the sum of the <= 4 output
- * pixels' contributions that meet in one source pixel depends on execution order; the shared-source forms add all OBJECTS'
- * contributions to that same sum (the reference adds G separately computed tensors in object order).  The result is
- * therefore reproducible to fp32 rounding of a sum of <= 4 G terms (measured run to run: <= 2 ulp of the largest term), not
- * bit for bit -- tests/test_kernels_gpu.py::test_stn_shared_source_gradient_is_order_independent_to_rounding pins that. */
+ * Determinism: mogan_stn_bwd / _ex gather rather than scatter: every source pixel sums the contributions of the output
+ * pixels whose taps land on it, samples in batch order and output pixels in row-major order, with no atomics, so dx is the
+ * same bit for bit from run to run (the shared-source forms add the objects in object order, as the reference does).
+ * tests/test_kernels_gpu.py::test_stn_shared_source_gradient_is_order_independent_to_rounding pins that. */
 int mogan_stn_fwd_ex(const float* x, const float* theta, float* y, int B, int C, int Hin, int Win, int Hout, int Wout,
                      int align_corners, int xB, int x_plane, int theta_G, hipStream_t stream);
 int mogan_stn_bwd_ex(const float* dy, const float* theta, float* dx, int B, int C, int Hin, int Win, int Hout, int Wout,

@@ -17,16 +17,6 @@ namespace {
 
 static inline int ok_launch() { return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH; }
 
-// zero-fill as a kernel node (not hipMemsetAsync): memset nodes captured into a hipGraph were observed
-// to race with the atomics kernel that follows them on this ROCm (rare NaN gradients under replay)
-__global__ __launch_bounds__(256) void zero_fill_kernel(float* __restrict__ p, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0.f;
-}
-static inline void zero_fill(float* p, size_t n, hipStream_t st) {
-    size_t b = (n + 255) / 256; if (b > 65536) b = 65536; if (b < 1) b = 1;
-    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)b), dim3(256), 0, st, p, n);
-}
-
 struct Taps { int x0, y0; float wx1, wy1; bool vx0, vx1, vy0, vy1; };
 
 __device__ __forceinline__ Taps stn_taps(const float* __restrict__ th, int oy, int ox, int Hin, int Win, int Hout,
@@ -92,41 +82,110 @@ __global__ __launch_bounds__(256) void stn_fwd_ex_kernel(const float* __restrict
     }
 }
 
-template <bool PLANE>
-__global__ __launch_bounds__(256) void stn_bwd_ex_kernel(const float* __restrict__ dy, const float* __restrict__ theta,
-                                                         float* __restrict__ dx, int C, int Hin, int Win, int Hout,
-                                                         int Wout, int ac, int cchunk, int xB, int tG) {
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    const bool in = pix < Hout * Wout;
-    const int b = blockIdx.z, bx = b % xB, c0 = blockIdx.y * cchunk, c1 = min(C, c0 + cchunk);
-    const int oy = in ? pix / Wout : 0, ox = in ? pix - oy * Wout : 0;
-    const int nb = tG > 0 ? (int)gridDim.z / tG : 1;
-    const int tb = tG > 0 ? (b % nb) * tG + b / nb : b;
-    const Taps t = stn_taps(theta + tb * 6, oy, ox, Hin, Win, Hout, Wout, ac);
-    const float w00 = (1.f - t.wx1) * (1.f - t.wy1), w01 = t.wx1 * (1.f - t.wy1);
-    const float w10 = (1.f - t.wx1) * t.wy1, w11 = t.wx1 * t.wy1;
-    const bool v00 = in && t.vx0 && t.vy0, v01 = in && t.vx1 && t.vy0, v10 = in && t.vx0 && t.vy1, v11 = in && t.vx1 && t.vy1;
-    const int o00 = t.y0 * Win + t.x0;
-    if (PLANE) {
-        // d x[b, c] = sum over the output pixels of dy * (sum of the in-range tap weights): per wave a butterfly, one atomic
-        const float wsum = (v00 ? w00 : 0.f) + (v01 ? w01 : 0.f) + (v10 ? w10 : 0.f) + (v11 ? w11 : 0.f);
-        for (int c = c0; c < c1; ++c) {
-            float g = in ? dy[((size_t)b * C + c) * Hout * Wout + pix] * wsum : 0.f;
+// Backward as a gather in a fixed order (bit-reproducible, no atomics): dx of source pixel (bx, c, sy, sx) collects, for the
+// samples b = bx, bx + xB, ... in order and their output pixels in row-major order, dy * the weight of every tap of that
+// output pixel that lands on (sx, sy).  The taps are those of the forward (stn_taps); the output pixels searched are the
+// preimage window of the source cell [sx-1, sx+1) x [sy-1, sy+1) under theta, widened by 1 pixel (a singular theta or a
+// one-pixel source axis searches the whole output).
+struct Win2 { int x0, x1, y0, y1; };
+
+__device__ __forceinline__ Win2 stn_preimage(const float* __restrict__ th, int sy, int sx, int Hin, int Win, int Hout,
+                                             int Wout, int ac) {
+    Win2 w = {0, Wout - 1, 0, Hout - 1};
+    const double a = th[0], bb = th[1], tx = th[2], c = th[3], d = th[4], ty = th[5];
+    const double det = a * d - bb * c;
+    if (!(fabs(det) > 1e-30) || (ac && (Win < 2 || Hin < 2))) return w;
+    double lox = 1e300, hix = -1e300, loy = 1e300, hiy = -1e300;
+    for (int k = 0; k < 4; ++k) {
+        const double ix = sx - 1 + 2 * (k & 1), iy = sy - 1 + 2 * (k >> 1);      // corners of the source cell
+        const double gx = ac ? 2.0 * ix / (Win - 1) - 1.0 : (2.0 * ix + 1.0) / Win - 1.0;
+        const double gy = ac ? 2.0 * iy / (Hin - 1) - 1.0 : (2.0 * iy + 1.0) / Hin - 1.0;
+        const double xn = (d * (gx - tx) - bb * (gy - ty)) / det, yn = (a * (gy - ty) - c * (gx - tx)) / det;
+        const double ox = ac ? (xn + 1.0) * 0.5 * (Wout - 1) : ((xn + 1.0) * Wout - 1.0) * 0.5;
+        const double oy = ac ? (yn + 1.0) * 0.5 * (Hout - 1) : ((yn + 1.0) * Hout - 1.0) * 0.5;
+        lox = fmin(lox, ox); hix = fmax(hix, ox); loy = fmin(loy, oy); hiy = fmax(hiy, oy);
+    }
+    if (!(lox <= hix && loy <= hiy)) return w;                               // non-finite theta: search everything
+    // clamped to [-1, W] before the int conversion (an empty window when the preimage misses the output)
+    w.x0 = (int)fmin(fmax(floor(lox) - 1.0, 0.0), (double)Wout); w.x1 = (int)fmax(fmin(ceil(hix) + 1.0, (double)(Wout - 1)), -1.0);
+    w.y0 = (int)fmin(fmax(floor(loy) - 1.0, 0.0), (double)Hout); w.y1 = (int)fmax(fmin(ceil(hiy) + 1.0, (double)(Hout - 1)), -1.0);
+    return w;
+}
+
+// weight of output pixel (oy, ox)'s taps on source pixel (sy, sx), summed in the forward's tap order
+__device__ __forceinline__ float stn_tap_weight(const Taps& t, int sy, int sx) {
+    float w = 0.f;
+    const bool x0 = t.x0 == sx, x1 = t.x0 + 1 == sx, y0 = t.y0 == sy, y1 = t.y0 + 1 == sy;
+    if (x0 && y0 && t.vx0 && t.vy0) w += (1.f - t.wx1) * (1.f - t.wy1);
+    if (x1 && y0 && t.vx1 && t.vy0) w += t.wx1 * (1.f - t.wy1);
+    if (x0 && y1 && t.vx0 && t.vy1) w += (1.f - t.wx1) * t.wy1;
+    if (x1 && y1 && t.vx1 && t.vy1) w += t.wx1 * t.wy1;
+    return w;
+}
+
+constexpr int STN_BWD_CC = 8;              // channels per thread of the gather (its accumulators)
+
+// grid (ceil(Hin Win / 256), ceil(C / STN_BWD_CC), xB); B samples, sample b reads image b % xB; tG as in stn_fwd_ex_kernel
+__global__ __launch_bounds__(256) void stn_bwd_gather_kernel(const float* __restrict__ dy, const float* __restrict__ theta,
+                                                             float* __restrict__ dx, int B, int C, int Hin, int Win,
+                                                             int Hout, int Wout, int ac, int xB, int tG) {
+    const int sp = blockIdx.x * 256 + threadIdx.x;
+    if (sp >= Hin * Win) return;
+    const int bx = blockIdx.z, c0 = blockIdx.y * STN_BWD_CC, nc = min(C - c0, STN_BWD_CC);
+    const int sy = sp / Win, sx = sp - sy * Win;
+    const int nb = tG > 0 ? B / tG : 1;
+    float acc[STN_BWD_CC];
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o, 64);
-            if ((threadIdx.x & 63) == 0 && g != 0.f) atomicAdd(dx + (size_t)bx * C + c, g);
+    for (int k = 0; k < STN_BWD_CC; ++k) acc[k] = 0.f;
+    for (int b = bx; b < B; b += xB) {
+        const int tb = tG > 0 ? (b % nb) * tG + b / nb : b;
+        const float* th = theta + tb * 6;
+        const Win2 w = stn_preimage(th, sy, sx, Hin, Win, Hout, Wout, ac);
+        const float* g = dy + ((size_t)b * C + c0) * Hout * Wout;
+        for (int oy = w.y0; oy <= w.y1; ++oy)
+            for (int ox = w.x0; ox <= w.x1; ++ox) {
+                const float wt = stn_tap_weight(stn_taps(th, oy, ox, Hin, Win, Hout, Wout, ac), sy, sx);
+                if (wt == 0.f) continue;
+                const size_t o = (size_t)oy * Wout + ox;
+#pragma unroll
+                for (int k = 0; k < STN_BWD_CC; ++k)
+                    if (k < nc) acc[k] += g[(size_t)k * Hout * Wout + o] * wt;
+            }
+    }
+#pragma unroll
+    for (int k = 0; k < STN_BWD_CC; ++k)
+        if (k < nc) dx[((size_t)bx * C + c0 + k) * Hin * Win + sp] = acc[k];
+}
+
+// x_plane: d x[bx, c] = sum over the samples b = bx, bx + xB, ... and their output pixels of dy * (sum of the in-range tap
+// weights); one block per (c, bx), each thread a fixed strided subset, then a fixed-shape tree in LDS
+__global__ __launch_bounds__(256) void stn_bwd_plane_kernel(const float* __restrict__ dy, const float* __restrict__ theta,
+                                                            float* __restrict__ dx, int B, int C, int Hin, int Win,
+                                                            int Hout, int Wout, int ac, int xB, int tG) {
+    __shared__ float red[256];
+    const int c = blockIdx.x, bx = blockIdx.y, HW = Hout * Wout;
+    const int nb = tG > 0 ? B / tG : 1;
+    float acc = 0.f;
+    for (int b = bx; b < B; b += xB) {
+        const int tb = tG > 0 ? (b % nb) * tG + b / nb : b;
+        const float* g = dy + ((size_t)b * C + c) * HW;
+        for (int pix = threadIdx.x; pix < HW; pix += 256) {
+            const int oy = pix / Wout, ox = pix - oy * Wout;
+            const Taps t = stn_taps(theta + tb * 6, oy, ox, Hin, Win, Hout, Wout, ac);
+            const float w00 = (1.f - t.wx1) * (1.f - t.wy1), w01 = t.wx1 * (1.f - t.wy1);
+            const float w10 = (1.f - t.wx1) * t.wy1, w11 = t.wx1 * t.wy1;
+            const float wsum = (t.vx0 && t.vy0 ? w00 : 0.f) + (t.vx1 && t.vy0 ? w01 : 0.f) +
+                               (t.vx0 && t.vy1 ? w10 : 0.f) + (t.vx1 && t.vy1 ? w11 : 0.f);
+            acc += g[pix] * wsum;
         }
-        return;
     }
-    if (!(v00 || v01 || v10 || v11)) return;
-    for (int c = c0; c < c1; ++c) {
-        float* px = dx + ((size_t)bx * C + c) * Hin * Win;
-        const float g = dy[((size_t)b * C + c) * Hout * Wout + pix];
-        if (v00) atomicAdd(px + o00, g * w00);
-        if (v01) atomicAdd(px + o00 + 1, g * w01);
-        if (v10) atomicAdd(px + o00 + Win, g * w10);
-        if (v11) atomicAdd(px + o00 + Win + 1, g * w11);
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
     }
+    if (threadIdx.x == 0) dx[(size_t)bx * C + c] = red[0];
 }
 
 __global__ __launch_bounds__(256) void stn_fwd_kernel(const float* __restrict__ x, const float* __restrict__ theta,
@@ -149,29 +208,6 @@ __global__ __launch_bounds__(256) void stn_fwd_kernel(const float* __restrict__ 
         if (v10) acc += px[o00 + Win] * w10;
         if (v11) acc += px[o00 + Win + 1] * w11;
         y[((size_t)b * C + c) * Hout * Wout + pix] = acc;
-    }
-}
-
-__global__ __launch_bounds__(256) void stn_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ theta,
-                                                      float* __restrict__ dx, int C, int Hin, int Win, int Hout,
-                                                      int Wout, int ac, int cchunk) {
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= Hout * Wout) return;
-    const int b = blockIdx.z, c0 = blockIdx.y * cchunk, c1 = min(C, c0 + cchunk);
-    const int oy = pix / Wout, ox = pix - oy * Wout;
-    const Taps t = stn_taps(theta + b * 6, oy, ox, Hin, Win, Hout, Wout, ac);
-    const float w00 = (1.f - t.wx1) * (1.f - t.wy1), w01 = t.wx1 * (1.f - t.wy1);
-    const float w10 = (1.f - t.wx1) * t.wy1, w11 = t.wx1 * t.wy1;
-    const bool v00 = t.vx0 && t.vy0, v01 = t.vx1 && t.vy0, v10 = t.vx0 && t.vy1, v11 = t.vx1 && t.vy1;
-    if (!(v00 || v01 || v10 || v11)) return;
-    const int o00 = t.y0 * Win + t.x0;
-    for (int c = c0; c < c1; ++c) {
-        float* px = dx + ((size_t)b * C + c) * Hin * Win;
-        const float g = dy[((size_t)b * C + c) * Hout * Wout + pix];
-        if (v00) atomicAdd(px + o00, g * w00);
-        if (v01) atomicAdd(px + o00 + 1, g * w01);
-        if (v10) atomicAdd(px + o00 + Win, g * w10);
-        if (v11) atomicAdd(px + o00 + Win + 1, g * w11);
     }
 }
 
@@ -323,14 +359,7 @@ int mogan_stn_fwd(const float* x, const float* theta, float* y, int B, int C, in
 
 int mogan_stn_bwd(const float* dy, const float* theta, float* dx, int B, int C, int Hin, int Win, int Hout,
                   int Wout, int align_corners, hipStream_t stream) {
-    if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || B > 65535) return MOGAN_ERR_SHAPE;
-    zero_fill(dx, (size_t)B * C * Hin * Win, stream);
-    const int pb = (Hout * Wout + 255) / 256;
-    int csplit = (1024 + pb * B - 1) / (pb * B); if (csplit > C) csplit = C; if (csplit < 1) csplit = 1;
-    const int cchunk = (C + csplit - 1) / csplit; csplit = (C + cchunk - 1) / cchunk;
-    hipLaunchKernelGGL(stn_bwd_kernel, dim3(pb, csplit, B), dim3(256), 0, stream, dy, theta, dx, C, Hin, Win, Hout, Wout,
-                       align_corners, cchunk);
-    return ok_launch();
+    return mogan_stn_bwd_ex(dy, theta, dx, B, C, Hin, Win, Hout, Wout, align_corners, B, 0, 0, stream);
 }
 
 int mogan_stn_fwd_ex(const float* x, const float* theta, float* y, int B, int C, int Hin, int Win, int Hout, int Wout,
@@ -353,14 +382,15 @@ int mogan_stn_bwd_ex(const float* dy, const float* theta, float* dx, int B, int 
     if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || B > 65535 || xB <= 0 || B % xB != 0 ||
         theta_G < 0 || (theta_G > 0 && B % theta_G != 0))
         return MOGAN_ERR_SHAPE;
-    zero_fill(dx, (size_t)xB * C * (x_plane ? 1 : (size_t)Hin * Win), stream);
-    const int pb = (Hout * Wout + 255) / 256;
-    int csplit = (1024 + pb * B - 1) / (pb * B); if (csplit > C) csplit = C; if (csplit < 1) csplit = 1;
-    const int cchunk = (C + csplit - 1) / csplit; csplit = (C + cchunk - 1) / cchunk;
-    if (x_plane) hipLaunchKernelGGL((stn_bwd_ex_kernel<true>), dim3(pb, csplit, B), dim3(256), 0, stream, dy, theta, dx, C, Hin, Win,
-                                    Hout, Wout, align_corners, cchunk, xB, theta_G);
-    else hipLaunchKernelGGL((stn_bwd_ex_kernel<false>), dim3(pb, csplit, B), dim3(256), 0, stream, dy, theta, dx, C, Hin, Win,
-                            Hout, Wout, align_corners, cchunk, xB, theta_G);
+    if (x_plane) {
+        hipLaunchKernelGGL(stn_bwd_plane_kernel, dim3(C, xB), dim3(256), 0, stream, dy, theta, dx, B, C, Hin, Win, Hout, Wout,
+                           align_corners, xB, theta_G);
+    } else {
+        const int cg = (C + STN_BWD_CC - 1) / STN_BWD_CC;
+        if (cg > 65535) return MOGAN_ERR_SHAPE;
+        hipLaunchKernelGGL(stn_bwd_gather_kernel, dim3((Hin * Win + 255) / 256, cg, xB), dim3(256), 0, stream, dy, theta, dx,
+                           B, C, Hin, Win, Hout, Wout, align_corners, xB, theta_G);
+    }
     return ok_launch();
 }
 

@@ -58,7 +58,7 @@ def grads_probe(module, prefix):
 
 
 def state_probe(module, prefix):
-    return {prefix + k.replace(".", "__"): probe(v.float()) for k, v in module.state_dict().items()}
+    return {prefix + k.replace(".", "__"): probe(v.double()) for k, v in module.state_dict().items()}
 
 
 def build(ns, tree, stage):
@@ -105,9 +105,14 @@ def sub(img):
     return img[:, :, ::s, ::s]
 
 
-def gen_nets(ns, case, tree, stage, B):
+def gen_nets(ns, case, tree, stage, B, dtype=torch.float32):
+    """dtype float64: the same run in double precision (stackgan_<case>_nets_f64.npz, for the CPU oracle test of the
+    full-width stage II: an fp32 run on another CPU or math library differs from this one beyond the test's bounds)."""
     bt = synthetic.make_batch(tree, B, stage=stage, seed=21, text_dim=12)
+    bt = {k: v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v for k, v in bt.items()}
+    torch.cuda.FloatTensor = torch.DoubleTensor if dtype == torch.float64 else torch.FloatTensor   # model.py's buffers
     G, D = build(ns, tree, stage)
+    G, D = G.to(dtype), D.to(dtype)
     out = {"g_keys": np.array(list(G.state_dict().keys())), "d_keys": np.array(list(D.state_dict().keys()))}
     # reference bbox -> theta of this tree on the batch's boxes (mnist computes in float64)
     bb = bt["bbox_s2" if stage == 2 else "bbox"].view(-1, 4)
@@ -151,13 +156,13 @@ def gen_nets(ns, case, tree, stage, B):
     out.update(d_dx_sub=sub(x.grad), d_dx_p=probe(x.grad))
     out.update(grads_probe(D, "dg_"))
     out.update({k: v for k, v in state_probe(D, "ds_").items() if "running" in k})
-    save("stackgan_%s_nets" % case, **out)
+    save("stackgan_%s_nets%s" % (case, "" if dtype == torch.float32 else "_f64"), **out)
 
 
 def train_step(ns, tree, stage, G, D, optG, optD, bt):
     """S/trainer.py:188-231, C/trainer.py:127-157, M/trainer.py:131-160."""
     B = bt["z"].shape[0]
-    real_labels, fake_labels = torch.ones(B), torch.zeros(B)
+    real_labels, fake_labels = torch.ones(B, dtype=bt["z"].dtype), torch.zeros(B, dtype=bt["z"].dtype)
     if tree == "coco":
         inject_eps(G, bt, stage)
     fake, mu, logvar, _, _ = run_g(G, tree, stage, bt)
@@ -183,13 +188,17 @@ def train_step(ns, tree, stage, G, D, optG, optD, bt):
     return logs
 
 
-def gen_step(ns, case, tree, stage, B):
+def gen_step(ns, case, tree, stage, B, dtype=torch.float32):
+    """dtype float64: stackgan_<case>_step_f64.npz, as gen_nets"""
+    torch.cuda.FloatTensor = torch.DoubleTensor if dtype == torch.float64 else torch.FloatTensor   # model.py's buffers
     G, D = build(ns, tree, stage)
+    G, D = G.to(dtype), D.to(dtype)
     optD = torch.optim.Adam(D.parameters(), lr=2e-4, betas=(0.5, 0.999))
     optG = torch.optim.Adam([p for p in G.parameters() if p.requires_grad], lr=2e-4, betas=(0.5, 0.999))
     out = {}
     for step in range(2):
         bt = synthetic.make_batch(tree, B, stage=stage, seed=300 + step, text_dim=12)
+        bt = {k: v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v for k, v in bt.items()}
         logs = train_step(ns, tree, stage, G, D, optG, optD, bt)
         p = "s%d_" % step
         for k, v in logs.items():
@@ -200,16 +209,20 @@ def gen_step(ns, case, tree, stage, B):
         out.update(state_probe(G, p + "G_"))
         out.update(state_probe(D, p + "D_"))
         print(case, "step", step, {k: v for k, v in logs.items() if k != "fake"})
-    save("stackgan_%s_step" % case, **out)
+    save("stackgan_%s_step%s" % (case, "" if dtype == torch.float32 else "_f64"), **out)
 
 
 def main():
     only = sys.argv[1:]
     for case, (tree, stage, B, kw) in CASES.items():
-        if only and case not in only:
+        if only and case not in only and case + "_f64" not in only:
             continue
         ns = ref_shim.load_tree(tree)
         ref_shim.set_tree_cfg(ns.cfg, tree, stage, **kw)
+        if case + "_f64" in only:                   # e.g. `python tests/golden/make_golden_stackgan.py coco_s2_f64`
+            gen_nets(ns, case, tree, stage, B, torch.float64)
+            gen_step(ns, case, tree, stage, B, torch.float64)
+            continue
         gen_nets(ns, case, tree, stage, B)
         gen_step(ns, case, tree, stage, B)
 

@@ -428,9 +428,9 @@ def test_first_discriminator_layer_streaming_kernel(B, H, W, Cout):
 
 
 def test_stn_shared_source_gradient_is_order_independent_to_rounding():
-    """mogan_stn_bwd_ex adds every object's contribution to the ONE image-batch gradient with fp32 atomics (include/mogan_hip.h,
-    "Determinism"): two runs agree to the rounding of a short sum, and both agree with the fixed-order sum of the per-object
-    gradients to the same bound -- not bit for bit."""
+    """mogan_stn_bwd_ex adds every object's contribution to the ONE image-batch gradient (include/mogan_hip.h, "Determinism"):
+    two runs agree to the rounding of a short sum, and both agree with the fixed-order sum of the per-object gradients to the
+    same bound (bit-for-bit agreement of runs: test_stn_backward_is_bitwise_reproducible)."""
     B, G, C, S = 5, 3, 7, 16
     x = T("sdx", (B, C, 32, 32)).to(DEV)
     th = (T("sdth", (B, G, 2, 3), 0.3) + torch.tensor([[1.0, 0, 0], [0, 1.0, 0]])).to(DEV)
@@ -452,6 +452,49 @@ def test_stn_shared_source_gradient_is_order_independent_to_rounding():
     for o in outs:
         assert float((o.double() - ref).abs().max()) <= 4e-6 * scale
     assert float((outs[0] - outs[1]).abs().max()) <= 4e-6 * scale and float((outs[1] - outs[2]).abs().max()) <= 4e-6 * scale
+
+
+@pytest.mark.parametrize("ac", [False, True])
+def test_stn_backward_is_bitwise_reproducible(ac):
+    """mogan_stn_bwd / _ex gather every source pixel's contributions in a fixed order (include/mogan_hip.h, "Determinism"):
+    two runs give the same dx bit for bit, for the plain, shared-source and constant-source forms.  C = 13 spans two channel
+    groups of the gather with a partial second one; the boxes include tiny ones (0.01 and 0.03 of the image), whose crops
+    magnify one source pixel onto many output pixels, and an absent object.  Values against the fp64 oracle."""
+    Bp, G, C = 2, 3, 13
+    bbox = torch.tensor([[0.1, 0.2, 0.3, 0.4], [0.5, 0.5, 0.01, 0.01], [-1, -1, -1, -1],
+                         [0.0, 0.0, 1.0, 1.0], [0.3, 0.6, 0.03, 0.2], [0.45, 0.1, 0.5, 0.85]])
+    th, thi = (t.view(Bp, G, 2, 3) for t in __import__("mogan_amd.attngan.synthetic", fromlist=["x"]).bbox_to_theta(bbox))
+    objmajor = lambda t: t.transpose(0, 1).reshape(G * Bp, 2, 3)         # sample n = g * Bp + b
+    g = T("stnrep.g", (G * Bp, C, 16, 16))
+
+    def twice(fn, x):
+        outs = []
+        for _ in range(2):
+            xd = x.detach().to(DEV).requires_grad_(True)
+            fn(xd).backward(g.to(DEV))
+            outs.append(xd.grad.clone())
+        assert torch.equal(outs[0], outs[1])
+        return outs[0]
+
+    # plain: one theta per sample, crop (64 x 64 -> 16 x 16) and placement (16 x 16 -> 16 x 16)
+    for theta, hw in ((objmajor(th), (64, 64)), (objmajor(thi), (16, 16))):
+        x = T("stnrep.x%d" % hw[0], (G * Bp, C) + hw).requires_grad_(True)
+        ref = O.stn(x.double(), theta.double(), (G * Bp, C, 16, 16), align_corners=ac)
+        ref.backward(g.double())
+        _check(twice(lambda xd: ops.stn(xd, theta.to(DEV), (G * Bp, C, 16, 16), ac), x), x.grad, 1e-5, "plain dx")
+    # shared image batch read by every object
+    x = T("stnrep.xs", (Bp, C, 64, 64)).requires_grad_(True)
+    ref = O.stn(x.double().repeat(G, 1, 1, 1), objmajor(th).double(), (G * Bp, C, 16, 16), align_corners=ac)
+    ref.backward(g.double())
+    _check(twice(lambda xd: ops.stn_shared(xd, th.to(DEV), G * Bp, (64, 64), (16, 16), ac, theta_G=G), x), x.grad, 1e-5,
+           "shared dx")
+    # constant source
+    v = T("stnrep.v", (G * Bp, C)).requires_grad_(True)
+    ref = O.stn(v.double().view(G * Bp, C, 1, 1).repeat(1, 1, 16, 16), objmajor(thi).double(), (G * Bp, C, 16, 16),
+                align_corners=ac)
+    ref.backward(g.double())
+    _check(twice(lambda vd: ops.stn_shared(vd, thi.to(DEV), G * Bp, (16, 16), (16, 16), ac, plane=True, theta_G=G), v),
+           v.grad, 1e-5, "plane dx")
 
 
 @pytest.mark.parametrize("ac", [False, True])

@@ -355,15 +355,19 @@ def test_full_width_blocks_oracle_vs_reference(tag):
 
 
 def test_full_width_nets_oracle_vs_reference():
-    """G_NET forward + discriminator_loss through D_NET256 + backward at coco_train.yml widths, B = 4: the oracle (fp32,
-    same torch-CPU ops as the reference) against the reference's fixture."""
+    """G_NET forward + discriminator_loss through D_NET256 + backward at coco_train.yml widths, B = 4: the oracle (same
+    torch-CPU ops as the reference) against the reference's fixture, both in float64 (fw_nets_f64): the fp32 rounding of
+    another CPU or math library, amplified through the full-width nets, alone exceeds these bounds."""
     from helpers import big_probe_close
-    g = golden("fw_nets")
+    g = golden("fw_nets_f64")
     cfg = O.Cfg()
     B = 4
+    dt = torch.float64
     bt = synthetic.make_batch(B, words_num=12, nef=256, seed=21)
-    G = O.from_state_dict(det_state(O.g_net_spec(cfg), "G."), requires_grad=False)
-    D = O.from_state_dict(det_state(O.d_net_spec(2, cfg), "D2."))
+    bt = {k: ([t.to(dt) for t in v] if k == "imgs" else v.to(dt) if torch.is_tensor(v) and v.is_floating_point() else v)
+          for k, v in bt.items()}
+    G = O.from_state_dict(det_state(O.g_net_spec(cfg), "G."), dtype=dt, requires_grad=False)
+    D = O.from_state_dict(det_state(O.d_net_spec(2, cfg), "D2."), dtype=dt)
     with torch.no_grad():
         imgs, atts, mu, logvar, _ = O.g_net(G, cfg, bt["z"], bt["sent_emb"], bt["words_embs"], bt["mask"], bt["tmi"],
                                            bt["label_one_hot"], bt["eps"])

@@ -27,11 +27,11 @@ def _freeze_stage1(net):
             v.requires_grad_(False)
 
 
-def _nets(case):
+def _nets(case, dtype=torch.float32):
     cfg, tree, stage, B = oracle_cfg(case)
     gs, ds = specs(cfg)
-    G = S.from_state_dict(det_state(gs, "G."))
-    D = S.from_state_dict(det_state(ds, "D."))
+    G = S.from_state_dict(det_state(gs, "G."), dtype=dtype)
+    D = S.from_state_dict(det_state(ds, "D."), dtype=dtype)
     if stage == 2:
         _freeze_stage1(G)
     return cfg, tree, stage, B, G, D, gs, ds
@@ -58,10 +58,11 @@ def test_theta_of_tree(case):
     np.testing.assert_array_equal(tmi.reshape(-1, 2, 3).numpy(), g["ref_tmi"])
 
 
-def _check_nets(case):
-    g = golden("stackgan_%s_nets" % case)
-    cfg, tree, stage, B, G, D, _, _ = _nets(case)
+def _check_nets(case, dtype=torch.float32):
+    g = golden("stackgan_%s_nets%s" % (case, "" if dtype == torch.float32 else "_f64"))
+    cfg, tree, stage, B, G, D, _, _ = _nets(case, dtype)
     bt = synthetic.make_batch(tree, B, stage=stage, seed=21, text_dim=12)
+    bt = {k: v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v for k, v in bt.items()}
     z = bt["z"].clone().requires_grad_(True)
     st = S.TrainState(G, D, cfg)
     fake, mu, logvar = S.generate(st, dict(bt, z=z))
@@ -87,7 +88,7 @@ def _check_nets(case):
     tm, tmi = (bt["tm_s2"], bt["tmi_s2"]) if stage == 2 else (bt["tm"], bt["tmi"])
     x = bt["real_imgs"].clone().requires_grad_(True)
     f = S.d_features(D, cfg, x, bt["label_one_hot"], tm, tmi)
-    cond = T("D.cond", (B, 128), 0.5) if tree == "coco" else bt["label_one_hot"].sum(1)
+    cond = T("D.cond", (B, 128), 0.5).to(dtype) if tree == "coco" else bt["label_one_hot"].sum(1)
     c = S.cond_logits(D, cfg, f, cond)
     cw = S.cond_logits(D, cfg, f[:B - 1], cond[1:])
     loss = (f * T("D.gf", f.shape)).sum() + (c * T("D.gc", c.shape)).sum() + (cw * T("D.gcw", cw.shape)).sum()
@@ -106,13 +107,14 @@ def _check_nets(case):
             probe_close(probe(v), g["ds_" + k.replace(".", "__")], 1e-5, what=k)
 
 
-def _check_steps(case):
-    g = golden("stackgan_%s_step" % case)
-    cfg, tree, stage, B, G, D, _, _ = _nets(case)
+def _check_steps(case, dtype=torch.float32):
+    g = golden("stackgan_%s_step%s" % (case, "" if dtype == torch.float32 else "_f64"))
+    cfg, tree, stage, B, G, D, _, _ = _nets(case, dtype)
     st = S.TrainState(G, D, cfg)
     init = {n: {k: probe(v) for k, v in S.parameters(net)} for n, net in (("G", G), ("D", D))}
     for step in range(2):
         bt = synthetic.make_batch(tree, B, stage=stage, seed=300 + step, text_dim=12)
+        bt = {k: v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v for k, v in bt.items()}
         logs = S.train_step(st, bt)
         p = "s%d_" % step
         for k in ("errD", "errD_real", "errD_wrong", "errD_fake", "errG") + (("kl",) if cfg.text else ()):
@@ -141,6 +143,8 @@ def test_two_train_steps(case):
 
 
 def test_stage2_networks_and_steps():
-    """coco stage II at the generator's full width (GF_DIM 192 is forced by S/model.py:340)."""
-    _check_nets("coco_s2")
-    _check_steps("coco_s2")
+    """coco stage II at the generator's full width (GF_DIM 192 is forced by S/model.py:340), oracle and reference both in
+    float64 (stackgan_coco_s2_nets_f64 / _step_f64): the fp32 rounding of another CPU, math library or thread count,
+    amplified through the full-width stage II, alone exceeds these bounds."""
+    _check_nets("coco_s2", torch.float64)
+    _check_steps("coco_s2", torch.float64)
