@@ -272,12 +272,14 @@ FLIPPED_DGRAD = True
 class _FrozenConv:
     """one BasicConv2d (or a group of same-input 1x1 ones) with eval-mode BN folded: forward (w, scale, shift), backward w * scale"""
 
-    def __init__(self, mods):
+    def __init__(self, mods, names=None):
         mods = list(mods)
         m0 = mods[0].conv
         self.k, self.stride, self.pad = m0.kernel_size, m0.stride[0], m0.padding
         for m in mods[1:]:
             assert m.conv.kernel_size == self.k and m.conv.stride[0] == self.stride and m.conv.padding == self.pad
+        self.names = names                       # torchvision layer names of the members (read by tests only)
+        self.couts = [m.conv.weight.shape[0] for m in mods]
         with torch.no_grad():
             self.w = torch.cat([m.conv.weight for m in mods], 0).contiguous()
             folded = [m.folded() for m in mods]
@@ -464,8 +466,8 @@ class FrozenTrunk:
     """Folded weights of an eval-mode, frozen CNN_ENCODER trunk + its explicit forward/backward (see the section comment)."""
 
     def __init__(self, enc):
-        g = lambda *names: _FrozenConv([getattr(blk, n) for n in names])
-        self.stem = {n: _FrozenConv([getattr(enc, n)]) for n in ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3",
+        g = lambda *names: _FrozenConv([getattr(blk, n) for n in names], names=[name + "." + n for n in names])
+        self.stem = {n: _FrozenConv([getattr(enc, n)], names=[n]) for n in ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3",
                                                                "Conv2d_3b_1x1", "Conv2d_4a_3x3")}
         self.blocks = []
         for name, _ in TRUNK[5:]:
@@ -688,9 +690,10 @@ class _PS:
 class _PConv:
     """one convolution of the panel trunk (or a group of same-input 1x1 ones: rows concatenated): packed filters, folded BN"""
 
-    def __init__(self, mods, dgrad=True):
+    def __init__(self, mods, dgrad=True, names=None):
         from ..hip.lib import call, load, stream_ptr
         mods = list(mods)
+        self.names = names                       # torchvision layer names of the members (read by tests only)
         m0 = mods[0].conv
         self.k, self.stride, self.pad = m0.kernel_size, m0.stride[0], m0.padding
         for m in mods[1:]:
@@ -830,12 +833,12 @@ class PanelTrunk(FrozenTrunk):
     """Stem as FrozenTrunk (wide maps, few channels: the streaming / Winograd kernels); Mixed_5b .. 7c on pixel panels."""
 
     def __init__(self, enc):
-        self.stem = {n: _FrozenConv([getattr(enc, n)]) for n in ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3",
+        self.stem = {n: _FrozenConv([getattr(enc, n)], names=[n]) for n in ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3",
                                                                "Conv2d_3b_1x1", "Conv2d_4a_3x3")}
         self.blocks = []
         for name, _ in TRUNK[5:]:
             blk = getattr(enc, name)
-            g = lambda *names, **kw: _PConv([getattr(blk, n) for n in names], **kw)
+            g = lambda *names, **kw: _PConv([getattr(blk, n) for n in names], names=[name + "." + n for n in names], **kw)
             if isinstance(blk, InceptionA):
                 fcs = dict(g1=g("branch1x1", "branch5x5_1", "branch3x3dbl_1", "branch_pool"), b5=g("branch5x5_2"),
                            d2=g("branch3x3dbl_2"), d3=g("branch3x3dbl_3"))

@@ -18,7 +18,7 @@ from oracle import inception_oracle as IO  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def test_cnn_encoder_vs_cpu_restatement():
+def test_cnn_encoder_vs_cpu_restatement(monkeypatch):
     from mogan_amd.attngan import model
     cfg.TRAIN.FLAG, cfg.TEXT.EMBEDDING_DIM = True, 32
     torch.manual_seed(3)
@@ -54,7 +54,16 @@ def test_cnn_encoder_vs_cpu_restatement():
         p_.requires_grad = False
     assert enc._frozen()
     xf = x.detach().cuda().requires_grad_(True)
-    f2, c2 = enc(xf)
+    import inception_decisions as D
+    runs, fwd = [], inception.PanelTrunk.forward
+
+    def recorded(self, x299):
+        out = fwd(self, x299)
+        runs.append((self, out[0]))
+        return out
+    with D.recording(monkeypatch) as rec, monkeypatch.context() as m:
+        m.setattr(inception.PanelTrunk, "forward", recorded)
+        f2, c2 = enc(xf)
     ((f2 * gf.cuda()).sum() + (c2 * gc.cuda()).sum()).backward()
     torch.cuda.synchronize()
     assert rel(f2, f_ref) < 2e-5 and rel(c2, c_ref) < 2e-5, (rel(f2, f_ref), rel(c2, c_ref))
@@ -63,6 +72,19 @@ def test_cnn_encoder_vs_cpu_restatement():
     print("frozen trunk: features vs fp64 %.1e, vs module path %.1e; image gradient vs fp64 %.1e (module path %.1e), vs module "
           "path %.1e" % (rel(f2, f_ref), rel(f2, f.detach().cpu().double()), rel(xf.grad, x.grad), rel(xd.grad, x.grad),
                          rel(xf.grad, xd.grad.detach().cpu().double())))
+    # the same with the trunk's own ReLU / max-pool decisions imposed on the fp64 oracle: fp32 rounding is all that is left
+    (trunk, tapes), = runs
+    dec = D.decisions(trunk, tapes, rec)
+    xm = x.detach().double().requires_grad_(True)
+    with D.imposed(*dec) as flips:
+        f_m, c_m = IO.cnn_encoder(sd, xm)
+        ((f_m * gf.double()).sum() + (c_m * gc.double()).sum()).backward()
+    n, worst = D.flip_summary(flips)
+    print("frozen trunk, matched decisions: image gradient vs fp64 %.2e (%d flips, worst |pre| / rms %.1e)"
+          % (rel(xf.grad, xm.grad), n, worst))
+    assert rel(f2, f_m) < 2e-5 and rel(c2, c_m) < 2e-5, (rel(f2, f_m), rel(c2, c_m))
+    assert rel(xf.grad, xm.grad) < 5e-5, rel(xf.grad, xm.grad)          # measured 9.2e-6 (31 flips)
+    assert worst <= 1e-4, flips                                           # measured 1.1e-5
 
 
 def test_main_trains_on_synthetic_and_checkpoints(tmp_path):
