@@ -2,6 +2,7 @@
 """bench.py -- images/sec of one coco-attngan G+D train step (256x256) on N MI355X of one node.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full     (+ roofline, CPU baseline and parity legs, see below)
     python bench.py --gpus N --steps K --warmup W          (re-executes itself under torch.distributed.run, N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -11,7 +12,8 @@ minibatch of B=16 per GPU: text-encode, G forward, 3 x (D zero_grad, discriminat
 Adam), generator_loss incl. Inception + DAMSM words/sentence losses + KL, backward, Adam, EMA.
 fp32 everywhere, random-init networks of the full coco_train.yml widths, inputs resident in HBM.
 W untimed warm-up steps, then exactly K steps bracketed by barrier + torch.cuda.synchronize();
-elapsed = MAX over ranks; rank 0 prints ONE JSON line.  Extra objects on that line:
+elapsed = MAX over ranks; rank 0 prints ONE JSON line.  A plain run does only that: set-up, warm-up, the timed steps, the
+arrays of --dump-outputs, the line.  With --full it goes on, after the timed region, to the legs that add these objects:
   roofline      dominant MFMA kernel family by time (round 4: the implicit GEMM runs as gemm_kernel, the weight-heavy layers as
                 pgemm_kernel, the frozen Inception trunk as pgemm_group_kernel; all listed under `families`, their sum under
                 `implicit_gemm_layers`): algorithmic fp32 flops per launch (2*M*N*K
@@ -23,6 +25,7 @@ elapsed = MAX over ranks; rank 0 prints ONE JSON line.  Extra objects on that li
                 timed on this host's cores on the same workload (rank 0, N=1 only): 1 warm-up + 2 timed steps.
   parity        that warm-up step against ONE HIP step from the same weights with the same z / eps: relative
                 difference of every loss, max-abs difference of the generated 64x64 / 256x256 images.
+--no-roofline / --no-cpu-baseline drop one of them from a --full run.  The same holds for the secondary workloads (--workload).
 """
 import argparse
 import json
@@ -432,7 +435,7 @@ def run_family(name, args, device):
            "losses": {k: float(v) for k, v in logs.items() if torch.is_tensor(v) and v.dim() == 0}}
     if outputs is not None:
         out["dump_outputs"] = {"dir": dump_dir, "arrays": dump_outputs(outputs, dump_dir)}
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         rows, eager_ms = roofline_leg(engine, run_step)
         tot_ms = sum(r["ms_per_step"] for r in rows)
         tot_gf = sum(r["gflop_per_step"] for r in rows)
@@ -449,7 +452,7 @@ def run_family(name, args, device):
                            "eager_ms_per_step": eager_ms,
                            "kernels": [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}
                                        for r in rows[:8]]}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"], out["parity"] = family_cpu_baseline(engine, cfg, tree, stage, B, bt_cpu, dev_batch=batch)
     print(json.dumps(out), flush=True)
     del engine, G, D
@@ -468,10 +471,14 @@ def main():
                     "of eager multi-stream launches (the default: measured faster once the independent branches "
                     "and the weight gradients run on side streams)")
     ap.add_argument("--no-graph", action="store_true", help="(default; kept for older command lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=2, help="timed steps of the CPU oracle leg after its warm-up step (25-30 s "
-                    "each on the GPU box's host; default 2 keeps the default run within minutes, BASELINE.md section 3 asks "
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the legs that measure or check more "
+                    "than the headline figure: the roofline leg (per-kernel MFMA timing over extra eager steps) and, on one "
+                    "GPU, the CPU oracle baseline with its parity step.  Off by default: a plain run sets up, warms up, times "
+                    "the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline and parity step")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline leg")
+    ap.add_argument("--cpu-steps", type=int, default=2, help="--full: timed steps of the CPU oracle leg after its warm-up step "
+                    "(25-30 s each on the benchmark host; default 2 keeps the run within minutes, BASELINE.md section 3 asks "
                     "for 5: --cpu-steps 5)")
     ap.add_argument("--no-text-prefetch", action="store_true", help="text-encode every batch at the start of its own step")
     ap.add_argument("--no-inputs-ready", action="store_true", help="A/B: D_i(real) of a step waits for the main stream (the "
@@ -517,10 +524,10 @@ def main():
         world, args.gpus)
 
     # wall clock per phase of this run -> stderr and `phase_s` of the line (the driver's bench run took 491 s
-    # around a 0.73 s timed region).  On the builder's boxes the whole default run is 102 s: initialisation 2 s (the orthogonal
-    # init of D_NET256's largest layer is 1.1 s), warm-up + timed region 4 s, roofline leg 0.2 s, CPU oracle + parity 94 s
-    # (profiles/r06_ab.txt); what a run spends beyond that is outside this process (first import of torch on a fresh box) or the
-    # host's CPU leg -- the line says which
+    # around a 0.73 s timed region).  On the builder's boxes a --full run is 102 s: initialisation 2 s (the orthogonal init of
+    # D_NET256's largest layer is 1.1 s), warm-up + timed region 4 s, roofline leg 0.2 s, CPU oracle + parity 94 s
+    # (profiles/r06_ab.txt; a plain run stops after the timed region); what a run spends beyond that is outside this process
+    # (first import of torch on a fresh box) or the host's CPU leg -- the line says which
     phase_s, _t_phase = {}, [time.perf_counter()]
 
     def lap(name):
@@ -646,7 +653,7 @@ def main():
                                    "host_enqueue_ms_per_step": r["host_elapsed"] / args.steps * 1e3, "launch": r["launch"],
                                    "buckets": r["comm"]} for m, r in results.items()}}
     rows = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # EVERY rank runs these extra steps (they contain the gradient all-reduces: a rank-0-only leg would leave
         # the collectives unmatched and hang for N>1); rank 0 reports
         rows, eager_ms = roofline_leg(engine, run_step)
@@ -692,7 +699,7 @@ def main():
             "eager_ms_per_step": eager_ms,
             "kernels": [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in rows[:10]],
         }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         dev_batch = dict(batch)
         dev_batch.update(engine.encode_batch_for_cpu(batch))
         out["cpu_baseline"], out["parity"] = cpu_baseline_leg(engine, bt_cpu, dev_batch, B, device, timed_steps=args.cpu_steps,

@@ -193,7 +193,7 @@ def test_sample_rows_from_a_checkpoint_via_main(tmp_path):
 
 
 def test_bench_two_ranks_control_flow():
-    """`python bench.py --gpus 2 ...` as ONE plain command: bench.py re-executes itself under torch.distributed.run (2 ranks,
+    """`python bench.py --gpus 2 ... --full` as ONE plain command: bench.py re-executes itself under torch.distributed.run (2 ranks,
     the way the driver launches N>1 and what train.sh:25-29 hands to data_parallel in the reference) -- on this 1-GPU box
     both ranks share cuda:0 and the process group is gloo (MOGAN_ONE_GPU / MOGAN_DIST_BACKEND), which exercises everything
     but RCCL itself: matched collectives on every rank in the warm-up, the timed steps AND the roofline leg, the MAX
@@ -205,7 +205,7 @@ def test_bench_two_ranks_control_flow():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]

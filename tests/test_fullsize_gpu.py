@@ -175,11 +175,11 @@ def test_headline_workload_one_step_against_the_oracle():
 @pytest.mark.parametrize("name", ["clevr", "coco_s2"])
 def test_secondary_workloads_one_step_against_the_oracle_at_their_stated_size(name):
     """BASELINE configs 2 and 3 at the size they are quoted on (CLEVR B = 32; MS-COCO StackGAN stage II 256x256 B = 24, yml
-    widths): `bench.py --workload <name>` -- a few timed steps, then its `parity` object: one HIP step against one step of
+    widths): `bench.py --workload <name> --full` -- a few timed steps, then its `parity` object: one HIP step against one step of
     oracle/stackgan_oracle.py from the benchmarked weights on the same batch / z / eps.  Losses 1e-4 relative, images 1e-3."""
     import argparse
     bench = _bench_module()
-    args = argparse.Namespace(family_batch=None, graph=False, no_graph=False, warmup=2, steps=3, no_roofline=True,
+    args = argparse.Namespace(family_batch=None, graph=False, no_graph=False, warmup=2, steps=3, full=True, no_roofline=True,
                               no_cpu_baseline=False)
     real = bench.family_cpu_baseline
     bench.family_cpu_baseline = lambda *a, **k: real(*a, **dict(k, timed_steps=0))     # parity step only

@@ -19,7 +19,7 @@ python $R/tools/stats_summary.py $O/${RN}_bench_kernel_stats.csv 13 > $O/${RN}_b
 env MOGAN_FAST_INIT=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/km -o km -- $B2 > /tmp/km.log 2>&1
 cp /tmp/km/km_kernel_stats.csv $O/${RN}_bench_kernel_stats_multistream.csv
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/${RN}_bench_n1.json.log 2>/dev/null
+python bench.py --steps 20 --warmup 5 --full > $O/${RN}_bench_n1.json.log 2>/dev/null
 : > $O/${RN}_family_bench_n1.jsonl
-for w in mnist clevr coco_s1 coco_s2; do python bench.py --workload $w --steps 20 --warmup 5 2>/dev/null | tail -1 >> $O/${RN}_family_bench_n1.jsonl; done
+for w in mnist clevr coco_s1 coco_s2; do python bench.py --workload $w --steps 20 --warmup 5 --full 2>/dev/null | tail -1 >> $O/${RN}_family_bench_n1.jsonl; done
 tail -1 $O/${RN}_bench_n1.json.log | cut -c1-200; wc -l $O/${RN}_family_bench_n1.jsonl; ls -la $O/${RN}_*
