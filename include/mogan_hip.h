@@ -226,6 +226,9 @@ int mogan_conv2d_wgrad(const float* dy, const float* x, float* dw, int B, int Ci
  *                            buffer and the bookkeeping: the library keeps no weight state)
  *   mogan_conv2d_fwd_pk      y = conv2d(x, w) from the forward-packed weights;  workspace: B*Hs*Ws*Cin*6 bytes + split-K slabs
  *   mogan_conv2d_dgrad_pk    dx = conv2d data gradient from the dgrad-packed weights; workspace: B*OH*OW*Cout*6 bytes + slabs
+ *                            (both need the workspace for the packed activations: where it is NULL or smaller than that panel,
+ *                            rounded up to 256 bytes, they return MOGAN_ERR_WS and write nothing; a workspace that holds the
+ *                            panel but not two slabs only disables the K-split)
  *   mogan_pk_debug_force     test hook (process-wide): take_all != 0 drops the size heuristic of mogan_pk_conv_eligible (hard
  *                            constraints stay); cfg in 0..2 forces a tile shape (-1 = heuristic), split > 0 a K-split count */
 int mogan_pk_conv_eligible(int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW, int stride, int ph, int pw, int dgrad);
@@ -242,7 +245,8 @@ int mogan_conv2d_dgrad_pk(const float* dy, const void* wpk, float* dx, int B, in
 int mogan_pk_debug_force(int take_all, int cfg, int split);
 /* weight gradient of the same weight-heavy layers on the packed kernels: dY and the transposed im2col matrix of x are packed per
  * call into the workspace (ws_bytes >= what mogan_pk_wgrad_eligible checks: ~ (Cout + Cin*KH*KW) * B*OH*OW * 6 bytes), dW
- * (Cout,Cin,KH,KW) is written or (accumulate != 0) added to.  Same fp32 products as mogan_conv2d_wgrad, other summation order. */
+ * (Cout,Cin,KH,KW) is written or (accumulate != 0) added to.  Same fp32 products as mogan_conv2d_wgrad, other summation order.
+ * A workspace that does not hold both packed operands: MOGAN_ERR_WS, dW untouched. */
 int mogan_pk_wgrad_eligible(int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW, int stride, int ph, int pw, size_t ws_bytes);
 int mogan_conv2d_wgrad_pk(const float* dy, const float* x, float* dw, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW,
                           int stride, int ph, int pw, int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
@@ -319,7 +323,8 @@ int mogan_panel_tail_group(int n, const MoganTailArgs* args, hipStream_t stream)
  * upsampled grid sees only 2x2 distinct source pixels, so 4 multiply-adds per output pixel replace 9 (same result up
  * to the fp32 rounding of the pre-summed weights).  x (B,Cin,Hs,Ws), w (Cout,Cin,3,3), y (B,Cout,2Hs,2Ws).
  * dgrad returns dx at the SOURCE resolution (B,Cin,Hs,Ws) (no mogan_down2_sum).  The workspace must hold
- * mogan_upconv3x3_ws_bytes(Cout,Cin) for K (dK in wgrad) in front of the split-K scratch of the inner conv. */
+ * mogan_upconv3x3_ws_bytes(Cout,Cin) for K (dK in wgrad) in front of the split-K scratch of the inner conv; where it does not
+ * (or is NULL) fwd / dgrad / wgrad return MOGAN_ERR_WS and write nothing. */
 size_t mogan_upconv3x3_ws_bytes(int Cout, int Cin);
 /* K (Cin, Cout, 4, 4) of w alone: a caller that owns w keeps K per weight version (and, with mogan_conv_prep_*, the filter image of
  * the kernel that runs the virtual 4x4 s2 convolution) and then calls mogan_conv2d_dgrad_wp(x, K, image, y, B, Cout, 2 Hs, 2 Ws, Cin,

@@ -60,8 +60,17 @@ class Guarded:
     def bstride(self):
         return self.parent.stride(0)
 
-    def problems(self, expect=None, atol=None, exact=False):
-        """list of violated contract items (empty = all fine); expect: the slice's expected values (fp64 or exact)"""
+    def reset(self):
+        """the state before the call again (poison or base, sentinels outside), for a second call into the same buffer"""
+        _bits(self.buf).copy_(self.before)
+
+    def untouched(self):
+        """whether every element, inside and outside the slice, still holds what it held before the call (a declined call)"""
+        return bool((_bits(self.buf) == self.before).all())
+
+    def problems(self, expect=None, atol=None, exact=False, written=True):
+        """list of violated contract items (empty = all fine); expect: the slice's expected values (fp64 or exact);
+        written=False: no "never written" item (a byte image whose bytes may equal the poison pattern, or that has padding)"""
         out = []
         bits = _bits(self.buf)
         outside = (bits != self.before) & ~self.inside
@@ -71,7 +80,7 @@ class Guarded:
                        % (pos.numel(), int(pos[0]), int(pos[-1])))
         vb = _bits(self.view)
         pz = (vb == (POISON if self.dtype == torch.float32 else POISON_U8))
-        if self.base is None and bool(pz.any()):
+        if written and self.base is None and bool(pz.any()):
             out.append("%d slice elements never written (first at %s)" % (int(pz.sum()), tuple(torch.nonzero(pz)[0].tolist())))
         if expect is not None:
             got = self.view.cpu()
@@ -87,8 +96,8 @@ class Guarded:
                            % (int(bad.sum()), i, float(got[i]), float(exp[i])))
         return out
 
-    def check(self, expect=None, atol=None, exact=False, what=""):
-        p = self.problems(expect, atol, exact)
+    def check(self, expect=None, atol=None, exact=False, what="", written=True):
+        p = self.problems(expect, atol, exact, written)
         assert not p, "%s: %s" % (what, "; ".join(p))
 
 

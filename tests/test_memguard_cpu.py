@@ -77,3 +77,34 @@ def test_banded_allocation_reports_a_write_past_its_end():
     assert (u.t == mg.POISON_U8).all() and u.intact()
     u.buf[u.band - 1] = 0
     assert not u.intact()
+
+
+def test_reset_untouched_and_images_without_the_written_check():
+    g = mg.Guarded((2, 3, 4), (slice(None), slice(1, 3)), "cpu")
+    assert g.untouched()
+    g.view.fill_(2.0)
+    assert not g.untouched() and g.problems() == []
+    g.reset()                                          # poison again: a second call starts from the same state
+    assert g.untouched() and torch.isnan(g.view).all() and any("never written" in s for s in g.problems())
+    g.parent[0, 0, 0] = 1.0                            # outside the slice: touched, and reset() restores the sentinel
+    assert not g.untouched()
+    g.reset()
+    assert g.untouched() and g.problems(written=False) == []
+
+    base = torch.randn(2, 2, 4)
+    a = mg.Guarded((2, 3, 4), (slice(None), slice(1, 3)), "cpu", base=base)
+    a.view.add_(1.0)
+    a.reset()
+    assert a.untouched() and torch.equal(a.view, base)
+
+    u = mg.Guarded((16,), (Ellipsis,), "cpu", dtype=torch.uint8)     # a byte image: 0xFF is a value it may hold
+    u.view[:8] = 3
+    assert any("never written" in s for s in u.problems()) and u.problems(written=False) == []
+    u.buf[0] = 0
+    assert any("outside the slice" in s for s in u.problems(written=False))
+    try:
+        u.check(written=False, what="image")
+    except AssertionError as e:
+        assert "image" in str(e)
+    else:
+        raise AssertionError("a write into the band was not reported")
