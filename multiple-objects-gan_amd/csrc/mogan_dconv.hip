@@ -883,13 +883,11 @@ static int launch_wgrad(WGradP& p, void* ws, size_t ws_bytes, hipStream_t st) {
 
 // ---- internal entry points (hidden visibility: not part of the C ABI) ---------------------------------------
 // return 1 = handled, 0 = not eligible (caller falls back to the implicit-GEMM kernel), <0 = error
-int mogan_dconv_fwd_try(const float* x, const float* w, float* y, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW,
-                        int stride, int ph, int pw, int up, void* ws, size_t ws_bytes, hipStream_t st, const void* d2prep,
-                        size_t* d2query) {
-    const int H = Hs << up, W = Ws << up;
-    const int OH = (H + 2 * ph - KH) / stride + 1, OW = (W + 2 * pw - KW) / stride + 1;
-    const bool k33 = KH == 3 && KW == 3 && stride == 1 && ph == 1 && pw == 1;
-    const bool k44 = KH == 4 && KW == 4 && stride == 2 && ph == 1 && pw == 1 && up == 0;
+int mogan_dconv_fwd_try(const float* x, const float* w, float* y, const MoganConvShape& g, void* ws, size_t ws_bytes, hipStream_t st,
+                        const void* d2prep, size_t* d2query) {
+    const int B = g.B, Cin = g.Cin, Hs = g.Hs, Ws = g.Ws, Cout = g.Cout, KH = g.KH, KW = g.KW, ph = g.ph, pw = g.pw, up = g.up;
+    const int H = g.H, W = g.W, OH = g.OH, OW = g.OW;
+    const bool k33 = mogan_is_k33(g), k44 = mogan_is_k44(g);
     if (!(k33 || k44)) return 0;
     if (!pow2(OH) || !pow2(OW) || OW < 16 || OH < 8 || OH * std::min(32, OW) < 128) return 0;
     if ((Cin % 8) != 0 || Cout < 64 || (((uintptr_t)w) & 15) != 0) return 0;
@@ -913,13 +911,11 @@ int mogan_dconv_fwd_try(const float* x, const float* w, float* y, int B, int Cin
 }
 
 // data gradient of the same two conv families; dx is (B,Cin,H,W) in the conv-input domain
-int mogan_dconv_dgrad_try(const float* dy, const float* w, float* dx, int B, int Cin, int Hs, int Ws, int Cout, int KH,
-                          int KW, int stride, int ph, int pw, int up, void* ws, size_t ws_bytes, hipStream_t st, const void* d2prep,
-                          size_t* d2query) {
-    const int H = Hs << up, W = Ws << up;
-    const int OH = (H + 2 * ph - KH) / stride + 1, OW = (W + 2 * pw - KW) / stride + 1;
-    const bool k33 = KH == 3 && KW == 3 && stride == 1 && ph == 1 && pw == 1;
-    const bool k44 = KH == 4 && KW == 4 && stride == 2 && ph == 1 && pw == 1 && up == 0;
+int mogan_dconv_dgrad_try(const float* dy, const float* w, float* dx, const MoganConvShape& g, void* ws, size_t ws_bytes,
+                          hipStream_t st, const void* d2prep, size_t* d2query) {
+    const int B = g.B, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, ph = g.ph, pw = g.pw;
+    const int H = g.H, W = g.W, OH = g.OH, OW = g.OW;
+    const bool k33 = mogan_is_k33(g), k44 = mogan_is_k44(g);
     if (!(k33 || k44)) return 0;
     // the dgrad "forward" runs over dY (OH x OW) and produces H x W (k33) or the (H/2 x W/2) parity grids (k44)
     const int gH = k33 ? H : H / 2, gW = k33 ? W : W / 2;
@@ -963,13 +959,11 @@ int mogan_dconv_dgrad_try(const float* dy, const float* w, float* dx, int B, int
     return rc ? rc : 1;
 }
 
-int mogan_dconv_wgrad_try(const float* dy, const float* x, float* dw, int B, int Cin, int Hs, int Ws, int Cout, int KH,
-                          int KW, int stride, int ph, int pw, int up, int accumulate, void* ws, size_t ws_bytes,
-                          hipStream_t st) {
-    const int H = Hs << up, W = Ws << up;
-    const int OH = (H + 2 * ph - KH) / stride + 1, OW = (W + 2 * pw - KW) / stride + 1;
-    const bool k33 = KH == 3 && KW == 3 && stride == 1 && ph == 1 && pw == 1;
-    const bool k44 = KH == 4 && KW == 4 && stride == 2 && ph == 1 && pw == 1 && up == 0;
+int mogan_dconv_wgrad_try(const float* dy, const float* x, float* dw, const MoganConvShape& g, int accumulate, void* ws,
+                          size_t ws_bytes, hipStream_t st) {
+    const int B = g.B, Cin = g.Cin, Hs = g.Hs, Ws = g.Ws, Cout = g.Cout, KH = g.KH, KW = g.KW, ph = g.ph, pw = g.pw, up = g.up;
+    const int H = g.H, W = g.W, OH = g.OH, OW = g.OW;
+    const bool k33 = mogan_is_k33(g), k44 = mogan_is_k44(g);
     if (!(k33 || k44)) return 0;
     if (!pow2(OH) || !pow2(OW) || OW < 16 || OH < 4 || Cout < 64 || Cin * KH * KW < 256) return 0;
     if ((((uintptr_t)dy) & 15) != 0) return 0;

@@ -948,28 +948,113 @@ static int run_group(int mode, GemmP* ps, const int* nz, int n, hipStream_t st) 
     return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH;
 }
 
-static int conv_geom(GemmP& p, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW, int s, int ph, int pw, int up) {
+// The ONE place a convolution's shape is validated and its derived dims are computed (MoganConvShape, mogan_internal.h):
+// every convolution entry point starts here, the try functions of the other translation units read the result.
+static int conv_geom(MoganConvShape& g, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW, int s, int ph, int pw, int up) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || Hs <= 0 || Ws <= 0 || KH <= 0 || KW <= 0 || s <= 0 || up < 0 || up > 1)
         return MOGAN_ERR_SHAPE;
-    p.Bn = B; p.Cin = Cin; p.Cout = Cout; p.Hs = Hs; p.Ws = Ws; p.up = up;
-    p.H = Hs << up; p.W = Ws << up; p.KH = KH; p.KW = KW; p.s = s; p.ph = ph; p.pw = pw;
-    p.OH = (p.H + 2 * ph - KH) / s + 1; p.OW = (p.W + 2 * pw - KW) / s + 1;
-    if (p.OH <= 0 || p.OW <= 0) return MOGAN_ERR_SHAPE;
-    p.fd_ohw = make_fd(p.OH * p.OW); p.fd_ow = make_fd(p.OW);
-    p.fd_khw = make_fd(KH * KW); p.fd_kw = make_fd(KW);
-    p.nkh = (KH + s - 1) / s; p.nkw = (KW + s - 1) / s;
-    p.fd_nk = make_fd(p.nkh * p.nkw); p.fd_nkw = make_fd(p.nkw);
-    if ((long long)B * Cin * p.H * p.W >= (1ll << 30) || (long long)B * Cout * p.OH * p.OW >= (1ll << 30) ||
+    g = MoganConvShape{B, Cin, Hs, Ws, Cout, KH, KW, s, ph, pw, up, Hs << up, Ws << up, 0, 0};
+    g.OH = (g.H + 2 * ph - KH) / s + 1; g.OW = (g.W + 2 * pw - KW) / s + 1;
+    if (g.OH <= 0 || g.OW <= 0) return MOGAN_ERR_SHAPE;
+    if ((long long)B * Cin * g.H * g.W >= (1ll << 30) || (long long)B * Cout * g.OH * g.OW >= (1ll << 30) ||
         (long long)Cout * Cin * KH * KW >= (1ll << 30))
         return MOGAN_ERR_SHAPE;
     return 0;
 }
 
-// dense defaults of the strided-I/O fields (after M / the gathered operand are known)
-static void dense_io(GemmP& p, int mode) {
-    if (mode == CONV_FWD) { p.xbs = (unsigned)p.Cin * p.Hs * p.Ws; p.ybs = (long long)p.Cout * p.OH * p.OW; }
-    else { p.xbs = (unsigned)p.Cout * p.OH * p.OW; p.ybs = (long long)p.Cin * p.H * p.W; }
-    p.C2 = nullptr; p.ybs2 = 0; p.msplit = 0x7fffffff; p.mask = nullptr; p.mbs = 0;
+// a fresh GemmP with the geometry the kernel's gather modes decode (and their fast divisors) ...
+static void gemm_geom(GemmP& p, const MoganConvShape& g) {
+    p = GemmP{};
+    p.Bn = g.B; p.Cin = g.Cin; p.Cout = g.Cout; p.Hs = g.Hs; p.Ws = g.Ws; p.up = g.up;
+    p.H = g.H; p.W = g.W; p.KH = g.KH; p.KW = g.KW; p.s = g.stride; p.ph = g.ph; p.pw = g.pw; p.OH = g.OH; p.OW = g.OW;
+    p.fd_ohw = make_fd(g.OH * g.OW); p.fd_ow = make_fd(g.OW);
+    p.fd_khw = make_fd(g.KH * g.KW); p.fd_kw = make_fd(g.KW);
+    p.nkh = (g.KH + g.stride - 1) / g.stride; p.nkw = (g.KW + g.stride - 1) / g.stride;
+    p.fd_nk = make_fd(p.nkh * p.nkw); p.fd_nkw = make_fd(p.nkw);
+}
+// ... and its launch once A / B / C and the GEMM dims are filled in: the z-batches (the stride-parity classes of a data gradient)
+// and the size of the result follow from the geometry
+static int run_conv(int mode, GemmP& p, void* ws, size_t ws_bytes, hipStream_t st) {
+    const long long numel = mode == CONV_FWD     ? (long long)p.Bn * p.Cout * p.OH * p.OW
+                            : mode == CONV_DGRAD ? (long long)p.Bn * p.Cin * p.H * p.W
+                                                 : (long long)p.Cout * p.Cin * p.KH * p.KW;
+    return run_gemm(mode, p, mode == CONV_DGRAD ? p.s * p.s : 1, numel, ws, ws_bytes, st);
+}
+
+// ---- the forward and the data-gradient problem ------------------------------------------------------------------------------
+// What a convolution may carry beyond the dense y = conv(x, w) / dx = conv^T(dy, w); everything is off by default.
+struct ConvExtra {
+    // channel-slice addressing (slices of larger NCHW tensors): batch strides, in elements, of the gathered operand (x / dy) and of
+    // the result (y / dx).  !sliced: both dense, the two strides are not looked at.  Forward only: out_bstride < 0 = dense
+    bool sliced = false; long long in_bstride = 0, out_bstride = -1;
+    const float* relu_of = nullptr; long long relu_bstride = 0;         // zero the NEW result where relu_of <= 0 (shaped like it)
+    int accumulate = 0;                                                 // add to y / dx
+    // forward only
+    float* y2 = nullptr; long long y2_bstride = 0; int msplit = 0;      // 0 < msplit < Cout: output channels >= msplit go to y2
+    const float* scale = nullptr; const float* shift = nullptr; int relu = 0;   // epilogue y = act(scale[m] * y + shift[m])
+    float slope = 0.f;                                                  // epilogue y = LeakyReLU_slope(y) (> 0, without scale)
+};
+
+// THE GemmP of a forward convolution (every scalar entry point and the grouped launch); 0 or an error.
+// There is NO lower bound on y_bstride here: with msplit, y holds only the first msplit channels, so Cout*OH*OW would refuse
+// valid calls of the trunk (mogan_conv2d_fwd_ex, which has one output, checks its own).
+static int build_fwd(GemmP& p, const MoganConvShape& g, const float* x, const float* w, float* y, const ConvExtra& e) {
+    const long long xd = (long long)g.Cin * g.Hs * g.Ws, yd = (long long)g.Cout * g.OH * g.OW;
+    const long long xbs = e.sliced ? e.in_bstride : xd, ybs = e.sliced && e.out_bstride >= 0 ? e.out_bstride : yd;
+    if (xbs < xd || (long long)(g.B - 1) * xbs + xd >= (1ll << 30)) return MOGAN_ERR_SHAPE;
+    gemm_geom(p, g);
+    p.A = w; p.B = x; p.C = y; p.M = g.Cout; p.N = g.B * g.OH * g.OW; p.K = g.Cin * g.KH * g.KW; p.accumulate = e.accumulate;
+    // extent of x from the strides; for a dense x this is B * Cin * Hs * Ws
+    p.a_bytes = 4u * g.Cout * g.Cin * g.KH * g.KW; p.b_bytes = 4u * (unsigned)((long long)(g.B - 1) * xbs + xd);
+    p.avec = (p.K % 4 == 0) && (((uintptr_t)w & 15) == 0);
+    p.ep_scale = e.scale; p.ep_shift = e.shift; p.ep_relu = e.relu; p.ep_slope = e.slope;
+    p.xbs = (unsigned)xbs; p.ybs = ybs; p.mask = e.relu_of; p.mbs = e.relu_bstride; p.msplit = 0x7fffffff;
+    if (e.y2 != nullptr && e.msplit > 0 && e.msplit < g.Cout) { p.C2 = e.y2; p.ybs2 = e.y2_bstride; p.msplit = e.msplit; }
+    return 0;
+}
+static int gemm_fwd(const MoganConvShape& g, const float* x, const float* w, float* y, const ConvExtra& e, void* ws, size_t ws_bytes,
+                    hipStream_t st) {
+    GemmP p; const int rc = build_fwd(p, g, x, w, y, e);
+    return rc ? rc : run_conv(CONV_FWD, p, ws, ws_bytes, st);
+}
+
+// THE GemmP of a data gradient.  dx is the gradient w.r.t. the conv input in the (upsampled) H x W domain: (B,Cin,H,W).
+// A strided parity class that has no tap (stride > kernel) would leave its pixels unwritten.  That is NOT refused here: the plain
+// chain (mogan_conv2d_dgrad) never has refused it, the slice forms do (prep_dgrad) -- a difference kept as it was found.
+static int build_dgrad(GemmP& p, const MoganConvShape& g, const float* dy, const float* w, float* dx, const ConvExtra& e) {
+    const long long yd = (long long)g.Cout * g.OH * g.OW, xd = (long long)g.Cin * g.H * g.W;
+    const long long ybs = e.sliced ? e.in_bstride : yd, xbs = e.sliced ? e.out_bstride : xd;
+    if (ybs < yd || xbs < xd || (long long)(g.B - 1) * ybs + yd >= (1ll << 30)) return MOGAN_ERR_SHAPE;
+    gemm_geom(p, g);
+    p.A = w; p.B = dy; p.C = dx; p.M = g.Cin; p.K = g.Cout * p.nkh * p.nkw; p.accumulate = e.accumulate;
+    // extent of dy from the strides; for a dense dy this is B * Cout * OH * OW
+    p.a_bytes = 4u * g.Cout * g.Cin * g.KH * g.KW; p.b_bytes = 4u * (unsigned)((long long)(g.B - 1) * ybs + yd);
+    const int Hc = (g.H + g.stride - 1) / g.stride, Wc = (g.W + g.stride - 1) / g.stride;
+    p.N = g.B * Hc * Wc;   // class (0,0) has the most columns
+    p.xbs = (unsigned)ybs; p.ybs = xbs; p.mask = e.relu_of; p.mbs = e.relu_bstride; p.msplit = 0x7fffffff;
+    return 0;
+}
+
+// ---- dispatch stages -------------------------------------------------------------------------------------------------------------
+// the profile record that brackets a stage: its mode column (mogan_prof_dump) = the direction, NO_PROF = no record
+enum { NO_PROF = -1, PROF_FWD = 4, PROF_DGRAD = 5, PROF_WGRAD = 6 };
+enum { K_DIRECT = 0, K_WINO = 1 };      // ... and its cfg column = the kernel family
+// One stage of a dispatch chain, "try a faster kernel first": attempt() returns 1 = handled, 0 = geometry not eligible, < 0 = error.
+// true: the chain ends here and returns rc (0 or the error); false: on to the next stage.
+template <class Attempt>
+static bool stage(int& rc, int prof, int kernel, const MoganConvShape& g, hipStream_t st, Attempt attempt) {
+    if (prof != NO_PROF) {         // recorded with the M, N, K of the implicit GEMM the stage stands in for
+        // algorithmic FLOPs of a convolution, any direction; Winograd: the multiplies F(2x2,3x3) executes, 16 per 2x2 outputs, not 36
+        const double fl = (kernel == K_WINO ? 4.0 / 9.0 : 1.0) * 2.0 * g.Cout * (double)g.B * g.OH * g.OW * g.Cin * g.KH * g.KW;
+        const int px = g.B * g.OH * g.OW, ck = g.Cin * g.KH * g.KW;
+        if (prof == PROF_FWD) mogan_prof_begin(prof, kernel, fl, g.Cout, px, ck, st);
+        else if (prof == PROF_DGRAD) mogan_prof_begin(prof, kernel, fl, g.Cin, g.B * g.H * g.W, g.Cout * g.KH * g.KW, st);
+        else mogan_prof_begin(prof, kernel, fl, g.Cout, ck, px, st);
+    }
+    const int r = attempt();
+    if (prof != NO_PROF) mogan_prof_end(r == 1, st);
+    rc = r < 0 ? r : 0;
+    return r != 0;
 }
 
 }  // namespace
@@ -1082,35 +1167,21 @@ int mogan_conv2d_fwd(const float* x, const float* w, float* y, int B, int Cin, i
 
 int mogan_conv2d_fwd_wp(const float* x, const float* w, const void* wprep, float* y, int B, int Cin, int Hs, int Ws, int Cout, int KH,
                         int KW, int stride, int ph, int pw, int up, void* ws, size_t ws_bytes, hipStream_t stream) {
-    GemmP p{}; int rc = conv_geom(p, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up); if (rc) return rc;
-    if (g_force_cfg < 0) {          // <= 4 output channels: HBM streaming work, direct VALU kernel
-        rc = mogan_smallc_fwd_try(x, w, y, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    if (g_force_cfg < 0 && up == 0) {   // 3 input channels, 4x4 s2: the discriminators' first layer as a streaming kernel (mogan_stem.hip)
-        rc = mogan_stem_fwd_try(x, w, y, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 1.f, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    if (g_force_cfg == -1) {        // 3x3 s1 p1 at >= 32 channels: fused Winograd F(2x2,3x3), 2.25x fewer multiplies (-2: test hook, off)
-        // (recorded flops = the multiplies the kernel executes: 16 per 2x2 outputs instead of 36)
-        mogan_prof_begin(4, 1, (4.0 / 9.0) * 2.0 * Cout * (double)B * p.OH * p.OW * Cin * KH * KW, Cout, B * p.OH * p.OW, Cin * KH * KW, stream);
-        rc = mogan_wino_try(x, w, wprep, y, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, 0, nullptr, nullptr, 0, ws, ws_bytes, stream);
-        mogan_prof_end(rc == 1, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    if (mogan_use_dconv && g_force_cfg < 0) {
-        mogan_prof_begin(4, 0, 2.0 * Cout * (double)B * p.OH * p.OW * Cin * KH * KW, Cout, B * p.OH * p.OW, Cin * KH * KW, stream);
-        // (the image of a 4x4 s2 convolution is dconv2_fwd_kernel's: mogan_conv_prep_bytes)
-        rc = mogan_dconv_fwd_try(x, w, y, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, ws, ws_bytes, stream,
-                                 (KH == 4 && KW == 4 && stride == 2) ? wprep : nullptr);
-        mogan_prof_end(rc == 1, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    p.A = w; p.B = x; p.C = y; p.M = Cout; p.N = B * p.OH * p.OW; p.K = Cin * KH * KW; p.accumulate = 0;
-    p.a_bytes = 4u * Cout * Cin * KH * KW; p.b_bytes = 4u * B * Cin * Hs * Ws;
-    p.avec = (p.K % 4 == 0) && (((uintptr_t)w & 15) == 0);
-    dense_io(p, CONV_FWD);
-    return run_gemm(CONV_FWD, p, 1, (long long)B * Cout * p.OH * p.OW, ws, ws_bytes, stream);
+    MoganConvShape g; int rc = conv_geom(g, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up); if (rc) return rc;
+    // <= 4 output channels: HBM streaming work, direct VALU kernel
+    if (g_force_cfg < 0 && stage(rc, NO_PROF, K_DIRECT, g, stream, [&] { return mogan_smallc_fwd_try(x, w, y, g, stream); })) return rc;
+    // 3 input channels, 4x4 s2: the discriminators' first layer as a streaming kernel (mogan_stem.hip)
+    if (g_force_cfg < 0 && up == 0 && stage(rc, NO_PROF, K_DIRECT, g, stream, [&] { return mogan_stem_fwd_try(x, w, y, g, 1.f, stream); }))
+        return rc;
+    // 3x3 s1 p1 at >= 32 channels: fused Winograd F(2x2,3x3), 2.25x fewer multiplies (-2: test hook, off)
+    if (g_force_cfg == -1 && stage(rc, PROF_FWD, K_WINO, g, stream, [&] {
+            return mogan_wino_try(x, w, wprep, y, g, 0, nullptr, nullptr, 0, ws, ws_bytes, stream); }))
+        return rc;
+    // (the image of a 4x4 s2 convolution is dconv2_fwd_kernel's: mogan_conv_prep_bytes)
+    if (mogan_use_dconv && g_force_cfg < 0 && stage(rc, PROF_FWD, K_DIRECT, g, stream, [&] {
+            return mogan_dconv_fwd_try(x, w, y, g, ws, ws_bytes, stream, (KH == 4 && KW == 4 && stride == 2) ? wprep : nullptr); }))
+        return rc;
+    return gemm_fwd(g, x, w, y, ConvExtra{}, ws, ws_bytes, stream);
 }
 
 // conv + LeakyReLU in the epilogue of the implicit-GEMM kernel (or of its split-K reduction): the first layer of every
@@ -1119,21 +1190,74 @@ int mogan_conv2d_fwd_wp(const float* x, const float* w, const void* wprep, float
 // caller then runs mogan_conv2d_fwd + mogan_act_fwd).
 int mogan_conv2d_lrelu_fwd(const float* x, const float* w, float* z, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW,
                            int stride, int ph, int pw, float slope, void* ws, size_t ws_bytes, hipStream_t stream) {
-    GemmP p{}; int rc = conv_geom(p, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 0); if (rc) return rc;
+    MoganConvShape g; int rc = conv_geom(g, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 0); if (rc) return rc;
     if (!(slope > 0.f)) return MOGAN_ERR_SHAPE;
     // only layers the dispatch of mogan_conv2d_fwd would hand to the implicit-GEMM kernel anyway: few input channels
     if (Cin > 16 || Cout <= 4) return 1;
-    if (g_force_cfg < 0) {
-        rc = mogan_stem_fwd_try(x, w, z, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, slope, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    p.A = w; p.B = x; p.C = z; p.M = Cout; p.N = B * p.OH * p.OW; p.K = Cin * KH * KW; p.accumulate = 0;
-    p.a_bytes = 4u * Cout * Cin * KH * KW; p.b_bytes = 4u * B * Cin * Hs * Ws;
-    p.avec = (p.K % 4 == 0) && (((uintptr_t)w & 15) == 0);
-    p.ep_slope = slope;
-    dense_io(p, CONV_FWD);
-    return run_gemm(CONV_FWD, p, 1, (long long)B * Cout * p.OH * p.OW, ws, ws_bytes, stream);
+    if (g_force_cfg < 0 && stage(rc, NO_PROF, K_DIRECT, g, stream, [&] { return mogan_stem_fwd_try(x, w, z, g, slope, stream); })) return rc;
+    ConvExtra e; e.slope = slope;
+    return gemm_fwd(g, x, w, z, e, ws, ws_bytes, stream);
 }
+
+}  // extern "C"
+namespace {
+// GemmP of one member of the slice / affine forward form (the arguments of mogan_conv2d_affine_fwd_ex); 0 or an error
+static int prep_fwd(GemmP& p, MoganConvShape& g, const MoganConvFwdArgs& a) {
+    const int rc = conv_geom(g, a.B, a.Cin, a.Hs, a.Ws, a.Cout, a.KH, a.KW, a.stride, a.ph, a.pw, 0); if (rc) return rc;
+    if (!a.scale || !a.shift) return MOGAN_ERR_SHAPE;
+    ConvExtra e;
+    e.sliced = true; e.in_bstride = a.x_bstride; e.out_bstride = a.y_bstride;
+    e.y2 = a.y2; e.y2_bstride = a.y2_bstride; e.msplit = a.msplit;
+    e.scale = a.scale; e.shift = a.shift; e.relu = a.relu;
+    return build_fwd(p, g, a.x, a.w, a.y, e);
+}
+// ... run on its own: tile heuristics, split-K, and the one fast-path stage of this form
+static int affine_fwd_one(const MoganConvFwdArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+    MoganConvShape g; GemmP p; int rc = prep_fwd(p, g, a); if (rc) return rc;
+    const bool plain = a.x_bstride == (long long)a.Cin * a.Hs * a.Ws && p.ybs == (long long)a.Cout * g.OH * g.OW && !p.C2;
+    // the trunk's 3x3 s1 layers on well-filled grids (147x147, 71x71): fused Winograd (dense, one output; no prepared image)
+    if (plain && g_force_cfg < 0 && stage(rc, PROF_FWD, K_WINO, g, st, [&] {
+            return mogan_wino_try(a.x, a.w, nullptr, a.y, g, 0, a.scale, a.shift, a.relu, ws, ws_bytes, st); }))
+        return rc;
+    return run_conv(CONV_FWD, p, ws, ws_bytes, st);
+}
+// GemmP of one member of the slice data-gradient form (the arguments of mogan_conv2d_dgrad_ex; g = its shape); 0 or an error
+static int prep_dgrad(GemmP& p, const MoganConvShape& g, const MoganConvDgradArgs& a) {
+    // a strided parity class that has no tap (stride > kernel) would leave its pixels unwritten: not used by the trunk
+    if (a.stride > a.KH || a.stride > a.KW) return MOGAN_ERR_SHAPE;
+    ConvExtra e;
+    e.sliced = true; e.in_bstride = a.dy_bstride; e.out_bstride = a.dx_bstride;
+    e.relu_of = a.relu_of; e.relu_bstride = a.relu_bstride; e.accumulate = a.accumulate;
+    return build_dgrad(p, g, a.dy, a.w, a.dx, e);
+}
+// the dispatch chain of the plain data gradient (mogan_conv2d_dgrad / _wp)
+static int dgrad_chain(const MoganConvShape& g, const float* dy, const float* w, const void* wprep, float* dx, void* ws, size_t ws_bytes,
+                       hipStream_t st) {
+    int rc;
+    // <= 4 channels on one side (image heads, first D convolution)
+    if (g_force_cfg < 0 && stage(rc, NO_PROF, K_DIRECT, g, st, [&] { return mogan_smallc_dgrad_try(dy, w, dx, g, st); })) return rc;
+    if (g_force_cfg == -1 && stage(rc, PROF_DGRAD, K_WINO, g, st, [&] {
+            return mogan_wino_try(dy, w, wprep, dx, g, 1, nullptr, nullptr, 0, ws, ws_bytes, st); }))
+        return rc;
+    if (mogan_use_dconv && g_force_cfg < 0 && stage(rc, PROF_DGRAD, K_DIRECT, g, st, [&] {
+            return mogan_dconv_dgrad_try(dy, w, dx, g, ws, ws_bytes, st, (g.KH == 4 && g.KW == 4 && g.stride == 2) ? wprep : nullptr); }))
+        return rc;
+    GemmP p; rc = build_dgrad(p, g, dy, w, dx, ConvExtra{});
+    return rc ? rc : run_conv(CONV_DGRAD, p, ws, ws_bytes, st);
+}
+// ... run on its own
+static int dgrad_one(const MoganConvDgradArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+    MoganConvShape g; int rc = conv_geom(g, a.B, a.Cin, a.Hs, a.Ws, a.Cout, a.KH, a.KW, a.stride, a.ph, a.pw, 0); if (rc) return rc;
+    // a dense call without mask and without accumulate IS the plain data gradient and takes its whole chain -- before prep_dgrad's
+    // stride > kernel rejection, which therefore holds for every other call only (prep_dgrad itself, i.e. a group of two or more,
+    // refuses unconditionally)
+    if (a.dy_bstride == (long long)a.Cout * g.OH * g.OW && a.dx_bstride == (long long)a.Cin * a.Hs * a.Ws && !a.relu_of && !a.accumulate)
+        return dgrad_chain(g, a.dy, a.w, nullptr, a.dx, ws, ws_bytes, st);
+    GemmP p; rc = prep_dgrad(p, g, a);
+    return rc ? rc : run_conv(CONV_DGRAD, p, ws, ws_bytes, st);
+}
+}  // namespace
+extern "C" {
 
 // conv + per-channel affine (+ ReLU) in the epilogue of the implicit-GEMM kernel (or of its split-K reduction): the
 // BasicConv2d of the frozen Inception trunk = conv, eval-mode BN, ReLU (model.py:258-299) in one pass over the output
@@ -1153,27 +1277,9 @@ int mogan_conv2d_affine_fwd_ex(const float* x, long long x_bstride, const float*
                                float* y, long long y_bstride, float* y2, long long y2_bstride, int msplit, int B, int Cin,
                                int Hs, int Ws, int Cout, int KH, int KW, int stride, int ph, int pw, int relu, void* ws,
                                size_t ws_bytes, hipStream_t stream) {
-    GemmP p{}; int rc = conv_geom(p, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 0); if (rc) return rc;
-    if (!scale || !shift) return MOGAN_ERR_SHAPE;
-    const long long xd = (long long)Cin * Hs * Ws, yd = (long long)Cout * p.OH * p.OW;
-    if (y_bstride < 0) y_bstride = yd;
-    const bool two = y2 != nullptr && msplit > 0 && msplit < Cout;
-    const bool plain = x_bstride == xd && y_bstride == yd && !two;
-    if (x_bstride < xd || (long long)(B - 1) * x_bstride + xd >= (1ll << 30)) return MOGAN_ERR_SHAPE;
-    if (plain && g_force_cfg < 0) {          // the trunk's 3x3 s1 layers on well-filled grids (147x147, 71x71): fused Winograd
-        mogan_prof_begin(4, 1, (4.0 / 9.0) * 2.0 * Cout * (double)B * p.OH * p.OW * Cin * KH * KW, Cout, B * p.OH * p.OW, Cin * KH * KW, stream);
-        rc = mogan_wino_try(x, w, nullptr, y, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 0, 0, scale, shift, relu, ws, ws_bytes, stream);
-        mogan_prof_end(rc == 1, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    p.A = w; p.B = x; p.C = y; p.M = Cout; p.N = B * p.OH * p.OW; p.K = Cin * KH * KW; p.accumulate = 0;
-    p.a_bytes = 4u * Cout * Cin * KH * KW; p.b_bytes = 4u * (unsigned)((long long)(B - 1) * x_bstride + xd);
-    p.avec = (p.K % 4 == 0) && (((uintptr_t)w & 15) == 0);
-    p.ep_scale = scale; p.ep_shift = shift; p.ep_relu = relu;
-    dense_io(p, CONV_FWD);
-    p.xbs = (unsigned)x_bstride; p.ybs = y_bstride;
-    if (two) { p.C2 = y2; p.ybs2 = y2_bstride; p.msplit = msplit; }
-    return run_gemm(CONV_FWD, p, 1, (long long)B * Cout * p.OH * p.OW, ws, ws_bytes, stream);
+    const MoganConvFwdArgs a{x, x_bstride, w, scale, shift, y, y_bstride, y2, y2_bstride, msplit,
+                             B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, relu};
+    return affine_fwd_one(a, ws, ws_bytes, stream);
 }
 
 // Plain forward convolution with channel-slice addressing, a ReLU mask on the result and accumulation: the data
@@ -1181,71 +1287,29 @@ int mogan_conv2d_affine_fwd_ex(const float* x, long long x_bstride, const float*
 // transposed filters (pad' = K - 1 - pad).  In the implicit GEMM's forward mode the filter operand is K-contiguous
 // (16-byte coalesced loads); its data-gradient mode has to gather W[co][ci][tap] with a stride of KH*KW floats between
 // consecutive rows.  For FROZEN weights the flipped copy is made once (attngan/inception.py).
+// No fast-path stage: always the implicit GEMM.
 int mogan_conv2d_fwd_ex(const float* x, long long x_bstride, const float* w, float* y, long long y_bstride,
                         const float* relu_of, long long relu_bstride, int accumulate, int B, int Cin, int Hs, int Ws,
                         int Cout, int KH, int KW, int stride, int ph, int pw, void* ws, size_t ws_bytes, hipStream_t stream) {
-    GemmP p{}; int rc = conv_geom(p, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 0); if (rc) return rc;
-    const long long xd = (long long)Cin * Hs * Ws, yd = (long long)Cout * p.OH * p.OW;
-    if (y_bstride < 0) y_bstride = yd;
-    if (x_bstride < xd || y_bstride < yd || (long long)(B - 1) * x_bstride + xd >= (1ll << 30)) return MOGAN_ERR_SHAPE;
-    p.A = w; p.B = x; p.C = y; p.M = Cout; p.N = B * p.OH * p.OW; p.K = Cin * KH * KW; p.accumulate = accumulate;
-    p.a_bytes = 4u * Cout * Cin * KH * KW; p.b_bytes = 4u * (unsigned)((long long)(B - 1) * x_bstride + xd);
-    p.avec = (p.K % 4 == 0) && (((uintptr_t)w & 15) == 0);
-    dense_io(p, CONV_FWD);
-    p.xbs = (unsigned)x_bstride; p.ybs = y_bstride; p.mask = relu_of; p.mbs = relu_bstride;
-    return run_gemm(CONV_FWD, p, 1, (long long)B * Cout * p.OH * p.OW, ws, ws_bytes, stream);
+    MoganConvShape g; int rc = conv_geom(g, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 0); if (rc) return rc;
+    // one output tensor, all Cout channels: this form (and only this one, see build_fwd) bounds y_bstride from below
+    if (y_bstride >= 0 && y_bstride < (long long)Cout * g.OH * g.OW) return MOGAN_ERR_SHAPE;
+    ConvExtra e;
+    e.sliced = true; e.in_bstride = x_bstride; e.out_bstride = y_bstride;
+    e.relu_of = relu_of; e.relu_bstride = relu_bstride; e.accumulate = accumulate;
+    return gemm_fwd(g, x, w, y, e, ws, ws_bytes, stream);
 }
-
-}  // extern "C"
-namespace {
-// GemmP of one strided / fused forward convolution (the arguments of mogan_conv2d_affine_fwd_ex); 0 or an error
-static int prep_fwd(GemmP& p, const MoganConvFwdArgs& a) {
-    int rc = conv_geom(p, a.B, a.Cin, a.Hs, a.Ws, a.Cout, a.KH, a.KW, a.stride, a.ph, a.pw, 0); if (rc) return rc;
-    if (!a.scale || !a.shift) return MOGAN_ERR_SHAPE;
-    const long long xd = (long long)a.Cin * a.Hs * a.Ws, yd = (long long)a.Cout * p.OH * p.OW;
-    const long long ybs = a.y_bstride < 0 ? yd : a.y_bstride;
-    if (a.x_bstride < xd || (long long)(a.B - 1) * a.x_bstride + xd >= (1ll << 30)) return MOGAN_ERR_SHAPE;
-    p.A = a.w; p.B = a.x; p.C = a.y; p.M = a.Cout; p.N = a.B * p.OH * p.OW; p.K = a.Cin * a.KH * a.KW; p.accumulate = 0;
-    p.a_bytes = 4u * a.Cout * a.Cin * a.KH * a.KW; p.b_bytes = 4u * (unsigned)((long long)(a.B - 1) * a.x_bstride + xd);
-    p.avec = (p.K % 4 == 0) && (((uintptr_t)a.w & 15) == 0);
-    p.ep_scale = a.scale; p.ep_shift = a.shift; p.ep_relu = a.relu;
-    dense_io(p, CONV_FWD);
-    p.xbs = (unsigned)a.x_bstride; p.ybs = ybs;
-    if (a.y2 != nullptr && a.msplit > 0 && a.msplit < a.Cout) { p.C2 = a.y2; p.ybs2 = a.y2_bstride; p.msplit = a.msplit; }
-    return 0;
-}
-static int prep_dgrad(GemmP& p, const MoganConvDgradArgs& a, int* nz) {
-    int rc = conv_geom(p, a.B, a.Cin, a.Hs, a.Ws, a.Cout, a.KH, a.KW, a.stride, a.ph, a.pw, 0); if (rc) return rc;
-    const long long yd = (long long)a.Cout * p.OH * p.OW, xd = (long long)a.Cin * a.Hs * a.Ws;
-    if (a.dy_bstride < yd || a.dx_bstride < xd || (long long)(a.B - 1) * a.dy_bstride + yd >= (1ll << 30)) return MOGAN_ERR_SHAPE;
-    if (a.stride > a.KH || a.stride > a.KW) return MOGAN_ERR_SHAPE;
-    p.A = a.w; p.B = a.dy; p.C = a.dx; p.M = a.Cin; p.K = a.Cout * p.nkh * p.nkw; p.accumulate = a.accumulate;
-    p.a_bytes = 4u * a.Cout * a.Cin * a.KH * a.KW; p.b_bytes = 4u * (unsigned)((long long)(a.B - 1) * a.dy_bstride + yd);
-    const int Hc = (p.H + a.stride - 1) / a.stride, Wc = (p.W + a.stride - 1) / a.stride;
-    p.N = a.B * Hc * Wc;
-    dense_io(p, CONV_DGRAD);
-    p.xbs = (unsigned)a.dy_bstride; p.ybs = a.dx_bstride; p.mask = a.relu_of; p.mbs = a.relu_bstride;
-    *nz = a.stride * a.stride;
-    return 0;
-}
-}  // namespace
-extern "C" {
 
 // n <= 4 independent forward convolutions (arguments as mogan_conv2d_affine_fwd_ex) in ONE launch, no split-K.  The outputs
-// must not overlap.  n == 1 falls back to the single-problem entry point (tile heuristics, split-K).
+// must not overlap.  n == 1, and a group too small to fill the chip, run member by member (tile heuristics, split-K).
 int mogan_conv2d_affine_fwd_group(int n, const MoganConvFwdArgs* args, void* ws, size_t ws_bytes, hipStream_t stream) {
     if (n <= 0 || n > MAXG || !args) return MOGAN_ERR_SHAPE;
-    if (n == 1) {
-        const MoganConvFwdArgs& a = args[0];
-        return mogan_conv2d_affine_fwd_ex(a.x, a.x_bstride, a.w, a.scale, a.shift, a.y, a.y_bstride, a.y2, a.y2_bstride, a.msplit,
-                                          a.B, a.Cin, a.Hs, a.Ws, a.Cout, a.KH, a.KW, a.stride, a.ph, a.pw, a.relu, ws, ws_bytes,
-                                          stream);
-    }
+    if (n == 1) return affine_fwd_one(args[0], ws, ws_bytes, stream);
     GemmP ps[MAXG]; int nz[MAXG];
-    for (int i = 0; i < n; ++i) { ps[i] = GemmP{}; int rc = prep_fwd(ps[i], args[i]); if (rc) return rc; nz[i] = 1; }
+    for (int i = 0; i < n; ++i) { MoganConvShape g; int rc = prep_fwd(ps[i], g, args[i]); if (rc) return rc; nz[i] = 1; }
     int rc = run_group(CONV_FWD, ps, nz, n, stream);
     if (rc != 1) return rc;
-    for (int i = 0; i < n; ++i) { rc = mogan_conv2d_affine_fwd_group(1, args + i, ws, ws_bytes, stream); if (rc) return rc; }
+    for (int i = 0; i < n; ++i) { rc = affine_fwd_one(args[i], ws, ws_bytes, stream); if (rc) return rc; }
     return 0;
 }
 
@@ -1253,16 +1317,18 @@ int mogan_conv2d_affine_fwd_group(int n, const MoganConvFwdArgs* args, void* ws,
 // write (or accumulate into) the same dx elements.
 int mogan_conv2d_dgrad_group(int n, const MoganConvDgradArgs* args, void* ws, size_t ws_bytes, hipStream_t stream) {
     if (n <= 0 || n > MAXG || !args) return MOGAN_ERR_SHAPE;
-    if (n == 1) {
-        const MoganConvDgradArgs& a = args[0];
-        return mogan_conv2d_dgrad_ex(a.dy, a.dy_bstride, a.w, a.dx, a.dx_bstride, a.relu_of, a.relu_bstride, a.accumulate, a.B,
-                                     a.Cin, a.Hs, a.Ws, a.Cout, a.KH, a.KW, a.stride, a.ph, a.pw, ws, ws_bytes, stream);
-    }
+    if (n == 1) return dgrad_one(args[0], ws, ws_bytes, stream);
     GemmP ps[MAXG]; int nz[MAXG];
-    for (int i = 0; i < n; ++i) { ps[i] = GemmP{}; int rc = prep_dgrad(ps[i], args[i], &nz[i]); if (rc) return rc; }
+    for (int i = 0; i < n; ++i) {
+        const MoganConvDgradArgs& a = args[i];
+        MoganConvShape g; int rc = conv_geom(g, a.B, a.Cin, a.Hs, a.Ws, a.Cout, a.KH, a.KW, a.stride, a.ph, a.pw, 0);
+        if (!rc) rc = prep_dgrad(ps[i], g, a);
+        if (rc) return rc;
+        nz[i] = a.stride * a.stride;
+    }
     int rc = run_group(CONV_DGRAD, ps, nz, n, stream);
     if (rc != 1) return rc;
-    for (int i = 0; i < n; ++i) { rc = mogan_conv2d_dgrad_group(1, args + i, ws, ws_bytes, stream); if (rc) return rc; }
+    for (int i = 0; i < n; ++i) { rc = dgrad_one(args[i], ws, ws_bytes, stream); if (rc) return rc; }
     return 0;
 }
 
@@ -1273,31 +1339,8 @@ int mogan_conv2d_dgrad(const float* dy, const float* w, float* dx, int B, int Ci
 
 int mogan_conv2d_dgrad_wp(const float* dy, const float* w, const void* wprep, float* dx, int B, int Cin, int Hs, int Ws, int Cout,
                           int KH, int KW, int stride, int ph, int pw, int up, void* ws, size_t ws_bytes, hipStream_t stream) {
-    GemmP p{}; int rc = conv_geom(p, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up); if (rc) return rc;
-    if (g_force_cfg < 0) {          // <= 4 channels on one side (image heads, first D convolution)
-        rc = mogan_smallc_dgrad_try(dy, w, dx, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    if (g_force_cfg == -1) {
-        mogan_prof_begin(5, 1, (4.0 / 9.0) * 2.0 * Cout * (double)B * p.OH * p.OW * Cin * KH * KW, Cin, B * p.H * p.W, Cout * KH * KW, stream);
-        rc = mogan_wino_try(dy, w, wprep, dx, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, 1, nullptr, nullptr, 0, ws, ws_bytes, stream);
-        mogan_prof_end(rc == 1, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    if (mogan_use_dconv && g_force_cfg < 0) {
-        mogan_prof_begin(5, 0, 2.0 * Cout * (double)B * p.OH * p.OW * Cin * KH * KW, Cin, B * p.H * p.W, Cout * KH * KW, stream);
-        rc = mogan_dconv_dgrad_try(dy, w, dx, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, ws, ws_bytes, stream,
-                                   (KH == 4 && KW == 4 && stride == 2) ? wprep : nullptr);
-        mogan_prof_end(rc == 1, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    // dx is the gradient w.r.t. the conv input in the (upsampled) H x W domain: (B,Cin,H,W)
-    p.A = w; p.B = dy; p.C = dx; p.M = Cin; p.K = Cout * p.nkh * p.nkw; p.accumulate = 0;
-    p.a_bytes = 4u * Cout * Cin * KH * KW; p.b_bytes = 4u * B * Cout * p.OH * p.OW;
-    const int Hc = (p.H + stride - 1) / stride, Wc = (p.W + stride - 1) / stride;
-    p.N = B * Hc * Wc;   // class (0,0) has the most columns
-    dense_io(p, CONV_DGRAD);
-    return run_gemm(CONV_DGRAD, p, stride * stride, (long long)B * Cin * p.H * p.W, ws, ws_bytes, stream);
+    MoganConvShape g; const int rc = conv_geom(g, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up);
+    return rc ? rc : dgrad_chain(g, dy, w, wprep, dx, ws, ws_bytes, stream);
 }
 
 // ---- prepared filter images, any kind (include/mogan_hip.h "Prepared filter images") ------------------------------------------
@@ -1310,12 +1353,12 @@ size_t mogan_conv_prep_bytes(int B, int Cin, int Hs, int Ws, int Cout, int KH, i
     if (!mogan_use_dconv || g_force_cfg >= 0) return 0;
     // (the stages ahead of the direct kernels -- <= 4 channels on one side, the 3-channel first layer -- never meet a geometry the
     // direct kernels accept: those need >= 8 / >= 64 channels on the two sides)
+    // (a shape conv_geom refuses is one the direct kernels decline as well: their own size limits are the tighter ones)
+    MoganConvShape g; if (conv_geom(g, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up)) return 0;
     float* const fake = (float*)(uintptr_t)256;           // never dereferenced: the dry run launches nothing
     size_t bytes = 0;
-    const int rc = dgrad ? mogan_dconv_dgrad_try(fake, fake, fake, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, fake, (size_t)1 << 40, nullptr,
-                                                 nullptr, &bytes)
-                         : mogan_dconv_fwd_try(fake, fake, fake, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, fake, (size_t)1 << 40, nullptr,
-                                               nullptr, &bytes);
+    const int rc = dgrad ? mogan_dconv_dgrad_try(fake, fake, fake, g, fake, (size_t)1 << 40, nullptr, nullptr, &bytes)
+                         : mogan_dconv_fwd_try(fake, fake, fake, g, fake, (size_t)1 << 40, nullptr, nullptr, &bytes);
     return rc == 1 ? bytes : 0;
 }
 
@@ -1345,46 +1388,29 @@ int mogan_conv2d_dgrad_ex(const float* dy, long long dy_bstride, const float* w,
                           const float* relu_of, long long relu_bstride, int accumulate, int B, int Cin, int Hs, int Ws,
                           int Cout, int KH, int KW, int stride, int ph, int pw, void* ws, size_t ws_bytes,
                           hipStream_t stream) {
-    GemmP p{}; int rc = conv_geom(p, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 0); if (rc) return rc;
-    const long long yd = (long long)Cout * p.OH * p.OW, xd = (long long)Cin * Hs * Ws;
-    if (dy_bstride < yd || dx_bstride < xd || (long long)(B - 1) * dy_bstride + yd >= (1ll << 30)) return MOGAN_ERR_SHAPE;
-    if (dy_bstride == yd && dx_bstride == xd && !relu_of && !accumulate)
-        return mogan_conv2d_dgrad(dy, w, dx, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, 0, ws, ws_bytes, stream);
-    p.A = w; p.B = dy; p.C = dx; p.M = Cin; p.K = Cout * p.nkh * p.nkw; p.accumulate = accumulate;
-    p.a_bytes = 4u * Cout * Cin * KH * KW; p.b_bytes = 4u * (unsigned)((long long)(B - 1) * dy_bstride + yd);
-    const int Hc = (p.H + stride - 1) / stride, Wc = (p.W + stride - 1) / stride;
-    p.N = B * Hc * Wc;
-    dense_io(p, CONV_DGRAD);
-    p.xbs = (unsigned)dy_bstride; p.ybs = dx_bstride; p.mask = relu_of; p.mbs = relu_bstride;
-    // a strided parity class that has no tap (stride > kernel) would leave its pixels unwritten: not used by the trunk
-    if (stride > KH || stride > KW) return MOGAN_ERR_SHAPE;
-    return run_gemm(CONV_DGRAD, p, stride * stride, (long long)B * Cin * p.H * p.W, ws, ws_bytes, stream);
+    const MoganConvDgradArgs a{dy, dy_bstride, w, dx, dx_bstride, relu_of, relu_bstride, accumulate,
+                               B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw};
+    return dgrad_one(a, ws, ws_bytes, stream);
 }
 
 int mogan_conv2d_wgrad(const float* dy, const float* x, float* dw, int B, int Cin, int Hs, int Ws, int Cout, int KH,
                        int KW, int stride, int ph, int pw, int up, int accumulate, void* ws, size_t ws_bytes,
                        hipStream_t stream) {
-    GemmP p{}; int rc = conv_geom(p, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up); if (rc) return rc;
-    if (g_force_cfg < 0) {
-        rc = mogan_smallc_wgrad_try(dy, x, dw, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, accumulate, ws, ws_bytes, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    if (g_force_cfg == -1) {
-        mogan_prof_begin(6, 1, (4.0 / 9.0) * 2.0 * Cout * (double)B * p.OH * p.OW * Cin * KH * KW, Cout, Cin * KH * KW, B * p.OH * p.OW, stream);
-        rc = mogan_wino_wgrad_try(dy, x, dw, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, accumulate, ws, ws_bytes, stream);
-        mogan_prof_end(rc == 1, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    if (mogan_use_dconv && g_force_cfg < 0) {
-        mogan_prof_begin(6, 0, 2.0 * Cout * (double)B * p.OH * p.OW * Cin * KH * KW, Cout, Cin * KH * KW, B * p.OH * p.OW, stream);
-        rc = mogan_dconv_wgrad_try(dy, x, dw, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, accumulate, ws, ws_bytes, stream);
-        mogan_prof_end(rc == 1, stream);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    p.A = dy; p.B = x; p.C = dw; p.M = Cout; p.N = Cin * KH * KW; p.K = B * p.OH * p.OW; p.accumulate = accumulate;
-    p.a_bytes = 4u * B * Cout * p.OH * p.OW; p.b_bytes = 4u * B * Cin * Hs * Ws;
-    p.avec = ((p.OH * p.OW) % 4 == 0) && (((uintptr_t)dy & 15) == 0);
-    return run_gemm(CONV_WGRAD, p, 1, (long long)Cout * Cin * KH * KW, ws, ws_bytes, stream);
+    MoganConvShape g; int rc = conv_geom(g, B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up); if (rc) return rc;
+    if (g_force_cfg < 0 && stage(rc, NO_PROF, K_DIRECT, g, stream, [&] {
+            return mogan_smallc_wgrad_try(dy, x, dw, g, accumulate, ws, ws_bytes, stream); }))
+        return rc;
+    if (g_force_cfg == -1 && stage(rc, PROF_WGRAD, K_WINO, g, stream, [&] {
+            return mogan_wino_wgrad_try(dy, x, dw, g, accumulate, ws, ws_bytes, stream); }))
+        return rc;
+    if (mogan_use_dconv && g_force_cfg < 0 && stage(rc, PROF_WGRAD, K_DIRECT, g, stream, [&] {
+            return mogan_dconv_wgrad_try(dy, x, dw, g, accumulate, ws, ws_bytes, stream); }))
+        return rc;
+    GemmP p; gemm_geom(p, g);
+    p.A = dy; p.B = x; p.C = dw; p.M = Cout; p.N = Cin * KH * KW; p.K = B * g.OH * g.OW; p.accumulate = accumulate;
+    p.a_bytes = 4u * B * Cout * g.OH * g.OW; p.b_bytes = 4u * B * Cin * Hs * Ws;
+    p.avec = ((g.OH * g.OW) % 4 == 0) && (((uintptr_t)dy & 15) == 0);
+    return run_conv(CONV_WGRAD, p, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

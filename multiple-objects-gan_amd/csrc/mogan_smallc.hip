@@ -543,20 +543,20 @@ __global__ __launch_bounds__(256) void logits_head_bwd_kernel(const float* __res
     }
 }
 
-static inline bool is_full_map(int Hs, int Ws, int Cout, int KH, int KW, int ph, int pw, int up) {
-    return up == 0 && ph == 0 && pw == 0 && KH == Hs && KW == Ws && Cout >= 1 && Cout <= 4;
+static inline bool is_full_map(const MoganConvShape& g) {
+    return g.up == 0 && g.ph == 0 && g.pw == 0 && g.KH == g.Hs && g.KW == g.Ws && g.Cout >= 1 && g.Cout <= 4;
 }
 
 }  // namespace
 
 // ---- internal entry points (hidden visibility): 1 = handled, 0 = not eligible ------------------------------------
-int mogan_smallc_fwd_try(const float* x, const float* w, float* y, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW,
-                         int stride, int ph, int pw, int up, hipStream_t st) {
-    if (is_full_map(Hs, Ws, Cout, KH, KW, ph, pw, up) && (long long)Cin * KH * KW < (1ll << 30)) {
+int mogan_smallc_fwd_try(const float* x, const float* w, float* y, const MoganConvShape& g, hipStream_t st) {
+    const int B = g.B, Cin = g.Cin, Hs = g.Hs, Ws = g.Ws, Cout = g.Cout, KH = g.KH, KW = g.KW;
+    if (is_full_map(g) && (long long)Cin * KH * KW < (1ll << 30)) {
         hipLaunchKernelGGL(sc_dot_fwd, dim3((unsigned)(B * Cout)), dim3(256), 0, st, x, w, y, Cin * KH * KW, Cout);
         return hipGetLastError() == hipSuccess ? 1 : MOGAN_ERR_LAUNCH;
     }
-    if (!(KH == 3 && KW == 3 && stride == 1 && ph == 1 && pw == 1 && up == 0 && Cout >= 1 && Cout <= 4)) return 0;
+    if (!(mogan_is_k33(g) && g.up == 0 && Cout >= 1 && Cout <= 4)) return 0;
     constexpr int w4 = 1;
     if (w4 && (Ws % 128) == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0) {          // four pixels per thread, 8 x 128 tiles
         const int txs = Ws / 128, tys = cdiv(Hs, TR);
@@ -585,16 +585,16 @@ int mogan_smallc_fwd_try(const float* x, const float* w, float* y, int B, int Ci
     return hipGetLastError() == hipSuccess ? 1 : MOGAN_ERR_LAUNCH;
 }
 
-int mogan_smallc_dgrad_try(const float* dy, const float* w, float* dx, int B, int Cin, int Hs, int Ws, int Cout, int KH,
-                           int KW, int stride, int ph, int pw, int up, hipStream_t st) {
-    if (is_full_map(Hs, Ws, Cout, KH, KW, ph, pw, up) && (long long)Cin * KH * KW < (1ll << 30)) {
+int mogan_smallc_dgrad_try(const float* dy, const float* w, float* dx, const MoganConvShape& g, hipStream_t st) {
+    const int B = g.B, Cin = g.Cin, Hs = g.Hs, Ws = g.Ws, Cout = g.Cout, KH = g.KH, KW = g.KW, stride = g.stride, ph = g.ph, pw = g.pw,
+              up = g.up, OH = g.OH, OW = g.OW;
+    if (is_full_map(g) && (long long)Cin * KH * KW < (1ll << 30)) {
         const int K = Cin * KH * KW;
         const long long total = (long long)B * K;
         hipLaunchKernelGGL(sc_dot_dgrad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dy, w, dx, K, Cout, total);
         return hipGetLastError() == hipSuccess ? 1 : MOGAN_ERR_LAUNCH;
     }
     if (up == 0 && ph == 0 && pw == 0 && KH == 3 && KW == 3 && stride == 2 && Cin >= 1 && Cin <= 4 && Hs >= 3 && Ws >= 3) {
-        const int OH = (Hs - 3) / 2 + 1, OW = (Ws - 3) / 2 + 1;
         const int tiles_x = cdiv(cdiv(Ws, 2), TC), tiles_y = cdiv(cdiv(Hs, 2), TR);
         const long long nb = (long long)B * tiles_x * tiles_y;
         if (nb > 0x7fffffffLL) return 0;
@@ -623,7 +623,6 @@ int mogan_smallc_dgrad_try(const float* dy, const float* w, float* dx, int B, in
     }
     if (KH == 4 && KW == 4 && stride == 2 && Cin >= 1 && Cin <= 4 && (Hs % 2) == 0 && (Ws % 2) == 0 &&
         (((uintptr_t)dx) & 7) == 0) {
-        const int OH = Hs / 2, OW = Ws / 2;
         const int tiles_x = cdiv(OW, TC), tiles_y = cdiv(OH, TR);
         const long long nb = (long long)B * tiles_x * tiles_y;
         if (nb > 0x7fffffffLL) return 0;
@@ -639,15 +638,15 @@ int mogan_smallc_dgrad_try(const float* dy, const float* w, float* dx, int B, in
     return 0;
 }
 
-int mogan_smallc_wgrad_try(const float* dy, const float* x, float* dw, int B, int Cin, int Hs, int Ws, int Cout, int KH,
-                           int KW, int stride, int ph, int pw, int up, int accumulate, void* ws, size_t ws_bytes,
-                           hipStream_t st) {
-    if (is_full_map(Hs, Ws, Cout, KH, KW, ph, pw, up) && (long long)Cout * Cin * KH * KW < (1ll << 30)) {
+int mogan_smallc_wgrad_try(const float* dy, const float* x, float* dw, const MoganConvShape& g, int accumulate, void* ws,
+                           size_t ws_bytes, hipStream_t st) {
+    const int B = g.B, Cin = g.Cin, Hs = g.Hs, Ws = g.Ws, Cout = g.Cout, KH = g.KH, KW = g.KW;
+    if (is_full_map(g) && (long long)Cout * Cin * KH * KW < (1ll << 30)) {
         const int K = Cin * KH * KW;
         hipLaunchKernelGGL(sc_dot_wgrad, dim3((unsigned)cdiv(Cout * K, 256)), dim3(256), 0, st, dy, x, dw, K, Cout, B, accumulate);
         return hipGetLastError() == hipSuccess ? 1 : MOGAN_ERR_LAUNCH;
     }
-    if (!(KH == 3 && KW == 3 && stride == 1 && ph == 1 && pw == 1 && up == 0 && Cout >= 1 && Cout <= 4)) return 0;
+    if (!(mogan_is_k33(g) && g.up == 0 && Cout >= 1 && Cout <= 4)) return 0;
     const int tiles_x = cdiv(Ws, TC), tiles_y = cdiv(Hs, TR);
     const long long nblk = (long long)B * tiles_y;
     const int n = Cout * Cin * 9;

@@ -128,13 +128,13 @@ __global__ __launch_bounds__(256, 2) void stem_k4s2_lrelu_kernel(const float* __
 
 // ---- internal entry point (hidden): 1 = handled, 0 = not eligible, < 0 = error ----------------------------------------------------
 // y (B, Cout, H/2, W/2) = LeakyReLU_slope(conv4x4 s2 p1 (x (B, 3, H, W), w (Cout, 3, 4, 4))); slope = 1 is the plain convolution.
-int mogan_stem_fwd_try(const float* x, const float* w, float* y, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride,
-                       int ph, int pw, float slope, hipStream_t st) {
+// (the callers pass it convolutions without the fused upsample only: H x W is the stored map)
+int mogan_stem_fwd_try(const float* x, const float* w, float* y, const MoganConvShape& g, float slope, hipStream_t st) {
 #if MOGAN_X6
     constexpr int on = 1;
     if (!on) return 0;
-    if (!(Cin == 3 && KH == 4 && KW == 4 && stride == 2 && ph == 1 && pw == 1) || (H & 1) || (W & 1) || B <= 0) return 0;
-    const int OH = H / 2, OW = W / 2;
+    const int B = g.B, H = g.H, W = g.W, Cout = g.Cout, OH = g.OH, OW = g.OW;          // (H, W even: OH = H / 2, OW = W / 2)
+    if (!(g.Cin == 3 && mogan_is_k44(g)) || (H & 1) || (W & 1) || B <= 0) return 0;
     if ((OW & 31) || Cout < 32 || Cout > 128 || (Cout & 7) || (((uintptr_t)x) & 7) || !(slope > 0.f)) return 0;
     if ((long long)B * 3 * H * W >= (1ll << 29) || (long long)B * Cout * OH * OW >= (1ll << 30)) return 0;
     const long long ngroups = (long long)B * OH * (OW / 32);

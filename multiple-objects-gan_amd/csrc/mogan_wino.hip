@@ -855,15 +855,15 @@ static int g_wino = -1;
 
 // prep != nullptr: the caller's prepared filter image of THIS weight version and direction (mogan_wino_prep_group): no per-call
 // weight transform, the workspace is not touched.
-int mogan_wino_try(const float* in, const float* w, const void* prep, float* out, int B, int Cin, int H, int W, int Cout, int KH,
-                   int KW, int stride, int ph, int pw, int up, int dgrad, const float* ep_scale, const float* ep_shift, int ep_relu,
-                   void* ws, size_t ws_bytes, hipStream_t st) {
+int mogan_wino_try(const float* in, const float* w, const void* prep, float* out, const MoganConvShape& g, int dgrad,
+                   const float* ep_scale, const float* ep_shift, int ep_relu, void* ws, size_t ws_bytes, hipStream_t st) {
 #if MOGAN_X6
     if (g_wino < 0) { const char* e = getenv("MOGAN_WINO"); g_wino = (e && e[0] == '0') ? 0 : 1; }
-    if (!g_wino || !(KH == 3 && KW == 3 && stride == 1 && ph == pw && (ph == 0 || ph == 1) && up == 0)) return 0;
+    const int B = g.B, Cin = g.Cin, H = g.H, W = g.W, Cout = g.Cout, ph = g.ph;
+    if (!g_wino || !(g.KH == 3 && g.KW == 3 && g.stride == 1 && ph == g.pw && (ph == 0 || ph == 1) && g.up == 0)) return 0;
     const int Kin = dgrad ? Cout : Cin, Kout = dgrad ? Cin : Cout;       // channels the kernel reduces over / produces
     // conv: (H, W) -> (H + 2p - 2); its data gradient runs over dY (the smaller grid) with pad 2 - p and produces (H, W)
-    const int cH = H + 2 * ph - 2, cW = W + 2 * pw - 2;
+    const int cH = g.OH, cW = g.OW;
     const int iH = dgrad ? cH : H, iW = dgrad ? cW : W, oH = dgrad ? H : cH, oW = dgrad ? W : cW, pad = dgrad ? 2 - ph : ph;
     if (cH < 2 || cW < 2 || (Kin % CK2) || Kin < 32 || Kout < 64) return 0;
     if ((((uintptr_t)out) & 15) != 0) return 0;
@@ -913,12 +913,13 @@ int mogan_wino_try(const float* in, const float* w, const void* prep, float* out
 }
 
 // dw (Cout,Cin,3,3) (+)= weight gradient of conv3x3 s1 p1; workspace: nsplit * 16 * Cout * Cin floats
-int mogan_wino_wgrad_try(const float* dy, const float* x, float* dw, int B, int Cin, int H, int W, int Cout, int KH, int KW,
-                         int stride, int ph, int pw, int up, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
+int mogan_wino_wgrad_try(const float* dy, const float* x, float* dw, const MoganConvShape& g, int accumulate, void* ws,
+                         size_t ws_bytes, hipStream_t st) {
+    const int B = g.B, Cin = g.Cin, H = g.H, W = g.W, Cout = g.Cout;
     if (g_wino < 0) { const char* e = getenv("MOGAN_WINO"); g_wino = (e && e[0] == '0') ? 0 : 1; }
     // MOGAN_WINO_WGRAD=0 falls back to the direct kernel (2 = timing aid: main kernel without the finish pass)
     constexpr int wg_on = 1;
-    if (!g_wino || !wg_on || !(KH == 3 && KW == 3 && stride == 1 && ph == 1 && pw == 1 && up == 0)) return 0;
+    if (!g_wino || !wg_on || !(mogan_is_k33(g) && g.up == 0)) return 0;
     if (Cin < 32 || Cout < 64 || (H % 2) || (W % (2 * WCT)) || (W % 2)) return 0;
     if ((((uintptr_t)dy) & 7) != 0) return 0;
     if ((long long)B * Cin * H * W >= (1ll << 30) || (long long)B * Cout * H * W >= (1ll << 30)) return 0;
