@@ -511,7 +511,7 @@ int mogan_reparam_bwd(const float* logvar, const float* eps, const float* dc, fl
  *          (nullable).  Limits: T <= 32, (C*T + T*(S+1) + 896) * 4 bytes of LDS <= 64 KB.
  *   bwd: dsim (B,Bc) -> dwc (B,C,Bc,T), dscore_t (B,Bc,T,S); the region-feature gradient is then two mogan_bmm calls:
  *          dctx[b] (C,S) = dwc[b] (C, Bc*T) . a2[b] (Bc*T, S)  +  wt (C, Bc*T) . dscore_t[b] (Bc*T, S).
- *        (image side only: the text encoder is frozen in the generator step, trainer.py:281-289).  S <= 512. */
+ *        (the image side; the text side is mogan_damsm_words_bwd_text, further down).  S <= 640. */
 int mogan_damsm_words_fwd(const float* ctx, const float* words, const int32_t* cap_lens, int B, int Bc, int C, int S, int T,
                           float gamma1, float gamma2, float gamma3, float* sim, float* a1, float* a2, float* wc, float* wt,
                           hipStream_t stream);
@@ -603,6 +603,44 @@ int mogan_lstm_encoder_fwd(const long long* captions, const int* lens, const flo
                            const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, const float* h0,
                            const float* c0, float* words, float* sent, int B, int T, int Tmax, int V, int E, int H,
                            hipStream_t stream);
+
+/* ---- DAMSM pre-training (attngan/pretrain_DAMSM.py): the text encoder under training, and the text side of the matching losses.
+ * mogan_lstm_encoder_train_fwd: the forward above with embedding dropout and the tensors the backward needs.  Same arguments and
+ * limits, plus
+ *   keep_mask (B, T, E) uint8 or NULL (keep everything), scale: the embedded row is multiplied by scale where the mask is 1 and by
+ *   0 where it is 0 (nn.Dropout: scale = 1 / (1 - p); the mask is drawn by the host side),
+ *   x (B, Tmax, E): the masked, scaled embedding rows (the GEMM operand of dW_ih), gates (2, B, Tmax, 4H): the post-activation
+ *   gates i, f, g, o, cells (2, B, Tmax, H): c_t, hprev (2, B, Tmax, H): the hidden state that ENTERED step t in walk order (the
+ *   reverse direction's "previous" step is t + 1).  All four are written everywhere, zero at t >= lens[b].
+ * mogan_lstm_encoder_bwd: back-propagation through time, one block per (direction, caption).
+ *   dwords (B, 2H, Tmax), dsent (B, 2H) (either nullable = 0), gates / cells / hprev as saved, c0 as in the forward (nullable),
+ *   w_hh[d] -> dgates (2, B, Tmax, 4H): the gradients of the PRE-activation gates, exactly zero at t >= lens[b], and
+ *   dbias (2, 4H) (nullable): their sums over (b, t) = d b_ih = d b_hh, summed in index order.  h0 / c0 get no gradient.
+ *   The weight gradients are GEMMs over the dense (B * Tmax) axis (mogan_bmm): dW_ih[d] = dgates[d]^T . x,
+ *   dW_hh[d] = dgates[d]^T . hprev[d], dx = sum_d dgates[d] . W_ih[d].
+ * mogan_embedding_bwd: demb[tok] += sum over the positions (b, t < lens[b]) that hold tok of (mask ? scale : 0) * dx[b, t, :].
+ *   Deterministic and free of atomics: the first position that holds a token owns its row and adds the later positions in index
+ *   order.  demb (V, E) is accumulated into (the optimizer's gradient bucket); rows of absent tokens are not touched. */
+int mogan_lstm_encoder_train_fwd(const long long* captions, const int* lens, const float* emb, const float* const* w_ih,
+                                 const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, const float* h0,
+                                 const float* c0, const uint8_t* keep_mask, float scale, float* words, float* sent, float* x,
+                                 float* gates, float* cells, float* hprev, int B, int T, int Tmax, int V, int E, int H,
+                                 hipStream_t stream);
+int mogan_lstm_encoder_bwd(const float* dwords, const float* dsent, const int* lens, const float* gates, const float* cells,
+                           const float* hprev, const float* c0, const float* const* w_hh, float* dgates, float* dbias, int B,
+                           int Tmax, int H, hipStream_t stream);
+int mogan_embedding_bwd(const long long* captions, const int* lens, const float* dx, const uint8_t* keep_mask, float scale,
+                        float* demb, int B, int T, int Tmax, int V, int E, hipStream_t stream);
+/* The text side of mogan_damsm_words_bwd / mogan_damsm_sent_bwd (same clamp rules).
+ * words: dwords (Bc,C,T) = sum_b of the gradient of pair (b,i)'s cosines with respect to the word itself,
+ *          k1[t] * wc[b,:,i,t] + k3[t] * w[i,:,t],  k1 = dcos / max(den, 1e-8),  k3 = -dcos * cos / |w|^2,
+ *        summed over b in index order, exactly zero at t >= cap_lens[i].  The path through the attention scores is added by the
+ *        caller, one mogan_bmm per image b over the caption axis: dwords[i] (C,T) += ctx[b] (C,S) . dscore_t[b,i] (T,S)^T.
+ * sent:  drnn[i] = sum_b dsim[b,i] * gamma3 * (cnn_b / den - cos * rnn_i / |rnn_i|^2). */
+int mogan_damsm_words_bwd_text(const float* words, const int32_t* cap_lens, const float* wc, const float* dsim, int B, int Bc,
+                               int C, int T, float gamma2, float gamma3, float* dwords, hipStream_t stream);
+int mogan_damsm_sent_bwd_text(const float* cnn, const float* rnn, const float* dsim, int B, int Bc, int C, float gamma3,
+                              float eps, float* drnn, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1097,7 +1097,9 @@ class _FrozenTrunkFn(torch.autograd.Function):
 def frozen_trunk(enc, x299):
     """(features 768x17x17, Mixed_7c output 2048x8x8) of the frozen eval-mode trunk of `enc` (a CNN_ENCODER)."""
     ft = getattr(enc, "_frozen_trunk", None)
-    key = _versions(*[t for t in list(enc.parameters()) + list(enc.buffers()) if t.is_floating_point()])
+    heads = getattr(enc, "HEADS", ())          # the two projections are no part of the trunk: training them rebuilds nothing
+    key = _versions(*[t for n, t in list(enc.named_parameters()) + list(enc.named_buffers())
+                      if t.is_floating_point() and n.split(".")[0] not in heads])
     cls = PanelTrunk if PANEL_TRUNK else FrozenTrunk
     if ft is None or type(ft) is not cls or getattr(enc, "_frozen_trunk_key", None) != key \
             or ft.stem["Conv2d_1a_3x3"].w.device != x299.device:

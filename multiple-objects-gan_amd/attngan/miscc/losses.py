@@ -53,15 +53,6 @@ def _labels_and_mask(labels, class_ids, batch_size, device):
     return labels.to(device=device, dtype=torch.int64).contiguous(), masks
 
 
-def _image_side_only(t, what):
-    """The fused DAMSM kernels differentiate with respect to the IMAGE side only -- in the generator step the text encoder
-    is frozen (trainer.py:281-289).  A caller that wants text-encoder gradients (DAMSM pre-training, pretrain_DAMSM.py: out
-    of scope) must not get silent zeros."""
-    if torch.is_grad_enabled() and t.requires_grad:
-        raise NotImplementedError("%s requires grad: the fused DAMSM losses give gradients to the image features only (the "
-                                  "text encoder is frozen in the GAN train step); detach() the text embeddings" % what)
-
-
 def _damsm_shape_check(C, S, T):
     """Limits of mogan_damsm_words_* (csrc/mogan_damsm.hip): T <= 32 words, S <= 640 regions, 64 KB of LDS."""
     lds = 4 * (C * T + T * (S + 1) + 3 * 10 * 32 + 4 * 32)
@@ -72,12 +63,12 @@ def _damsm_shape_check(C, S, T):
 
 def sent_loss(cnn_code, rnn_code, labels, class_ids, batch_size, eps=1e-8):
     """losses.py:20-59: cosine matrix of the image / sentence codes * gamma3 and cross-entropy both ways, fused
-    (mogan_damsm_sent_* + mogan_damsm_ce_*: 2 launches forward, 2 backward).  Gradient: cnn_code."""
+    (mogan_damsm_sent_* + mogan_damsm_ce_*: 2 launches forward, 2 backward).  Gradients: cnn_code, and rnn_code when it
+    requires one (DAMSM pre-training; one more launch)."""
     if labels is None:
         return None, None
-    _image_side_only(rnn_code, "sent_loss: rnn_code")
     lab, masks = _labels_and_mask(labels, class_ids, batch_size, cnn_code.device)
-    return ops.damsm_sent(cnn_code, rnn_code.detach(), lab, masks, cfg.TRAIN.SMOOTH.GAMMA3, eps)
+    return ops.damsm_sent(cnn_code, rnn_code, lab, masks, cfg.TRAIN.SMOOTH.GAMMA3, eps)
 
 
 def words_loss(img_features, words_emb, labels, cap_lens, class_ids, batch_size):
@@ -85,15 +76,15 @@ def words_loss(img_features, words_emb, labels, cap_lens, class_ids, batch_size)
     similarities[b, i] = log sum_t exp(gamma2 * cos(word_{i,t}, context_{b,i,t})) * gamma3, where the region context
     comes from func_attention(word_i, feature_b) (GlobalAttention.py:31-69) -- all B*B pairs in one fused launch
     (mogan_damsm_words_fwd) instead of the reference's B-iteration python loop, then the two cross-entropies.
-    Gradient: img_features (the text encoder is frozen in the generator step, trainer.py:281-289)."""
+    Gradients: img_features, and words_emb when it requires one (DAMSM pre-training; in the generator step the text encoder
+    is frozen, trainer.py:281-289, and nothing is launched for it)."""
     B = batch_size
     ih, iw = img_features.shape[2], img_features.shape[3]
     dev = img_features.device
-    _image_side_only(words_emb, "words_loss: words_emb")
     _damsm_shape_check(img_features.shape[1], ih * iw, words_emb.shape[2])
     lens = cap_lens.to(dev).to(torch.int32).reshape(B).contiguous()
     lab, masks = _labels_and_mask(labels, class_ids, B, dev)
-    l0, l1, a2 = ops.damsm_words(img_features, words_emb.detach(), lens, lab, masks, cfg.TRAIN.SMOOTH.GAMMA1,
+    l0, l1, a2 = ops.damsm_words(img_features, words_emb, lens, lab, masks, cfg.TRAIN.SMOOTH.GAMMA1,
                                  cfg.TRAIN.SMOOTH.GAMMA2, cfg.TRAIN.SMOOTH.GAMMA3)
     att_maps = None
     if labels is None or not torch.is_grad_enabled():         # visualisation (losses.py:87-91): caption i on image i

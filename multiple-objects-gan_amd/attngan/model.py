@@ -119,10 +119,11 @@ class BBOX_NET(nn.Module):
 
 # --------------------------------------------------------------------------- text / image encoders
 class RNN_ENCODER(nn.Module):
-    """model.py:120-204.  Frozen front-end that runs once per step without gradients.  The parameters live in the stock
-    nn.Embedding / nn.LSTM modules (state_dict keys of the reference); in eval mode on the device the forward is ONE launch
-    (csrc/mogan_lstm.hip: 119 launches and 0.8 ms of host time per call on MIOpen's LSTM), anything else -- training mode,
-    gradients, a GRU, other sizes -- takes the stock modules."""
+    """model.py:120-204.  The parameters live in the stock nn.Embedding / nn.LSTM modules (state_dict keys of the reference).
+    On the device the forward is ONE launch: in eval mode without gradients csrc/mogan_lstm.hip's eval kernel (the GAN step's
+    frozen front-end; 119 launches and 0.8 ms of host time per call on MIOpen's LSTM), with gradients enabled its training
+    kernel with embedding dropout (DAMSM pre-training, hip/ops.LstmEncoderFn).  Anything else -- a GRU, other sizes, the CPU --
+    takes the stock modules."""
 
     def __init__(self, ntoken, ninput=300, drop_prob=0.5, nhidden=128, nlayers=1, bidirectional=True):
         super(RNN_ENCODER, self).__init__()
@@ -147,17 +148,31 @@ class RNN_ENCODER(nn.Module):
             return (weight.new_zeros(shape), weight.new_zeros(shape))
         return weight.new_zeros(shape)
 
-    FUSED = True      # eval mode on the device: embedding + bi-LSTM as one launch (hip/ops.lstm_encoder_forward)
+    FUSED = True      # on the device: embedding + bi-LSTM as one launch (hip/ops.lstm_encoder_forward / lstm_encoder_train)
 
-    def forward(self, captions, cap_lens, hidden, mask=None):
+    def forward(self, captions, cap_lens, hidden, mask=None, drop_mask=None):
+        """drop_mask: uint8 (B, T, E) keep mask of the embedding dropout (1 = keep); in training mode without one it is drawn
+        here.  nn.LSTM(dropout=...) with one layer applies none: the embedding's is the only dropout, off in eval mode."""
         lens = cap_lens.data.tolist() if torch.is_tensor(cap_lens) else list(cap_lens)
-        if (self.FUSED and captions.is_cuda and not self.training and not torch.is_grad_enabled() and self.rnn_type == 'LSTM'
-                and self.nlayers == 1 and self.bidirectional):
+        fused = self.FUSED and captions.is_cuda and self.rnn_type == 'LSTM' and self.nlayers == 1 and self.bidirectional
+        if fused and not self.training and not torch.is_grad_enabled():
             from ..hip import ops
             out = ops.lstm_encoder_forward(captions, lens, self.encoder.weight, self.rnn, hidden[0], hidden[1])
             if out is not None:                     # (B, 2H, T_max) = the reference's output.transpose(1, 2), and (B, 2H)
                 return out
-        emb = self.drop(self.encoder(captions))
+        keep = drop_mask if self.training else None
+        scale = 1.0 / (1.0 - self.drop_prob) if self.training and self.drop_prob < 1 else 1.0
+        if fused and torch.is_grad_enabled():
+            from ..hip import ops
+            if self.training and self.drop_prob > 0 and keep is None:
+                keep = (torch.rand(captions.shape[0], captions.shape[1], self.ninput, device=captions.device)
+                        >= self.drop_prob).to(torch.uint8)
+            out = ops.lstm_encoder_train(captions, lens, self.encoder.weight, self.rnn, hidden[0], hidden[1], keep,
+                                         scale if keep is not None else 1.0)
+            if out is not None:
+                return out
+        emb = self.encoder(captions)
+        emb = self.drop(emb) if keep is None else emb * (keep.to(emb.dtype) * scale)
         emb = pack_padded_sequence(emb, lens, batch_first=True)
         output, hidden = self.rnn(emb, hidden)
         output = pad_packed_sequence(output, batch_first=True)[0]
@@ -189,8 +204,15 @@ class CNN_ENCODER(nn.Module):
         self.emb_features.weight.data.uniform_(-0.1, 0.1)
         self.emb_cnn_code.weight.data.uniform_(-0.1, 0.1)
 
+    HEADS = ("emb_features", "emb_cnn_code")
+
+    def trunk_parameters(self):
+        return [p for n, p in self.named_parameters() if n.split(".")[0] not in self.HEADS]
+
     def _frozen(self):
-        return inception.FAST_TRUNK and not self.training and not any(p.requires_grad for p in self.parameters())
+        """the fast frozen trunk: eval mode and no TRUNK parameter asks for a gradient; the two heads may (DAMSM pre-training:
+        they then run under autograd on the trunk's outputs)"""
+        return inception.FAST_TRUNK and not self.training and not any(p.requires_grad for p in self.trunk_parameters())
 
     def forward(self, x):
         x = ops.bilinear_resize(x, 299, 299)

@@ -21,8 +21,9 @@
 // rank-(B*T) updates of d ctx are then plain strided GEMMs (mogan_bmm) over the caption axis -- no atomics.
 // Cross-entropies (rows: image -> caption, columns: caption -> image, optional same-class mask, losses.py:116-130)
 // and the sentence loss (cosine matrix of the two code vectors, losses.py:36-58) are small per-row kernels.
-// Gradients are produced for the IMAGE side only (region features / cnn code): in the generator step the text encoder
-// is frozen and its embeddings are detached (trainer.py:281-289).
+// The kernels above give the IMAGE side's gradients (region features / cnn code), all the generator step needs (its text encoder is
+// frozen, trainer.py:281-289); the TEXT side's (word / sentence embeddings: DAMSM pre-training) are two kernels of their own
+// further down, launched only when those inputs ask for a gradient.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mogan_hip.h"
@@ -466,6 +467,108 @@ __global__ __launch_bounds__(NT2) void damsm_sent_bwd_kernel(const float* __rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------- text side (DAMSM pre-training)
+// d words[i] (C x T), the part that does not pass through the attention scores: block per caption i, the images b = 0 .. B-1 one
+// after the other (fixed order, no atomics).  Per pair the cosines are formed again from wc and w as in damsm_words_bwd_kernel
+// (thread (t = tid % TMAX, part = tid / TMAX) sums a stripe of c), then
+//     d cos / d w = wc / den - cos * w / |w|^2     (den clamped: only the first term, with 1e-8)
+// is accumulated in LDS (C*T floats).  The score path is the caller's mogan_bmm per image.
+__global__ __launch_bounds__(NT2) void damsm_words_bwd_text_kernel(
+    const float* __restrict__ words, const int32_t* __restrict__ lens, const float* __restrict__ wc,
+    const float* __restrict__ dsim, int B, int Bc, int C, int T, float gamma2, float gamma3, float* __restrict__ dwords) {
+    extern __shared__ float smem[];
+    constexpr int NP = NT2 / TMAX;
+    float* acc = smem;                                        // [C*T]
+    float* red = acc + C * T;                                 // [NP][2][TMAX]
+    float* coef = red + NP * 2 * TMAX;                        // k1[TMAX], k3[TMAX]
+    float* w2s = coef + 2 * TMAX;                             // |w_t|^2
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int Ti = min(T, max(0, lens[i]));
+    const float* wi = words + (size_t)i * C * T;
+    const int t = tid % TMAX, part = tid / TMAX;
+    for (int e = tid; e < C * T; e += NT2) acc[e] = 0.f;
+    {
+        float w2 = 0.f;
+        if (t < Ti)
+            for (int c = part; c < C; c += NP) { const float wv = wi[c * T + t]; w2 = fmaf(wv, wv, w2); }
+        red[part * 2 * TMAX + t] = w2;
+    }
+    __syncthreads();
+    if (tid < TMAX) {
+        float w2 = 0.f;
+        for (int q = 0; q < NP; ++q) w2 += red[q * 2 * TMAX + tid];
+        w2s[tid] = w2;
+    }
+    __syncthreads();
+    for (int b = 0; b < B; ++b) {
+        float d = 0.f, a = 0.f;
+        if (t < Ti)
+            for (int c = part; c < C; c += NP) {
+                const float v = wc[(((size_t)b * C + c) * Bc + i) * T + t], wv = wi[c * T + t];
+                d = fmaf(v, wv, d); a = fmaf(v, v, a);
+            }
+        red[(part * 2 + 0) * TMAX + t] = d; red[(part * 2 + 1) * TMAX + t] = a;
+        __syncthreads();
+        if (tid < TMAX) {
+            float dd = 0.f, aa = 0.f;
+            for (int q = 0; q < NP; ++q) { dd += red[(q * 2 + 0) * TMAX + tid]; aa += red[(q * 2 + 1) * TMAX + tid]; }
+            const float w2 = w2s[tid];
+            const float den = sqrtf(aa) * sqrtf(w2);
+            const bool clamped = den < 1e-8f;
+            const float cosv = dd / fmaxf(den, 1e-8f);
+            const float e = tid < Ti ? __expf(gamma2 * cosv) : 0.f;
+            float z = e;
+#pragma unroll
+            for (int o = TMAX / 2; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);     // lanes 0..31 of wave 0
+            const float dcos = tid < Ti ? dsim[(size_t)b * Bc + i] * gamma3 * gamma2 * e / z : 0.f;
+            coef[tid] = dcos / fmaxf(den, 1e-8f);
+            coef[TMAX + tid] = (clamped || w2 <= 0.f) ? 0.f : -dcos * cosv / w2;
+        }
+        __syncthreads();
+        for (int e = tid; e < C * T; e += NT2) {
+            const int c = e / T, tt = e - c * T;
+            if (tt < Ti) acc[e] += coef[tt] * wc[(((size_t)b * C + c) * Bc + i) * T + tt] + coef[TMAX + tt] * wi[e];
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < C * T; e += NT2) {
+        const int c = e / T, tt = e - c * T;
+        dwords[(size_t)i * C * T + e] = tt < Ti ? acc[e] : 0.f;
+    }
+}
+
+// d rnn[i,c] = sum_b dsim[b,i] gamma3 ( cnn[b,c] / den - <cnn_b, rnn_i> rnn[i,c] / (|rnn_i|^2 den) ): damsm_sent_bwd_kernel with
+// the two sides swapped, block per caption i
+__global__ __launch_bounds__(NT2) void damsm_sent_bwd_text_kernel(const float* __restrict__ cnn, const float* __restrict__ rnn,
+                                                                 const float* __restrict__ dsim, int B, int Bc, int C,
+                                                                 float gamma3, float eps, float* __restrict__ drnn) {
+    extern __shared__ float smem[];           // k1[B], k2[B]
+    float* k1 = smem; float* k2 = smem + B;
+    const int i = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* ri = rnn + (size_t)i * C;
+    float n1s = 0.f;
+    for (int c = lane; c < C; c += 64) n1s = fmaf(ri[c], ri[c], n1s);
+    n1s = wave_sum(n1s);
+    const float n1 = sqrtf(n1s);
+    for (int b = wave; b < B; b += NT2 / 64) {
+        const float* xb = cnn + (size_t)b * C;
+        float d = 0.f, n0 = 0.f;
+        for (int c = lane; c < C; c += 64) { d = fmaf(xb[c], ri[c], d); n0 = fmaf(xb[c], xb[c], n0); }
+        d = wave_sum(d); n0 = sqrtf(wave_sum(n0));
+        if (lane == 0) {
+            const float den = n0 * n1, g = dsim[(size_t)b * Bc + i] * gamma3;
+            if (den < eps) { k1[b] = g / eps; k2[b] = 0.f; }
+            else { k1[b] = g / den; k2[b] = n1s > 0.f ? -g * d / (den * n1s) : 0.f; }
+        }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += NT2) {
+        float acc = 0.f, self = 0.f;
+        for (int b = 0; b < B; ++b) { acc = fmaf(k1[b], cnn[(size_t)b * C + c], acc); self += k2[b]; }
+        drnn[(size_t)i * C + c] = acc + self * ri[c];
+    }
+}
+
 // out[0] = sum_k w[k] * (*in[k])  (k < n <= 8): sums of 0-dim loss terms without a chain of scalar launches
 struct ScalarSumP { const float* in[8]; float w[8]; int n; };
 __global__ void scalar_sum_kernel(ScalarSumP p, float* __restrict__ out) {
@@ -546,6 +649,26 @@ int mogan_damsm_sent_bwd(const float* cnn, const float* rnn, const float* dsim, 
     if (B <= 0 || Bc <= 0 || C <= 0 || (size_t)Bc * 2 * sizeof(float) > 64 * 1024) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(damsm_sent_bwd_kernel, dim3(B), dim3(NT2), (size_t)Bc * 2 * sizeof(float), stream, cnn, rnn, dsim, Bc,
                        C, gamma3, eps, dcnn);
+    return ok_launch();
+}
+
+int mogan_damsm_words_bwd_text(const float* words, const int32_t* cap_lens, const float* wc, const float* dsim, int B, int Bc,
+                               int C, int T, float gamma2, float gamma3, float* dwords, hipStream_t stream) {
+    if (!words || !cap_lens || !wc || !dsim || !dwords) return MOGAN_ERR_SHAPE;
+    if (B <= 0 || Bc <= 0 || C <= 0 || T <= 0 || T > TMAX || Bc > 65535) return MOGAN_ERR_SHAPE;
+    const size_t lds = ((size_t)C * T + (NT2 / TMAX) * 2 * TMAX + 3 * TMAX) * sizeof(float);
+    if (lds > 64 * 1024) return MOGAN_ERR_SHAPE;
+    hipLaunchKernelGGL(damsm_words_bwd_text_kernel, dim3(Bc), dim3(NT2), lds, stream, words, cap_lens, wc, dsim, B, Bc, C, T,
+                       gamma2, gamma3, dwords);
+    return ok_launch();
+}
+
+int mogan_damsm_sent_bwd_text(const float* cnn, const float* rnn, const float* dsim, int B, int Bc, int C, float gamma3,
+                              float eps, float* drnn, hipStream_t stream) {
+    if (!cnn || !rnn || !dsim || !drnn) return MOGAN_ERR_SHAPE;
+    if (B <= 0 || Bc <= 0 || C <= 0 || (size_t)B * 2 * sizeof(float) > 64 * 1024) return MOGAN_ERR_SHAPE;
+    hipLaunchKernelGGL(damsm_sent_bwd_text_kernel, dim3(Bc), dim3(NT2), (size_t)B * 2 * sizeof(float), stream, cnn, rnn, dsim, B,
+                       Bc, C, gamma3, eps, drnn);
     return ok_launch();
 }
 

@@ -132,6 +132,11 @@ SIGNATURES = {
     "mogan_damsm_ce_bwd": [P, P, P, P, P, I, I, P, P],
     "mogan_damsm_sent_fwd": [P, P, I, I, I, F, F, P, P],
     "mogan_damsm_sent_bwd": [P, P, P, I, I, I, F, F, P, P],
+    "mogan_damsm_words_bwd_text": [P, P, P, P, I, I, I, I, F, F, P, P],
+    "mogan_damsm_sent_bwd_text": [P, P, P, I, I, I, F, F, P, P],
+    "mogan_lstm_encoder_train_fwd": [P] * 10 + [F] + [P] * 6 + [I] * 6 + [P],
+    "mogan_lstm_encoder_bwd": [P] * 10 + [I] * 3 + [P],
+    "mogan_embedding_bwd": [P, P, P, P, F, P, I, I, I, I, I, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }

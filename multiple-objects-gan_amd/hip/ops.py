@@ -1680,7 +1680,8 @@ class _PairCE:
 
 class DamsmWordsFn(torch.autograd.Function):
     """words_loss for all (image, caption) pairs (miscc/losses.py:62-132, GlobalAttention.py:31-69) -> (loss0, loss1,
-    attention a2 (B,Bc,T,S)).  Gradient: region features only."""
+    attention a2 (B,Bc,T,S)).  Gradients: the region features, and -- when they ask for one (DAMSM pre-training) -- the word
+    embeddings (mogan_damsm_words_bwd_text + one mogan_bmm per image for the path through the attention scores)."""
 
     @staticmethod
     def forward(ctx, feat, words, lens, labels, mask, g1, g2, g3):
@@ -1713,11 +1714,20 @@ class DamsmWordsFn(torch.autograd.Function):
         dst = torch.empty_like(a2)
         call("mogan_damsm_words_bwd", ptr(feat), ptr(words), ptr(lens), ptr(a1), ptr(a2), ptr(wc), ptr(dsim), B, Bc, C, S, T,
              g1, g2, g3, ptr(dwc), ptr(dst), stream_ptr())
-        dfeat = torch.empty_like(feat)
-        out = dfeat.view(B, C, S)
-        bmm_raw(dwc.view(B, C, Bc * T), a2.view(B, Bc * T, S), out)
-        bmm_raw(wt.view(1, C, Bc * T).expand(B, C, Bc * T), dst.view(B, Bc * T, S), out, accumulate=True)
-        return dfeat, None, None, None, None, None, None, None
+        dfeat = dwords = None
+        if ctx.needs_input_grad[0]:
+            dfeat = torch.empty_like(feat)
+            out = dfeat.view(B, C, S)
+            bmm_raw(dwc.view(B, C, Bc * T), a2.view(B, Bc * T, S), out)
+            bmm_raw(wt.view(1, C, Bc * T).expand(B, C, Bc * T), dst.view(B, Bc * T, S), out, accumulate=True)
+        if ctx.needs_input_grad[1]:
+            dwords = torch.empty_like(words)
+            call("mogan_damsm_words_bwd_text", ptr(words), ptr(lens), ptr(wc), ptr(dsim), B, Bc, C, T, g2, g3, ptr(dwords),
+                 stream_ptr())
+            fv = feat.view(B, C, S)
+            for b in range(B):          # dwords[i] (C,T) += ctx[b] (C,S) . dscore_t[b,i] (T,S)^T, the images in index order
+                bmm_raw(fv[b:b + 1].expand(Bc, C, S), dst[b].transpose(1, 2), dwords, accumulate=True)
+        return dfeat, dwords, None, None, None, None, None, None
 
 
 def damsm_words(feat, words, lens, labels, mask, gamma1, gamma2, gamma3):
@@ -1725,7 +1735,8 @@ def damsm_words(feat, words, lens, labels, mask, gamma1, gamma2, gamma3):
 
 
 class DamsmSentFn(torch.autograd.Function):
-    """sent_loss (miscc/losses.py:20-59) -> (loss0, loss1).  Gradient: cnn code only."""
+    """sent_loss (miscc/losses.py:20-59) -> (loss0, loss1).  Gradients: the cnn code, and the sentence code when it asks for
+    one (mogan_damsm_sent_bwd_text)."""
 
     @staticmethod
     def forward(ctx, cnn, rnn, labels, mask, g3, eps):
@@ -1743,10 +1754,16 @@ class DamsmSentFn(torch.autograd.Function):
         cnn, rnn = ctx.saved_tensors
         g3, eps = ctx.cfg
         dsim = _PairCE.backward(ctx, gl0, gl1)
-        dcnn = torch.empty_like(cnn)
-        call("mogan_damsm_sent_bwd", ptr(cnn), ptr(rnn), ptr(dsim), cnn.shape[0], rnn.shape[0], cnn.shape[1], g3, eps,
-             ptr(dcnn), stream_ptr())
-        return dcnn, None, None, None, None, None
+        dcnn = drnn = None
+        if ctx.needs_input_grad[0]:
+            dcnn = torch.empty_like(cnn)
+            call("mogan_damsm_sent_bwd", ptr(cnn), ptr(rnn), ptr(dsim), cnn.shape[0], rnn.shape[0], cnn.shape[1], g3, eps,
+                 ptr(dcnn), stream_ptr())
+        if ctx.needs_input_grad[1]:
+            drnn = torch.empty_like(rnn)
+            call("mogan_damsm_sent_bwd_text", ptr(cnn), ptr(rnn), ptr(dsim), cnn.shape[0], rnn.shape[0], cnn.shape[1], g3, eps,
+                 ptr(drnn), stream_ptr())
+        return dcnn, drnn, None, None, None, None
 
 
 def damsm_sent(cnn, rnn, labels, mask, gamma3, eps=1e-8):
@@ -1858,36 +1875,154 @@ def adam_step(p, g, m, v, ema, lr, beta1, beta2, eps, step=0, dev_state=None, ep
 
 
 # ------------------------------------------------------------------------------- text encoder (csrc/mogan_lstm.hip)
-def lstm_encoder_forward(captions, lens, emb_weight, rnn, h0=None, c0=None):
-    """Embedding + one-layer bidirectional LSTM over packed captions, eval mode, no gradient, as ONE launch
-    (mogan_lstm_encoder_fwd); `rnn` is the nn.LSTM whose parameters are used.  Returns (words (B, 2H, Tmax), sent (B, 2H)) or
-    None where the kernel does not cover the module (then the caller keeps the stock path)."""
-    import ctypes
+def _lstm_encoder_args(captions, lens, emb_weight, rnn, h0, c0):
+    """What both text-encoder paths need checked before a pointer reaches the kernels: the module is the one-layer bidirectional
+    LSTM with 128 units per direction, the sizes are inside the kernels' limits, and every tensor (the embedding table and the
+    initial states included) is float32, dense, on the captions' device and of the expected shape.
+    Returns (B, T, V, E, H, Tmax, lens, ws) or None (the caller keeps the stock modules)."""
+    if (not isinstance(rnn, torch.nn.LSTM) or rnn.num_layers != 1 or not rnn.bidirectional or not rnn.batch_first
+            or rnn.hidden_size != 128 or not rnn.bias or getattr(rnn, "proj_size", 0)):
+        return None
     H = rnn.hidden_size
-    if (not isinstance(rnn, torch.nn.LSTM) or rnn.num_layers != 1 or not rnn.bidirectional or not rnn.batch_first or H != 128
-            or not rnn.bias or getattr(rnn, "proj_size", 0)):
+    if captions.dim() != 2 or emb_weight.dim() != 2:
         return None
     B, T = captions.shape
     V, E = emb_weight.shape
     lens = [int(v) for v in lens]
     Tmax = max(lens) if lens else 0
-    if B > 64 or Tmax < 1 or Tmax > 32 or Tmax > T or E > 320 or E % 4 or min(lens) < 0 or captions.dtype != torch.int64:
+    if (len(lens) != B or B > 64 or Tmax < 1 or Tmax > 32 or Tmax > T or E > 320 or E % 4 or min(lens) < 0
+            or captions.dtype != torch.int64 or rnn.input_size != E):
         return None
     ws = [rnn.weight_ih_l0, rnn.weight_ih_l0_reverse, rnn.weight_hh_l0, rnn.weight_hh_l0_reverse,
           rnn.bias_ih_l0, rnn.bias_ih_l0_reverse, rnn.bias_hh_l0, rnn.bias_hh_l0_reverse]
-    if any(w.dtype != torch.float32 or not w.is_contiguous() or w.data_ptr() % 16 for w in ws) or not emb_weight.is_contiguous():
+    dev = captions.device
+    if any(w.dtype != torch.float32 or not w.is_contiguous() or w.data_ptr() % 16 or w.device != dev for w in ws):
         return None
+    if emb_weight.dtype != torch.float32 or not emb_weight.is_contiguous() or emb_weight.device != dev:
+        return None
+    for st in (h0, c0):
+        if st is not None and (st.dtype != torch.float32 or st.device != dev or tuple(st.shape) != (2, B, H)):
+            return None
+    return B, T, V, E, H, Tmax, lens, ws
+
+
+def _ptr_pairs(ws):
+    import ctypes
+    P2 = ctypes.c_void_p * 2
+    arr = [P2(ws[2 * i].data_ptr(), ws[2 * i + 1].data_ptr()) for i in range(len(ws) // 2)]
+    return arr, [ctypes.cast(a, ctypes.c_void_p) for a in arr]
+
+
+def lstm_encoder_forward(captions, lens, emb_weight, rnn, h0=None, c0=None):
+    """Embedding + one-layer bidirectional LSTM over packed captions, eval mode, no gradient, as ONE launch
+    (mogan_lstm_encoder_fwd); `rnn` is the nn.LSTM whose parameters are used.  Returns (words (B, 2H, Tmax), sent (B, 2H)) or
+    None where the kernel does not cover the module (then the caller keeps the stock path)."""
+    import ctypes
+    args = _lstm_encoder_args(captions, lens, emb_weight, rnn, h0, c0)
+    if args is None:
+        return None
+    B, T, V, E, H, Tmax, lens, ws = args
     dev = captions.device
     cap = captions if captions.is_contiguous() else captions.contiguous()
     words = torch.empty((B, 2 * H, Tmax), dtype=torch.float32, device=dev)
     sent = torch.empty((B, 2 * H), dtype=torch.float32, device=dev)
-    P2 = ctypes.c_void_p * 2
-    arr = [P2(ws[2 * i].data_ptr(), ws[2 * i + 1].data_ptr()) for i in range(4)]
+    keep, arr = _ptr_pairs(ws)
     lens_c = (ctypes.c_int * B)(*lens)
     h0p = ptr(_c(h0)) if h0 is not None else None
     c0p = ptr(_c(c0)) if c0 is not None else None
     call("mogan_lstm_encoder_fwd", cap.data_ptr(), ctypes.cast(lens_c, ctypes.c_void_p), emb_weight.data_ptr(),
-         ctypes.cast(arr[0], ctypes.c_void_p), ctypes.cast(arr[1], ctypes.c_void_p), ctypes.cast(arr[2], ctypes.c_void_p),
-         ctypes.cast(arr[3], ctypes.c_void_p), h0p, c0p, words.data_ptr(), sent.data_ptr(), B, T, Tmax, V, E, H, stream_ptr())
+         arr[0], arr[1], arr[2], arr[3], h0p, c0p, words.data_ptr(), sent.data_ptr(), B, T, Tmax, V, E, H, stream_ptr())
     PK_STATS["lstm_fused"] = PK_STATS.get("lstm_fused", 0) + 1
     return words, sent
+
+
+class LstmEncoderFn(torch.autograd.Function):
+    """The text encoder under training (csrc/mogan_lstm.hip): mogan_lstm_encoder_train_fwd forward; backward =
+    mogan_lstm_encoder_bwd (BPTT -> pre-activation gate gradients and the bias gradients), the weight gradients as mogan_bmm
+    GEMMs over the dense (B * Tmax) axis, mogan_embedding_bwd for the table.  Differentiable inputs: the embedding table and the
+    eight LSTM parameters (w_ih, w_ih_reverse, w_hh, w_hh_reverse, b_ih, b_ih_reverse, b_hh, b_hh_reverse); h0 / c0 get none."""
+
+    @staticmethod
+    def forward(ctx, cap, lens, h0, c0, keep_mask, scale, emb_weight, *ws):
+        import ctypes
+        B, T = cap.shape
+        V, E = emb_weight.shape
+        H, Tmax = 128, max(lens)
+        dev = cap.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        words, sent = torch.empty((B, 2 * H, Tmax), **f32), torch.empty((B, 2 * H), **f32)
+        x = torch.empty((B, Tmax, E), **f32)
+        gates, cells = torch.empty((2, B, Tmax, 4 * H), **f32), torch.empty((2, B, Tmax, H), **f32)
+        hprev = torch.empty((2, B, Tmax, H), **f32)
+        keep, arr = _ptr_pairs(ws)
+        lens_c = (ctypes.c_int * B)(*lens)
+        call("mogan_lstm_encoder_train_fwd", cap.data_ptr(), ctypes.cast(lens_c, ctypes.c_void_p), emb_weight.data_ptr(),
+             arr[0], arr[1], arr[2], arr[3], ptr(h0), ptr(c0), ptr(keep_mask), float(scale), ptr(words), ptr(sent), ptr(x),
+             ptr(gates), ptr(cells), ptr(hprev), B, T, Tmax, V, E, H, stream_ptr())
+        ctx.save_for_backward(x, gates, cells, hprev, ws[0], ws[1], ws[2], ws[3])
+        ctx.aux = (cap, lens, c0, keep_mask, float(scale), emb_weight)
+        return words, sent
+
+    @staticmethod
+    def backward(ctx, dwords, dsent):
+        import ctypes
+        x, gates, cells, hprev, wih0, wih1, whh0, whh1 = ctx.saved_tensors
+        cap, lens, c0, keep_mask, scale, emb_weight = ctx.aux
+        B, Tmax, E = x.shape
+        T = cap.shape[1]
+        H = 128
+        f32 = dict(dtype=torch.float32, device=x.device)
+        dwords = _c(dwords) if dwords is not None else None
+        dsent = _c(dsent) if dsent is not None else None
+        dg, db = torch.empty((2, B, Tmax, 4 * H), **f32), torch.empty((2, 4 * H), **f32)
+        keep, arr = _ptr_pairs([whh0, whh1])
+        lens_c = (ctypes.c_int * B)(*lens)
+        lens_p = ctypes.cast(lens_c, ctypes.c_void_p)
+        call("mogan_lstm_encoder_bwd", ptr(dwords), ptr(dsent), lens_p, ptr(gates), ptr(cells), ptr(hprev), ptr(c0), arr[0],
+             ptr(dg), ptr(db), B, Tmax, H, stream_ptr())
+        need = ctx.needs_input_grad[6:]
+        BT = B * Tmax
+        dgt = dg.view(2, BT, 4 * H).transpose(1, 2)
+        demb = dwih = dwhh = None
+        if need[1] or need[2]:
+            dwih = torch.empty((2, 4 * H, E), **f32)
+            bmm_raw(dgt, x.view(1, BT, E).expand(2, BT, E), dwih)
+        if need[3] or need[4]:
+            dwhh = torch.empty((2, 4 * H, H), **f32)
+            bmm_raw(dgt, hprev.view(2, BT, H), dwhh)
+        if need[0]:
+            dx = torch.empty((1, BT, E), **f32)
+            bmm_raw(dg[0].view(1, BT, 4 * H), wih0.view(1, 4 * H, E), dx)
+            bmm_raw(dg[1].view(1, BT, 4 * H), wih1.view(1, 4 * H, E), dx, accumulate=True)
+            gbuf = _grad_buf(emb_weight)             # the optimizer's (zeroed) gradient bucket: added to in place
+            into = gbuf if gbuf is not None else torch.zeros_like(emb_weight)
+            call("mogan_embedding_bwd", cap.data_ptr(), lens_p, ptr(dx), ptr(keep_mask), scale, ptr(into), B, T, Tmax,
+                 emb_weight.shape[0], E, stream_ptr())
+            if gbuf is not None:
+                _grad_hit(gbuf)
+            else:
+                demb = into
+        pick = lambda t, d, on: t[d] if (t is not None and on) else None
+        return (None, None, None, None, None, None, demb, pick(dwih, 0, need[1]), pick(dwih, 1, need[2]),
+                pick(dwhh, 0, need[3]), pick(dwhh, 1, need[4]), db[0] if need[5] else None, db[1] if need[6] else None,
+                db[0] if need[7] else None, db[1] if need[8] else None)
+
+
+def lstm_encoder_train(captions, lens, emb_weight, rnn, h0=None, c0=None, keep_mask=None, scale=1.0):
+    """Embedding (+ dropout through `keep_mask` (B, T, E) uint8 and `scale`) + one-layer bidirectional LSTM over packed captions
+    WITH gradients for the embedding table and the LSTM's parameters (LstmEncoderFn).  Returns (words (B, 2H, Tmax), sent
+    (B, 2H)) or None where the kernels do not cover the module."""
+    args = _lstm_encoder_args(captions, lens, emb_weight, rnn, h0, c0)
+    if args is None:
+        return None
+    B, T, V, E, H, Tmax, lens, ws = args
+    if keep_mask is not None:
+        if keep_mask.dtype != torch.uint8 or keep_mask.device != captions.device or tuple(keep_mask.shape) != (B, T, E):
+            return None
+        keep_mask = keep_mask.contiguous()
+    cap = captions if captions.is_contiguous() else captions.contiguous()
+    h0 = _c(h0.detach()) if h0 is not None else None
+    c0 = _c(c0.detach()) if c0 is not None else None
+    out = LstmEncoderFn.apply(cap, lens, h0, c0, keep_mask, float(scale), emb_weight, *ws)
+    PK_STATS["lstm_train_fused"] = PK_STATS.get("lstm_train_fused", 0) + 1
+    return out

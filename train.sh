@@ -14,6 +14,10 @@ if [ "$DATASET" = "coco-attngan" ]; then
     else
         HIP_VISIBLE_DEVICES="$GPU" python main.py --cfg cfg/coco_train.yml --gpu "$GPU" "${@:3}"
     fi
+elif [ "$DATASET" = "coco-damsm" ]; then
+    echo "Starting DAMSM pre-training of the MS-COCO text / image encoders (one GPU)."
+    cd "$HERE/multiple-objects-gan_amd/attngan" || exit 1
+    HIP_VISIBLE_DEVICES="${GPU%%,*}" python pretrain_DAMSM.py --cfg cfg/DAMSM/coco.yml --gpu 0 "${@:3}"
 elif [ "$DATASET" = "mnist" ] || [ "$DATASET" = "clevr" ] || [ "$DATASET" = "coco-stackgan-1" ] || [ "$DATASET" = "coco-stackgan-2" ]; then
     # the StackGAN-style trees: same step on the same kernels, single process.  Real data: the trees' own TextDatasets
     # (stackgan/datasets.py, round 5) read cfg.DATA_DIR; without the data sets pass  --synthetic N  after the GPU id:
@@ -28,6 +32,6 @@ elif [ "$DATASET" = "mnist" ] || [ "$DATASET" = "clevr" ] || [ "$DATASET" = "coc
     HIP_VISIBLE_DEVICES="${GPU%%,*}" python -c "import mogan_loader as m; m.load(); from mogan_amd.stackgan.$MOD import main; main.main()" \
         --cfg "$HERE/multiple-objects-gan_amd/stackgan/$MOD/cfg/$CFG" --gpu "$GPU" "${@:3}"
 else
-    echo "Dataset argument must be either \"mnist\", \"clevr\", \"coco-stackgan-1\", \"coco-stackgan-2\", or \"coco-attngan\"."
+    echo "Dataset argument must be either \"mnist\", \"clevr\", \"coco-stackgan-1\", \"coco-stackgan-2\", \"coco-attngan\", or \"coco-damsm\"."
     exit 1
 fi
