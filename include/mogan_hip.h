@@ -631,6 +631,39 @@ int mogan_lstm_encoder_bwd(const float* dwords, const float* dsent, const int* l
                            int Tmax, int H, hipStream_t stream);
 int mogan_embedding_bwd(const long long* captions, const int* lens, const float* dx, const uint8_t* keep_mask, float scale,
                         float* demb, int B, int T, int Tmax, int V, int E, hipStream_t stream);
+
+/* ---- text encoder with cfg.RNN_TYPE = 'GRU' (csrc/mogan_gru.hip): nn.Embedding + one-layer bidirectional nn.GRU over packed
+ * captions, the three LSTM entries above restated for PyTorch's GRU (gate order r, z, n):
+ *   r = s(W_ir x + b_ir + W_hr h + b_hr), z = s(W_iz x + b_iz + W_hz h + b_hz), hn = W_hn h + b_hn,
+ *   n = tanh(W_in x + b_in + r * hn), h' = (1 - z) * n + z * h.
+ * mogan_gru_encoder_fwd: eval mode, no gradients, ONE launch.  Arguments and limits as mogan_lstm_encoder_fwd:
+ *   captions (B, T) int64 token ids (clamped to [0, V)), lens[B] on the HOST (0 <= lens[i] <= Tmax <= T, Tmax <= 32), emb (V, E)
+ *   (E % 4 == 0, E <= 320), per direction d = 0 forward / 1 reverse: w_ih[d] (3H, E), w_hh[d] (3H, H), b_ih[d], b_hh[d] (3H)
+ *   (16-byte aligned weights), H = 128, B <= 64; h0 (2, B, H) or NULL (zeros); words (B, 2H, Tmax): the hidden states, zero for
+ *   t >= lens[b]; sent (B, 2H): the final states (forward | reverse); a caption of length 0 gives a zero row and sent = h0.
+ * mogan_gru_encoder_train_fwd: the same with embedding dropout (keep_mask (B, T, E) uint8 or NULL, scale, as in the LSTM entry) and
+ *   the tensors the backward needs: x (B, Tmax, E): the masked, scaled embedding rows, gates (2, B, Tmax, 3H): the post-activation
+ *   r, z, n, hn (2, B, Tmax, H), hprev (2, B, Tmax, H): the hidden state that ENTERED step t in walk order.  All four are written
+ *   everywhere, zero at t >= lens[b].
+ * mogan_gru_encoder_bwd: back-propagation through time, one block per (direction, caption).
+ *   dwords (B, 2H, Tmax), dsent (B, 2H) (either nullable = 0), gates / hn / hprev as saved, w_hh[d] ->
+ *   dgi (2, B, Tmax, 3H) = (dr, dz, dn): the gradients of the input-side pre-activations, dgh (2, B, Tmax, 3H) = (dr, dz, dn * r):
+ *   those of the hidden side (b_hn and W_hn sit inside r * (...)); both exactly zero at t >= lens[b];
+ *   dbias_ih, dbias_hh (2, 3H) (each nullable): their sums over (b, t) in index order -- d b_ih != d b_hh in the n block.
+ *   h0 gets no gradient.  The weight gradients are GEMMs over the dense (B * Tmax) axis (mogan_bmm): dW_ih[d] = dgi[d]^T . x,
+ *   dW_hh[d] = dgh[d]^T . hprev[d], dx = sum_d dgi[d] . W_ih[d]; the table's gradient is mogan_embedding_bwd.
+ * An out-of-range argument or a NULL required pointer returns MOGAN_ERR_SHAPE and nothing is written. */
+int mogan_gru_encoder_fwd(const long long* captions, const int* lens, const float* emb, const float* const* w_ih,
+                          const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, const float* h0,
+                          float* words, float* sent, int B, int T, int Tmax, int V, int E, int H, hipStream_t stream);
+int mogan_gru_encoder_train_fwd(const long long* captions, const int* lens, const float* emb, const float* const* w_ih,
+                                const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, const float* h0,
+                                const uint8_t* keep_mask, float scale, float* words, float* sent, float* x, float* gates, float* hn,
+                                float* hprev, int B, int T, int Tmax, int V, int E, int H, hipStream_t stream);
+int mogan_gru_encoder_bwd(const float* dwords, const float* dsent, const int* lens, const float* gates, const float* hn,
+                          const float* hprev, const float* const* w_hh, float* dgi, float* dgh, float* dbias_ih, float* dbias_hh,
+                          int B, int Tmax, int H, hipStream_t stream);
+
 /* The text side of mogan_damsm_words_bwd / mogan_damsm_sent_bwd (same clamp rules).
  * words: dwords (Bc,C,T) = sum_b of the gradient of pair (b,i)'s cosines with respect to the word itself,
  *          k1[t] * wc[b,:,i,t] + k3[t] * w[i,:,t],  k1 = dcos / max(den, 1e-8),  k3 = -dcos * cos / |w|^2,

@@ -1,4 +1,4 @@
-"""DAMSM pre-training: trains the text encoder (embedding + bi-LSTM) and the image encoder's two heads against the word /
+"""DAMSM pre-training: trains the text encoder (embedding + bi-LSTM, or bi-GRU with `RNN_TYPE: 'GRU'` in the yml) and the image encoder's two heads against the word /
 sentence matching losses, i.e. produces the `text_encoder%d.pth` / `image_encoder%d.pth` pair that TRAIN.NET_E names.
 
 The reference repository holds no such script (its users download the pair from the AttnGAN project); the recipe is AttnGAN's,
@@ -7,8 +7,9 @@ encoder and the heads, the text encoder's gradient norm clipped to TRAIN.RNN_GRA
 a floor of ENCODER_LR / 10, the Inception trunk frozen (eval mode).
 
 Same flags as main.py (--cfg --gpu --manualSeed --data_dir --output_dir ...); `--synthetic N` trains on N generated batches per
-epoch when the COCO pickles are not present.  One process, one GPU.  Not built: data-parallel pre-training, training the
-Inception trunk, a GRU text encoder, hipGraph capture of this step."""
+epoch when the COCO pickles are not present.  One process, one GPU.  Both values of RNN_TYPE train on the HIP path
+(csrc/mogan_lstm.hip, csrc/mogan_gru.hip).  Not built: data-parallel pre-training, training the Inception trunk, hipGraph
+capture of this step."""
 import argparse
 import datetime
 import os
@@ -53,8 +54,9 @@ def prepare_batch(data, device):
 
 
 class DAMSMEngine:
-    """The two encoders and ONE FlatAdam over what is trained: the text encoder's nine tensors and the image encoder's heads
-    (emb_features 1x1 convolution, emb_cnn_code linear).  The trunk is frozen and stays in eval mode (the fast frozen trunk)."""
+    """The two encoders and ONE FlatAdam over what is trained: the text encoder's nine tensors (LSTM or GRU: their count and
+    sizes are taken from the module, not assumed) and the image encoder's heads (emb_features 1x1 convolution, emb_cnn_code
+    linear).  The trunk is frozen and stays in eval mode (the fast frozen trunk)."""
 
     def __init__(self, text_encoder, image_encoder, lr=None, clip=None):
         self.text_encoder, self.image_encoder = text_encoder, image_encoder

@@ -137,6 +137,9 @@ SIGNATURES = {
     "mogan_lstm_encoder_train_fwd": [P] * 10 + [F] + [P] * 6 + [I] * 6 + [P],
     "mogan_lstm_encoder_bwd": [P] * 10 + [I] * 3 + [P],
     "mogan_embedding_bwd": [P, P, P, P, F, P, I, I, I, I, I, P],
+    "mogan_gru_encoder_fwd": [P] * 10 + [I] * 6 + [P],
+    "mogan_gru_encoder_train_fwd": [P] * 9 + [F] + [P] * 6 + [I] * 6 + [P],
+    "mogan_gru_encoder_bwd": [P] * 11 + [I] * 3 + [P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }

@@ -1,10 +1,11 @@
 """The text encoder under training (RNN_ENCODER forward + backward, embedding dropout on) and the whole DAMSM pre-training step:
-the fused HIP path against the stock nn.Embedding / nn.LSTM path (RNN_ENCODER.FUSED = False, MIOpen) in the same process.
+the fused HIP path against the stock nn.Embedding / nn.LSTM (or, with --rnn GRU, nn.GRU) path (RNN_ENCODER.FUSED = False, MIOpen)
+in the same process.
 
 Per shape and path: device time per call from hip events around ONE call (median of --iters after --warmup, the two paths
 alternating), host time per call (the enqueue, no synchronise inside), and -- in a pass of its own under torch.profiler -- the
 number of device kernels and their summed duration.  Then DAMSMEngine.step at B = 48 through the real trunk, both ways.
-python tools/time_text_train.py [--out profiles/damsm_pretrain_timing.json]"""
+python tools/time_text_train.py [--rnn {LSTM,GRU}] [--out profiles/damsm_pretrain_timing.json]"""
 import argparse
 import json
 import os
@@ -25,10 +26,12 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=8)
 ap.add_argument("--out", default="")
+ap.add_argument("--rnn", choices=("LSTM", "GRU"), default="LSTM", help="cfg.RNN_TYPE of the text encoder")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "timing needs the GPU"
 set_coco_train_defaults()
 cfg.TRAIN.FLAG = True
+cfg.RNN_TYPE = args.rnn
 dev = torch.device("cuda")
 V = synthetic.VOCAB
 
