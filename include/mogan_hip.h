@@ -592,7 +592,7 @@ int mogan_adam_step(float* p, const float* g, float* m, float* v, float* ema, lo
                     float beta2, float eps, int step, float* dev_state, int eps_mode, float grad_scale,
                     float ema_decay, hipStream_t stream);
 
-/* ---- text encoder (round 6, third session; csrc/mogan_lstm.hip): nn.Embedding + one-layer bidirectional nn.LSTM over packed
+/* ---- text encoder (round 6, third session; csrc/mogan_rnn.hip): nn.Embedding + one-layer bidirectional nn.LSTM over packed
  * captions in eval mode, without gradients -- RNN_ENCODER.forward, code/coco/attngan/model.py:183-204 (pack_padded_sequence,
  * self.rnn, pad_packed_sequence, the transposes) -- as ONE launch instead of the 119 of the stock module (MIOpen).
  *   captions (B, T) int64 token ids (clamped to [0, V)), lens[B] on the HOST (sorted or not; 0 <= lens[i] <= Tmax <= T, Tmax <= 32),
@@ -632,7 +632,7 @@ int mogan_lstm_encoder_bwd(const float* dwords, const float* dsent, const int* l
 int mogan_embedding_bwd(const long long* captions, const int* lens, const float* dx, const uint8_t* keep_mask, float scale,
                         float* demb, int B, int T, int Tmax, int V, int E, hipStream_t stream);
 
-/* ---- text encoder with cfg.RNN_TYPE = 'GRU' (csrc/mogan_gru.hip): nn.Embedding + one-layer bidirectional nn.GRU over packed
+/* ---- text encoder with cfg.RNN_TYPE = 'GRU' (csrc/mogan_rnn.hip): nn.Embedding + one-layer bidirectional nn.GRU over packed
  * captions, the three LSTM entries above restated for PyTorch's GRU (gate order r, z, n):
  *   r = s(W_ir x + b_ir + W_hr h + b_hr), z = s(W_iz x + b_iz + W_hz h + b_hz), hn = W_hn h + b_hn,
  *   n = tanh(W_in x + b_in + r * hn), h' = (1 - z) * n + z * h.

@@ -120,11 +120,11 @@ class BBOX_NET(nn.Module):
 # --------------------------------------------------------------------------- text / image encoders
 class RNN_ENCODER(nn.Module):
     """model.py:120-204.  The parameters live in the stock nn.Embedding / nn.LSTM (or nn.GRU) modules (state_dict keys of the
-    reference).  On the device the forward is ONE launch: in eval mode without gradients csrc/mogan_lstm.hip's eval kernel (the
-    GAN step's frozen front-end; 119 launches and 0.8 ms of host time per call on MIOpen's LSTM), with gradients enabled its
-    training kernel with embedding dropout (DAMSM pre-training, hip/ops.LstmEncoderFn).  cfg.RNN_TYPE = 'GRU' runs the same two
-    paths on csrc/mogan_gru.hip (hip/ops.gru_encoder_forward / GruEncoderFn).  Anything else -- other sizes, more layers, one
-    direction, the CPU -- takes the stock modules."""
+    reference).  On the device the forward is ONE launch of csrc/mogan_rnn.hip for either cell: in eval mode without gradients
+    the eval kernel (the GAN step's frozen front-end; 119 launches and 0.8 ms of host time per call on MIOpen's LSTM;
+    hip/ops.rnn_encoder_forward), with gradients enabled the training kernel with embedding dropout (DAMSM pre-training,
+    hip/ops.RnnEncoderFn).  Anything else -- other sizes, more layers, one direction, the CPU -- takes the stock modules
+    (SURVEY.md section 8(a) row 21)."""
 
     def __init__(self, ntoken, ninput=300, drop_prob=0.5, nhidden=128, nlayers=1, bidirectional=True):
         super(RNN_ENCODER, self).__init__()
@@ -149,18 +149,18 @@ class RNN_ENCODER(nn.Module):
             return (weight.new_zeros(shape), weight.new_zeros(shape))
         return weight.new_zeros(shape)
 
-    FUSED = True      # on the device: embedding + bi-LSTM / bi-GRU as one launch (hip/ops.lstm_encoder_forward / lstm_encoder_train, gru_*)
+    FUSED = True      # on the device: embedding + bi-LSTM / bi-GRU as one launch (hip/ops.rnn_encoder_forward / rnn_encoder_train)
 
     def forward(self, captions, cap_lens, hidden, mask=None, drop_mask=None):
         """drop_mask: uint8 (B, T, E) keep mask of the embedding dropout (1 = keep); in training mode without one it is drawn
-        here.  nn.LSTM(dropout=...) with one layer applies none: the embedding's is the only dropout, off in eval mode."""
+        here.  nn.LSTM(dropout=...) with one layer applies none: the embedding's is the only dropout, off in eval mode.
+        `hidden` is the pair (h0, c0) of an LSTM and one tensor h0 of a GRU."""
         lens = cap_lens.data.tolist() if torch.is_tensor(cap_lens) else list(cap_lens)
-        if self.rnn_type == 'GRU':
-            return self._forward_gru(captions, lens, hidden, drop_mask)
-        fused = self.FUSED and captions.is_cuda and self.rnn_type == 'LSTM' and self.nlayers == 1 and self.bidirectional
+        states = tuple(hidden) if self.rnn_type == 'LSTM' else (hidden,)
+        fused = self.FUSED and captions.is_cuda and self.nlayers == 1 and self.bidirectional
         if fused and not self.training and not torch.is_grad_enabled():
             from ..hip import ops
-            out = ops.lstm_encoder_forward(captions, lens, self.encoder.weight, self.rnn, hidden[0], hidden[1])
+            out = ops.rnn_encoder_forward(captions, lens, self.encoder.weight, self.rnn, states)
             if out is not None:                     # (B, 2H, T_max) = the reference's output.transpose(1, 2), and (B, 2H)
                 return out
         keep = drop_mask if self.training else None
@@ -170,8 +170,8 @@ class RNN_ENCODER(nn.Module):
             if self.training and self.drop_prob > 0 and keep is None:
                 keep = (torch.rand(captions.shape[0], captions.shape[1], self.ninput, device=captions.device)
                         >= self.drop_prob).to(torch.uint8)
-            out = ops.lstm_encoder_train(captions, lens, self.encoder.weight, self.rnn, hidden[0], hidden[1], keep,
-                                         scale if keep is not None else 1.0)
+            out = ops.rnn_encoder_train(captions, lens, self.encoder.weight, self.rnn, states, keep,
+                                        scale if keep is not None else 1.0)
             if out is not None:
                 return out
         emb = self.encoder(captions)
@@ -182,34 +182,6 @@ class RNN_ENCODER(nn.Module):
         words_emb = output.transpose(1, 2)
         sent_emb = (hidden[0] if self.rnn_type == 'LSTM' else hidden).transpose(0, 1).contiguous()
         return words_emb, sent_emb.view(-1, self.nhidden * self.num_directions)
-
-    def _forward_gru(self, captions, lens, hidden, drop_mask):
-        """forward with cfg.RNN_TYPE = 'GRU': `hidden` is one tensor (2, B, H), not a pair.  The same two fused paths
-        (hip/ops.gru_encoder_forward, gru_encoder_train); the stock modules where the kernels do not cover the module."""
-        fused = self.FUSED and captions.is_cuda and self.nlayers == 1 and self.bidirectional
-        if fused and not self.training and not torch.is_grad_enabled():
-            from ..hip import ops
-            out = ops.gru_encoder_forward(captions, lens, self.encoder.weight, self.rnn, hidden)
-            if out is not None:
-                return out
-        keep = drop_mask if self.training else None
-        scale = 1.0 / (1.0 - self.drop_prob) if self.training and self.drop_prob < 1 else 1.0
-        if fused and torch.is_grad_enabled():
-            from ..hip import ops
-            if self.training and self.drop_prob > 0 and keep is None:
-                keep = (torch.rand(captions.shape[0], captions.shape[1], self.ninput, device=captions.device)
-                        >= self.drop_prob).to(torch.uint8)
-            out = ops.gru_encoder_train(captions, lens, self.encoder.weight, self.rnn, hidden, keep,
-                                        scale if keep is not None else 1.0)
-            if out is not None:
-                return out
-        emb = self.encoder(captions)
-        emb = self.drop(emb) if keep is None else emb * (keep.to(emb.dtype) * scale)
-        emb = pack_padded_sequence(emb, lens, batch_first=True)
-        output, hidden = self.rnn(emb, hidden)
-        output = pad_packed_sequence(output, batch_first=True)[0]
-        sent_emb = hidden.transpose(0, 1).contiguous()
-        return output.transpose(1, 2), sent_emb.view(-1, self.nhidden * self.num_directions)
 
 
 class CNN_ENCODER(nn.Module):

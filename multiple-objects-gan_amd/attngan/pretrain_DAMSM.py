@@ -8,7 +8,7 @@ a floor of ENCODER_LR / 10, the Inception trunk frozen (eval mode).
 
 Same flags as main.py (--cfg --gpu --manualSeed --data_dir --output_dir ...); `--synthetic N` trains on N generated batches per
 epoch when the COCO pickles are not present.  One process, one GPU.  Both values of RNN_TYPE train on the HIP path
-(csrc/mogan_lstm.hip, csrc/mogan_gru.hip).  Not built: data-parallel pre-training, training the Inception trunk, hipGraph
+(csrc/mogan_rnn.hip).  Not built: data-parallel pre-training, training the Inception trunk, hipGraph
 capture of this step."""
 import argparse
 import datetime

@@ -1874,14 +1874,17 @@ def adam_step(p, g, m, v, ema, lr, beta1, beta2, eps, step=0, dev_state=None, ep
          ptr(dev_state), eps_mode, grad_scale, ema_decay, stream_ptr())
 
 
-# ------------------------------------------------------------------------------- text encoder (csrc/mogan_lstm.hip)
-def _lstm_encoder_args(captions, lens, emb_weight, rnn, h0, c0):
+# ------------------------------------------------------------------------------- text encoder (csrc/mogan_rnn.hip)
+# PK_STATS counts the calls per cell: lstm_fused / gru_fused (eval), lstm_train_fused / gru_train_fused (training)
+def _rnn_encoder_args(captions, lens, emb_weight, rnn, states):
     """What both text-encoder paths need checked before a pointer reaches the kernels: the module is the one-layer bidirectional
-    LSTM with 128 units per direction, the sizes are inside the kernels' limits, and every tensor (the embedding table and the
-    initial states included) is float32, dense, on the captions' device and of the expected shape.
-    Returns (B, T, V, E, H, Tmax, lens, ws) or None (the caller keeps the stock modules)."""
-    if (not isinstance(rnn, torch.nn.LSTM) or rnn.num_layers != 1 or not rnn.bidirectional or not rnn.batch_first
-            or rnn.hidden_size != 128 or not rnn.bias or getattr(rnn, "proj_size", 0)):
+    nn.LSTM or nn.GRU with 128 units per direction, `states` is the cell's tuple of initial states ((h0, c0) or (h0,), each a
+    tensor or None), the sizes are inside the kernels' limits, and every tensor (the embedding table and the initial states
+    included) is float32, dense, on the captions' device and of the expected shape.
+    Returns (B, T, V, E, H, Tmax, lens, ws, cell) with cell = 'lstm' or 'gru', or None (the caller keeps the stock modules)."""
+    cell = "lstm" if isinstance(rnn, torch.nn.LSTM) else "gru" if isinstance(rnn, torch.nn.GRU) else None
+    if (cell is None or len(states) != (2 if cell == "lstm" else 1) or rnn.num_layers != 1 or not rnn.bidirectional
+            or not rnn.batch_first or rnn.hidden_size != 128 or not rnn.bias or getattr(rnn, "proj_size", 0)):
         return None
     H = rnn.hidden_size
     if captions.dim() != 2 or emb_weight.dim() != 2:
@@ -1900,10 +1903,10 @@ def _lstm_encoder_args(captions, lens, emb_weight, rnn, h0, c0):
         return None
     if emb_weight.dtype != torch.float32 or not emb_weight.is_contiguous() or emb_weight.device != dev:
         return None
-    for st in (h0, c0):
+    for st in states:
         if st is not None and (st.dtype != torch.float32 or st.device != dev or tuple(st.shape) != (2, B, H)):
             return None
-    return B, T, V, E, H, Tmax, lens, ws
+    return B, T, V, E, H, Tmax, lens, ws, cell
 
 
 def _ptr_pairs(ws):
@@ -1913,87 +1916,97 @@ def _ptr_pairs(ws):
     return arr, [ctypes.cast(a, ctypes.c_void_p) for a in arr]
 
 
-def lstm_encoder_forward(captions, lens, emb_weight, rnn, h0=None, c0=None):
-    """Embedding + one-layer bidirectional LSTM over packed captions, eval mode, no gradient, as ONE launch
-    (mogan_lstm_encoder_fwd); `rnn` is the nn.LSTM whose parameters are used.  Returns (words (B, 2H, Tmax), sent (B, 2H)) or
-    None where the kernel does not cover the module (then the caller keeps the stock path)."""
+def rnn_encoder_forward(captions, lens, emb_weight, rnn, states):
+    """Embedding + one-layer bidirectional LSTM or GRU over packed captions, eval mode, no gradient, as ONE launch
+    (mogan_lstm_encoder_fwd / mogan_gru_encoder_fwd); `rnn` is the nn.LSTM / nn.GRU whose parameters are used, `states` its
+    initial states (h0, c0) / (h0,).  Returns (words (B, 2H, Tmax), sent (B, 2H)) or None where the kernel does not cover the
+    module (then the caller keeps the stock path)."""
     import ctypes
-    args = _lstm_encoder_args(captions, lens, emb_weight, rnn, h0, c0)
+    args = _rnn_encoder_args(captions, lens, emb_weight, rnn, states)
     if args is None:
         return None
-    B, T, V, E, H, Tmax, lens, ws = args
+    B, T, V, E, H, Tmax, lens, ws, cell = args
     dev = captions.device
     cap = captions if captions.is_contiguous() else captions.contiguous()
     words = torch.empty((B, 2 * H, Tmax), dtype=torch.float32, device=dev)
     sent = torch.empty((B, 2 * H), dtype=torch.float32, device=dev)
     keep, arr = _ptr_pairs(ws)
     lens_c = (ctypes.c_int * B)(*lens)
-    h0p = ptr(_c(h0)) if h0 is not None else None
-    c0p = ptr(_c(c0)) if c0 is not None else None
-    call("mogan_lstm_encoder_fwd", cap.data_ptr(), ctypes.cast(lens_c, ctypes.c_void_p), emb_weight.data_ptr(),
-         arr[0], arr[1], arr[2], arr[3], h0p, c0p, words.data_ptr(), sent.data_ptr(), B, T, Tmax, V, E, H, stream_ptr())
-    PK_STATS["lstm_fused"] = PK_STATS.get("lstm_fused", 0) + 1
+    states = [_c(st) if st is not None else None for st in states]
+    call("mogan_%s_encoder_fwd" % cell, cap.data_ptr(), ctypes.cast(lens_c, ctypes.c_void_p), emb_weight.data_ptr(),
+         arr[0], arr[1], arr[2], arr[3], *[ptr(st) for st in states], words.data_ptr(), sent.data_ptr(), B, T, Tmax, V, E, H,
+         stream_ptr())
+    PK_STATS[cell + "_fused"] = PK_STATS.get(cell + "_fused", 0) + 1
     return words, sent
 
 
-class LstmEncoderFn(torch.autograd.Function):
-    """The text encoder under training (csrc/mogan_lstm.hip): mogan_lstm_encoder_train_fwd forward; backward =
-    mogan_lstm_encoder_bwd (BPTT -> pre-activation gate gradients and the bias gradients), the weight gradients as mogan_bmm
-    GEMMs over the dense (B * Tmax) axis, mogan_embedding_bwd for the table.  Differentiable inputs: the embedding table and the
-    eight LSTM parameters (w_ih, w_ih_reverse, w_hh, w_hh_reverse, b_ih, b_ih_reverse, b_hh, b_hh_reverse); h0 / c0 get none."""
+class RnnEncoderFn(torch.autograd.Function):
+    """The text encoder under training (csrc/mogan_rnn.hip): mogan_{lstm,gru}_encoder_train_fwd forward; backward =
+    mogan_{lstm,gru}_encoder_bwd (BPTT -> the input-side and hidden-side pre-activation gate gradients dgi / dgh and the bias
+    gradients dbi / dbh), the weight gradients as mogan_bmm GEMMs over the dense (B * Tmax) axis (dgi against x and W_ih, dgh
+    against hprev), mogan_embedding_bwd for the table.  The GRU's two sides differ (the n block of the hidden side carries the
+    factor r); the LSTM is the case dgi is dgh, dbi is dbh.  `aux` is the cell's own saved tensor: c_t (LSTM) or hn (GRU).
+    Differentiable inputs: the embedding table and the eight parameters (w_ih, w_ih_reverse, w_hh, w_hh_reverse, b_ih,
+    b_ih_reverse, b_hh, b_hh_reverse); the initial states get none."""
 
     @staticmethod
-    def forward(ctx, cap, lens, h0, c0, keep_mask, scale, emb_weight, *ws):
+    def forward(ctx, cell, cap, lens, states, keep_mask, scale, emb_weight, *ws):
         import ctypes
         B, T = cap.shape
         V, E = emb_weight.shape
         H, Tmax = 128, max(lens)
+        G = (4 if cell == "lstm" else 3) * H
         dev = cap.device
         f32 = dict(dtype=torch.float32, device=dev)
         words, sent = torch.empty((B, 2 * H, Tmax), **f32), torch.empty((B, 2 * H), **f32)
         x = torch.empty((B, Tmax, E), **f32)
-        gates, cells = torch.empty((2, B, Tmax, 4 * H), **f32), torch.empty((2, B, Tmax, H), **f32)
+        gates, aux = torch.empty((2, B, Tmax, G), **f32), torch.empty((2, B, Tmax, H), **f32)
         hprev = torch.empty((2, B, Tmax, H), **f32)
         keep, arr = _ptr_pairs(ws)
         lens_c = (ctypes.c_int * B)(*lens)
-        call("mogan_lstm_encoder_train_fwd", cap.data_ptr(), ctypes.cast(lens_c, ctypes.c_void_p), emb_weight.data_ptr(),
-             arr[0], arr[1], arr[2], arr[3], ptr(h0), ptr(c0), ptr(keep_mask), float(scale), ptr(words), ptr(sent), ptr(x),
-             ptr(gates), ptr(cells), ptr(hprev), B, T, Tmax, V, E, H, stream_ptr())
-        ctx.save_for_backward(x, gates, cells, hprev, ws[0], ws[1], ws[2], ws[3])
-        ctx.aux = (cap, lens, c0, keep_mask, float(scale), emb_weight)
+        call("mogan_%s_encoder_train_fwd" % cell, cap.data_ptr(), ctypes.cast(lens_c, ctypes.c_void_p), emb_weight.data_ptr(),
+             arr[0], arr[1], arr[2], arr[3], *[ptr(st) for st in states], ptr(keep_mask), float(scale), ptr(words), ptr(sent),
+             ptr(x), ptr(gates), ptr(aux), ptr(hprev), B, T, Tmax, V, E, H, stream_ptr())
+        ctx.save_for_backward(x, gates, aux, hprev, ws[0], ws[1], ws[2], ws[3])
+        ctx.aux = (cell, cap, lens, states, keep_mask, float(scale), emb_weight)
         return words, sent
 
     @staticmethod
     def backward(ctx, dwords, dsent):
         import ctypes
-        x, gates, cells, hprev, wih0, wih1, whh0, whh1 = ctx.saved_tensors
-        cap, lens, c0, keep_mask, scale, emb_weight = ctx.aux
+        x, gates, aux, hprev, wih0, wih1, whh0, whh1 = ctx.saved_tensors
+        cell, cap, lens, states, keep_mask, scale, emb_weight = ctx.aux
         B, Tmax, E = x.shape
         T = cap.shape[1]
-        H = 128
+        H, G = 128, gates.shape[3]
         f32 = dict(dtype=torch.float32, device=x.device)
         dwords = _c(dwords) if dwords is not None else None
         dsent = _c(dsent) if dsent is not None else None
-        dg, db = torch.empty((2, B, Tmax, 4 * H), **f32), torch.empty((2, 4 * H), **f32)
+        dgi, dbi = torch.empty((2, B, Tmax, G), **f32), torch.empty((2, G), **f32)
         keep, arr = _ptr_pairs([whh0, whh1])
         lens_c = (ctypes.c_int * B)(*lens)
         lens_p = ctypes.cast(lens_c, ctypes.c_void_p)
-        call("mogan_lstm_encoder_bwd", ptr(dwords), ptr(dsent), lens_p, ptr(gates), ptr(cells), ptr(hprev), ptr(c0), arr[0],
-             ptr(dg), ptr(db), B, Tmax, H, stream_ptr())
+        if cell == "lstm":
+            dgh, dbh = dgi, dbi
+            call("mogan_lstm_encoder_bwd", ptr(dwords), ptr(dsent), lens_p, ptr(gates), ptr(aux), ptr(hprev), ptr(states[1]),
+                 arr[0], ptr(dgi), ptr(dbi), B, Tmax, H, stream_ptr())
+        else:
+            dgh, dbh = torch.empty((2, B, Tmax, G), **f32), torch.empty((2, G), **f32)
+            call("mogan_gru_encoder_bwd", ptr(dwords), ptr(dsent), lens_p, ptr(gates), ptr(aux), ptr(hprev), arr[0],
+                 ptr(dgi), ptr(dgh), ptr(dbi), ptr(dbh), B, Tmax, H, stream_ptr())
         need = ctx.needs_input_grad[6:]
         BT = B * Tmax
-        dgt = dg.view(2, BT, 4 * H).transpose(1, 2)
         demb = dwih = dwhh = None
         if need[1] or need[2]:
-            dwih = torch.empty((2, 4 * H, E), **f32)
-            bmm_raw(dgt, x.view(1, BT, E).expand(2, BT, E), dwih)
+            dwih = torch.empty((2, G, E), **f32)
+            bmm_raw(dgi.view(2, BT, G).transpose(1, 2), x.view(1, BT, E).expand(2, BT, E), dwih)
         if need[3] or need[4]:
-            dwhh = torch.empty((2, 4 * H, H), **f32)
-            bmm_raw(dgt, hprev.view(2, BT, H), dwhh)
+            dwhh = torch.empty((2, G, H), **f32)
+            bmm_raw(dgh.view(2, BT, G).transpose(1, 2), hprev.view(2, BT, H), dwhh)
         if need[0]:
             dx = torch.empty((1, BT, E), **f32)
-            bmm_raw(dg[0].view(1, BT, 4 * H), wih0.view(1, 4 * H, E), dx)
-            bmm_raw(dg[1].view(1, BT, 4 * H), wih1.view(1, 4 * H, E), dx, accumulate=True)
+            bmm_raw(dgi[0].view(1, BT, G), wih0.view(1, G, E), dx)
+            bmm_raw(dgi[1].view(1, BT, G), wih1.view(1, G, E), dx, accumulate=True)
             gbuf = _grad_buf(emb_weight)             # the optimizer's (zeroed) gradient bucket: added to in place
             into = gbuf if gbuf is not None else torch.zeros_like(emb_weight)
             call("mogan_embedding_bwd", cap.data_ptr(), lens_p, ptr(dx), ptr(keep_mask), scale, ptr(into), B, T, Tmax,
@@ -2004,171 +2017,24 @@ class LstmEncoderFn(torch.autograd.Function):
                 demb = into
         pick = lambda t, d, on: t[d] if (t is not None and on) else None
         return (None, None, None, None, None, None, demb, pick(dwih, 0, need[1]), pick(dwih, 1, need[2]),
-                pick(dwhh, 0, need[3]), pick(dwhh, 1, need[4]), db[0] if need[5] else None, db[1] if need[6] else None,
-                db[0] if need[7] else None, db[1] if need[8] else None)
-
-
-def lstm_encoder_train(captions, lens, emb_weight, rnn, h0=None, c0=None, keep_mask=None, scale=1.0):
-    """Embedding (+ dropout through `keep_mask` (B, T, E) uint8 and `scale`) + one-layer bidirectional LSTM over packed captions
-    WITH gradients for the embedding table and the LSTM's parameters (LstmEncoderFn).  Returns (words (B, 2H, Tmax), sent
-    (B, 2H)) or None where the kernels do not cover the module."""
-    args = _lstm_encoder_args(captions, lens, emb_weight, rnn, h0, c0)
-    if args is None:
-        return None
-    B, T, V, E, H, Tmax, lens, ws = args
-    if keep_mask is not None:
-        if keep_mask.dtype != torch.uint8 or keep_mask.device != captions.device or tuple(keep_mask.shape) != (B, T, E):
-            return None
-        keep_mask = keep_mask.contiguous()
-    cap = captions if captions.is_contiguous() else captions.contiguous()
-    h0 = _c(h0.detach()) if h0 is not None else None
-    c0 = _c(c0.detach()) if c0 is not None else None
-    out = LstmEncoderFn.apply(cap, lens, h0, c0, keep_mask, float(scale), emb_weight, *ws)
-    PK_STATS["lstm_train_fused"] = PK_STATS.get("lstm_train_fused", 0) + 1
-    return out
-
-
-# ------------------------------------------------------------------------------- text encoder, GRU (csrc/mogan_gru.hip)
-def _gru_encoder_args(captions, lens, emb_weight, rnn, h0):
-    """_lstm_encoder_args for cfg.RNN_TYPE = 'GRU': the module is the one-layer bidirectional nn.GRU with 128 units per direction,
-    the sizes are inside the kernels' limits, and every tensor (the embedding table and the initial state included) is float32,
-    dense, on the captions' device and of the expected shape.
-    Returns (B, T, V, E, H, Tmax, lens, ws) or None (the caller keeps the stock modules)."""
-    if (not isinstance(rnn, torch.nn.GRU) or rnn.num_layers != 1 or not rnn.bidirectional or not rnn.batch_first
-            or rnn.hidden_size != 128 or not rnn.bias):
-        return None
-    H = rnn.hidden_size
-    if captions.dim() != 2 or emb_weight.dim() != 2:
-        return None
-    B, T = captions.shape
-    V, E = emb_weight.shape
-    lens = [int(v) for v in lens]
-    Tmax = max(lens) if lens else 0
-    if (len(lens) != B or B > 64 or Tmax < 1 or Tmax > 32 or Tmax > T or E > 320 or E % 4 or min(lens) < 0
-            or captions.dtype != torch.int64 or rnn.input_size != E):
-        return None
-    ws = [rnn.weight_ih_l0, rnn.weight_ih_l0_reverse, rnn.weight_hh_l0, rnn.weight_hh_l0_reverse,
-          rnn.bias_ih_l0, rnn.bias_ih_l0_reverse, rnn.bias_hh_l0, rnn.bias_hh_l0_reverse]
-    dev = captions.device
-    if any(w.dtype != torch.float32 or not w.is_contiguous() or w.data_ptr() % 16 or w.device != dev for w in ws):
-        return None
-    if emb_weight.dtype != torch.float32 or not emb_weight.is_contiguous() or emb_weight.device != dev:
-        return None
-    if h0 is not None and (h0.dtype != torch.float32 or h0.device != dev or tuple(h0.shape) != (2, B, H)):
-        return None
-    return B, T, V, E, H, Tmax, lens, ws
-
-
-def gru_encoder_forward(captions, lens, emb_weight, rnn, h0=None):
-    """Embedding + one-layer bidirectional GRU over packed captions, eval mode, no gradient, as ONE launch
-    (mogan_gru_encoder_fwd); `rnn` is the nn.GRU whose parameters are used.  Returns (words (B, 2H, Tmax), sent (B, 2H)) or
-    None where the kernel does not cover the module (then the caller keeps the stock path)."""
-    import ctypes
-    args = _gru_encoder_args(captions, lens, emb_weight, rnn, h0)
-    if args is None:
-        return None
-    B, T, V, E, H, Tmax, lens, ws = args
-    dev = captions.device
-    cap = captions if captions.is_contiguous() else captions.contiguous()
-    words = torch.empty((B, 2 * H, Tmax), dtype=torch.float32, device=dev)
-    sent = torch.empty((B, 2 * H), dtype=torch.float32, device=dev)
-    keep, arr = _ptr_pairs(ws)
-    lens_c = (ctypes.c_int * B)(*lens)
-    h0p = ptr(_c(h0)) if h0 is not None else None
-    call("mogan_gru_encoder_fwd", cap.data_ptr(), ctypes.cast(lens_c, ctypes.c_void_p), emb_weight.data_ptr(),
-         arr[0], arr[1], arr[2], arr[3], h0p, words.data_ptr(), sent.data_ptr(), B, T, Tmax, V, E, H, stream_ptr())
-    PK_STATS["gru_fused"] = PK_STATS.get("gru_fused", 0) + 1
-    return words, sent
-
-
-class GruEncoderFn(torch.autograd.Function):
-    """The GRU text encoder under training (csrc/mogan_gru.hip): mogan_gru_encoder_train_fwd forward; backward =
-    mogan_gru_encoder_bwd (BPTT -> the input-side and hidden-side pre-activation gradients dgi / dgh and both bias gradients:
-    d b_ih != d b_hh, the n block of the hidden side carries the factor r), the weight gradients as mogan_bmm GEMMs over the
-    dense (B * Tmax) axis (dgi against x and W_ih, dgh against hprev), mogan_embedding_bwd for the table.  Differentiable
-    inputs: the embedding table and the eight GRU parameters (w_ih, w_ih_reverse, w_hh, w_hh_reverse, b_ih, b_ih_reverse, b_hh,
-    b_hh_reverse); h0 gets none."""
-
-    @staticmethod
-    def forward(ctx, cap, lens, h0, keep_mask, scale, emb_weight, *ws):
-        import ctypes
-        B, T = cap.shape
-        V, E = emb_weight.shape
-        H, Tmax = 128, max(lens)
-        dev = cap.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        words, sent = torch.empty((B, 2 * H, Tmax), **f32), torch.empty((B, 2 * H), **f32)
-        x = torch.empty((B, Tmax, E), **f32)
-        gates, hn = torch.empty((2, B, Tmax, 3 * H), **f32), torch.empty((2, B, Tmax, H), **f32)
-        hprev = torch.empty((2, B, Tmax, H), **f32)
-        keep, arr = _ptr_pairs(ws)
-        lens_c = (ctypes.c_int * B)(*lens)
-        call("mogan_gru_encoder_train_fwd", cap.data_ptr(), ctypes.cast(lens_c, ctypes.c_void_p), emb_weight.data_ptr(),
-             arr[0], arr[1], arr[2], arr[3], ptr(h0), ptr(keep_mask), float(scale), ptr(words), ptr(sent), ptr(x),
-             ptr(gates), ptr(hn), ptr(hprev), B, T, Tmax, V, E, H, stream_ptr())
-        ctx.save_for_backward(x, gates, hn, hprev, ws[0], ws[1], ws[2], ws[3])
-        ctx.aux = (cap, lens, keep_mask, float(scale), emb_weight)
-        return words, sent
-
-    @staticmethod
-    def backward(ctx, dwords, dsent):
-        import ctypes
-        x, gates, hn, hprev, wih0, wih1, whh0, whh1 = ctx.saved_tensors
-        cap, lens, keep_mask, scale, emb_weight = ctx.aux
-        B, Tmax, E = x.shape
-        T = cap.shape[1]
-        H = 128
-        f32 = dict(dtype=torch.float32, device=x.device)
-        dwords = _c(dwords) if dwords is not None else None
-        dsent = _c(dsent) if dsent is not None else None
-        dgi, dgh = torch.empty((2, B, Tmax, 3 * H), **f32), torch.empty((2, B, Tmax, 3 * H), **f32)
-        dbi, dbh = torch.empty((2, 3 * H), **f32), torch.empty((2, 3 * H), **f32)
-        keep, arr = _ptr_pairs([whh0, whh1])
-        lens_c = (ctypes.c_int * B)(*lens)
-        lens_p = ctypes.cast(lens_c, ctypes.c_void_p)
-        call("mogan_gru_encoder_bwd", ptr(dwords), ptr(dsent), lens_p, ptr(gates), ptr(hn), ptr(hprev), arr[0],
-             ptr(dgi), ptr(dgh), ptr(dbi), ptr(dbh), B, Tmax, H, stream_ptr())
-        need = ctx.needs_input_grad[5:]
-        BT = B * Tmax
-        demb = dwih = dwhh = None
-        if need[1] or need[2]:
-            dwih = torch.empty((2, 3 * H, E), **f32)
-            bmm_raw(dgi.view(2, BT, 3 * H).transpose(1, 2), x.view(1, BT, E).expand(2, BT, E), dwih)
-        if need[3] or need[4]:
-            dwhh = torch.empty((2, 3 * H, H), **f32)
-            bmm_raw(dgh.view(2, BT, 3 * H).transpose(1, 2), hprev.view(2, BT, H), dwhh)
-        if need[0]:
-            dx = torch.empty((1, BT, E), **f32)
-            bmm_raw(dgi[0].view(1, BT, 3 * H), wih0.view(1, 3 * H, E), dx)
-            bmm_raw(dgi[1].view(1, BT, 3 * H), wih1.view(1, 3 * H, E), dx, accumulate=True)
-            gbuf = _grad_buf(emb_weight)             # the optimizer's (zeroed) gradient bucket: added to in place
-            into = gbuf if gbuf is not None else torch.zeros_like(emb_weight)
-            call("mogan_embedding_bwd", cap.data_ptr(), lens_p, ptr(dx), ptr(keep_mask), scale, ptr(into), B, T, Tmax,
-                 emb_weight.shape[0], E, stream_ptr())
-            if gbuf is not None:
-                _grad_hit(gbuf)
-            else:
-                demb = into
-        pick = lambda t, d, on: t[d] if (t is not None and on) else None
-        return (None, None, None, None, None, demb, pick(dwih, 0, need[1]), pick(dwih, 1, need[2]),
                 pick(dwhh, 0, need[3]), pick(dwhh, 1, need[4]), dbi[0] if need[5] else None, dbi[1] if need[6] else None,
                 dbh[0] if need[7] else None, dbh[1] if need[8] else None)
 
 
-def gru_encoder_train(captions, lens, emb_weight, rnn, h0=None, keep_mask=None, scale=1.0):
-    """Embedding (+ dropout through `keep_mask` (B, T, E) uint8 and `scale`) + one-layer bidirectional GRU over packed captions
-    WITH gradients for the embedding table and the GRU's parameters (GruEncoderFn).  Returns (words (B, 2H, Tmax), sent
-    (B, 2H)) or None where the kernels do not cover the module."""
-    args = _gru_encoder_args(captions, lens, emb_weight, rnn, h0)
+def rnn_encoder_train(captions, lens, emb_weight, rnn, states, keep_mask=None, scale=1.0):
+    """Embedding (+ dropout through `keep_mask` (B, T, E) uint8 and `scale`) + one-layer bidirectional LSTM or GRU over packed
+    captions WITH gradients for the embedding table and the module's parameters (RnnEncoderFn).  Returns (words (B, 2H, Tmax),
+    sent (B, 2H)) or None where the kernels do not cover the module."""
+    args = _rnn_encoder_args(captions, lens, emb_weight, rnn, states)
     if args is None:
         return None
-    B, T, V, E, H, Tmax, lens, ws = args
+    B, T, V, E, H, Tmax, lens, ws, cell = args
     if keep_mask is not None:
         if keep_mask.dtype != torch.uint8 or keep_mask.device != captions.device or tuple(keep_mask.shape) != (B, T, E):
             return None
         keep_mask = keep_mask.contiguous()
     cap = captions if captions.is_contiguous() else captions.contiguous()
-    h0 = _c(h0.detach()) if h0 is not None else None
-    out = GruEncoderFn.apply(cap, lens, h0, keep_mask, float(scale), emb_weight, *ws)
-    PK_STATS["gru_train_fused"] = PK_STATS.get("gru_train_fused", 0) + 1
+    states = tuple(_c(st.detach()) if st is not None else None for st in states)
+    out = RnnEncoderFn.apply(cell, cap, lens, states, keep_mask, float(scale), emb_weight, *ws)
+    PK_STATS[cell + "_train_fused"] = PK_STATS.get(cell + "_train_fused", 0) + 1
     return out

@@ -18,20 +18,22 @@ def test_gru_reference_stays_inside_the_step_assertions():
 
 
 def test_gru_encoder_argument_checks_decline_what_the_kernels_do_not_cover():
-    """hip/ops._gru_encoder_args, the one helper of the eval and the training path: the covered module is accepted; an nn.LSTM,
-    H != 128, a unidirectional module, a half-precision or off-device tensor, a mis-shaped h0, Tmax > 32, E % 4 != 0 and
-    len(lens) != B give None (the caller keeps the stock modules) before any pointer is taken."""
+    """hip/ops._rnn_encoder_args, the one helper of the eval and the training path, with an nn.GRU and its one state: the covered
+    module is accepted; an nn.LSTM handed that state, an nn.GRU handed (h, c), an nn.RNN, H != 128, a unidirectional module, a
+    half-precision or off-device tensor, a mis-shaped h0, Tmax > 32, E % 4 != 0 and len(lens) != B give None (the caller keeps
+    the stock modules) before any pointer is taken."""
     G = lambda *a, **k: torch.nn.GRU(*a, batch_first=True, **k)
     rnn = G(300, 128, 1, bidirectional=True)
     cap = torch.ones(3, 12, dtype=torch.int64)
     lens = [12, 5, 1]
     emb = torch.zeros(50, 300)
     h = torch.zeros(2, 3, 128)
-    ok = ops._gru_encoder_args(cap, lens, emb, rnn, h)
+    ok = ops._rnn_encoder_args(cap, lens, emb, rnn, (h,))
     assert ok is not None and ok[:6] == (3, 12, 50, 300, 128, 12) and len(ok[7]) == 8
-    assert ops._gru_encoder_args(cap, lens, emb, rnn, None) is not None
-    assert ops._gru_encoder_args(cap, [12, 0, 0], emb, rnn, None) is not None              # empty captions are covered
+    assert ops._rnn_encoder_args(cap, lens, emb, rnn, (None,)) is not None
+    assert ops._rnn_encoder_args(cap, [12, 0, 0], emb, rnn, (None,)) is not None           # empty captions are covered
     bad = [dict(rnn=torch.nn.LSTM(300, 128, 1, batch_first=True, bidirectional=True)), dict(rnn=G(300, 64, 1, bidirectional=True)),
+           dict(rnn=torch.nn.RNN(300, 128, 1, batch_first=True, bidirectional=True)),
            dict(rnn=G(300, 128, 1)), dict(rnn=G(300, 128, 2, bidirectional=True)), dict(rnn=G(300, 128, 1, bidirectional=True).half()),
            dict(rnn=G(300, 128, 1, bidirectional=True).to("meta")), dict(emb=emb.half()), dict(emb=emb.to("meta")),
            dict(emb=emb.t()), dict(h0=h.half()), dict(h0=h.to("meta")), dict(h0=torch.zeros(2, 4, 128)),
@@ -41,7 +43,8 @@ def test_gru_encoder_argument_checks_decline_what_the_kernels_do_not_cover():
     for kw in bad:
         a = dict(cap=cap, lens=lens, emb=emb, rnn=rnn, h0=h)
         a.update(kw)
-        assert ops._gru_encoder_args(a["cap"], a["lens"], a["emb"], a["rnn"], a["h0"]) is None, list(kw)
-    for fn in (ops.gru_encoder_forward, ops.gru_encoder_train):            # both public functions decline through it
-        assert fn(cap, lens, emb.half(), rnn, h) is None
-        assert fn(cap, lens, emb, torch.nn.LSTM(300, 128, 1, batch_first=True, bidirectional=True), h) is None
+        assert ops._rnn_encoder_args(a["cap"], a["lens"], a["emb"], a["rnn"], (a["h0"],)) is None, list(kw)
+    assert ops._rnn_encoder_args(cap, lens, emb, rnn, (h, h)) is None                          # an nn.GRU handed (h, c)
+    for fn in (ops.rnn_encoder_forward, ops.rnn_encoder_train):            # both public functions decline through it
+        assert fn(cap, lens, emb.half(), rnn, (h,)) is None
+        assert fn(cap, lens, emb, torch.nn.LSTM(300, 128, 1, batch_first=True, bidirectional=True), (h,)) is None

@@ -1,4 +1,4 @@
-"""-m gpu: the text encoder with cfg.RNN_TYPE = 'GRU' on the HIP path (csrc/mogan_gru.hip) -- the eval forward as one launch, the
+"""-m gpu: the text encoder with cfg.RNN_TYPE = 'GRU' on the HIP path (csrc/mogan_rnn.hip) -- the eval forward as one launch, the
 training forward and back-propagation through time through the module, the three entry points under the memory contract, two
 whole pre-training steps against the CPU restatement in fp64 (tests/damsm_gru_cases.py) and the pre-training entry point.
 

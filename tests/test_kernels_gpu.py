@@ -1408,7 +1408,7 @@ def test_panel_tail_box_filter():
 @pytest.mark.parametrize("case", [(16, 12, [12, 12, 11, 10, 9, 9, 8, 8, 7, 7, 6, 6, 5, 5, 5, 5]), (6, 18, [15, 11, 9, 9, 6, 1]),
                                   (1, 12, [12]), (3, 32, [32, 20, 2])])
 def test_text_encoder_as_one_launch(case):
-    """csrc/mogan_lstm.hip (mogan_lstm_encoder_fwd): RNN_ENCODER.forward in eval mode -- embedding, packed bidirectional LSTM,
+    """csrc/mogan_rnn.hip (mogan_lstm_encoder_fwd): RNN_ENCODER.forward in eval mode -- embedding, packed bidirectional LSTM,
     unpacking, the transposes (model.py:183-204) -- as one launch against the stock nn.Embedding / nn.LSTM path of the same module
     on the device (MIOpen) and against torch on the CPU in fp64: zero / non-zero initial state, T_max < T, a one-word caption."""
     from mogan_amd.attngan import model
