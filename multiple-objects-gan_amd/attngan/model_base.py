@@ -68,7 +68,7 @@ class _HipBNMixin:
         """groups > 1: x holds `groups` batches one behind the other, each of which the reference passes through this layer in a
         call of its own (one BatchNorm call per object; D(real) and D(fake) of a discriminator update): own batch
         statistics per group, running statistics and the call counter updated group after group -- one launch where the maps
-        are small, else the large-map kernels once per group on the group's slice (hip/ops.BNActGroupedFn)."""
+        are small, else the large-map kernels once per group on the group's slice (hip/ops.BNActFn with groups > 1)."""
         if self.training and groups > 1:
             assert residual is None
             for _ in range(groups):

@@ -1,19 +1,29 @@
 // mogan_norm.hip -- BatchNorm (training statistics) fused with GLU / LeakyReLU / ReLU / residual-add,
 // forward and backward, plus the eval-mode per-channel affine used by the frozen Inception trunk.
 //
-// All of it is HBM-bound.  Layout x (B,C,HW), NCHW.  Kernels:
-//   bn_partial   grid (C, YS): one block reduces a (batch-range x HW-range) slab of one channel with
-//                float4 loads and fp64 accumulators (E[x^2]-mean^2 is then safe), wave64 shuffle
-//                reduction, one (sum,sumsq) pair per block into the workspace;
-//   bn_finalize  one wave per channel: fixed-order sum of the partials -> mean, invstd, running stats;
-//   bn_act_fwd   y = act(gamma*xhat+beta) (+res): one pass, float4;  GLU reads channel c and c+C/2;
-//   bn_bwd_partial / bn_bwd_finalize / bn_bwd_apply: the two-reduction BN backward with the activation
-//                backward recomputed from x (nothing but x, mean, invstd is saved by the forward).
+// All of it is HBM-bound.  Layout x (B,C,HW), NCHW.  What is computed per channel and per element -- statistics, running
+// update, act(x*sc+sh), the activation backward, dx, dgamma / dbeta -- is mogan_bn.h; the kernels here only differ in how
+// they spread that over blocks and launches.  Sums are fp64 (E[x^2]-mean^2 is then safe), wave64 shuffle reductions, fixed
+// order; the backward recomputes the activation from x (the forward saves nothing but x, mean, invstd).  Three paths per
+// direction, chosen from the shape alone:
+//   one launch     bn_small_ok: B*HW <= SMALL_NE values per channel and HW >= 16.  A block per output channel (GLU: per
+//                  pair) holds the channel's values in registers, reduces them and applies (bn_small_fwd / bn_small_bwd).
+//                  The grouped entry points are this path with G > 1: G calls, each with its own statistics, in one launch.
+//   two launches   bn_fused_ok: larger maps with HW % 4 == 0 and HW >= 64.  bn_partial / bn_bwd_partial, grid (C, YS),
+//                  leave one fp64 partial sum per (batch-range x HW-range) slab; the apply kernels (bn_fwd_apply_fused /
+//                  bn_bwd_apply_fused) sum a channel's partials per wave and one block per channel also writes mean /
+//                  invstd / running statistics, or dgamma / dbeta.
+//   three launches everything else (odd plane sizes beyond the one-launch limit, HW < 16, BatchNorm1d with its own
+//                  thread-per-channel bn1d_partial): partial, bn_finalize / bn_bwd_finalize (a thread per channel), then
+//                  bn_act_fwd / bn_bwd_apply.  mogan_bn_stats and mogan_bn_act_fwd are this path's two halves.
+// Apply grids carry (image, channel) in gridDim.y: batches with B*Cy > 65535 go out in chunks (for_batch_chunks).
 // Replaces nn.BatchNorm1d/2d + GLU / nn.LeakyReLU / nn.ReLU at code/coco/attngan/model.py:48-81,
 // 96-101,364-373,575-611,667-680.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/mogan_hip.h"
+#include "mogan_bn.h"
 
 namespace {
 
@@ -63,7 +73,16 @@ static Split make_split(int B, int C, int HW) {
     return s;
 }
 
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
+// W consecutive values (W == 4: one 16-byte access, the address is 16-byte aligned)
+template <int W>
+__device__ __forceinline__ void load_vec(const float* p, float (&v)[4]) {
+    if (W == 4) { const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+    else v[0] = *p;
+}
+template <int W>
+__device__ __forceinline__ void store_vec(float* p, const float (&v)[4]) {
+    if (W == 4) *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); else *p = v[0];
+}
 
 // -------------------------------------------------------------------------------- forward stats
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ x, int B, int C, int HW,
@@ -107,6 +126,14 @@ __global__ __launch_bounds__(256) void bn1d_partial_kernel(const float* __restri
     part[(size_t)c * 2] = s; part[(size_t)c * 2 + 1] = q;
 }
 
+// what a BatchNorm call leaves per channel: batch statistics for the backward, running statistics updated
+__device__ __forceinline__ void write_stats(int c, float mean, float invstd, double var, double n, float momentum,
+                                            float* __restrict__ mo, float* __restrict__ io, float* __restrict__ rmean,
+                                            float* __restrict__ rvar) {
+    mo[c] = mean; io[c] = invstd;
+    bn_running_update(rmean, rvar, c, mean, var, n, momentum);
+}
+
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ part, int C, int YS, double n,
                                                           float eps, float momentum, float* __restrict__ mean,
                                                           float* __restrict__ invstd, float* __restrict__ rmean,
@@ -115,15 +142,10 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restri
     if (c >= C) return;
     double s = 0, q = 0;
     for (int y = 0; y < YS; ++y) { s += part[((size_t)c * YS + y) * 2]; q += part[((size_t)c * YS + y) * 2 + 1]; }
-    const double m = s / n;
-    double var = q / n - m * m; if (var < 0) var = 0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)m;
-    if (rvar) {
-        const double unb = n > 1 ? var * n / (n - 1.0) : var;
-        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
-    }
+    float mu, is;
+    double var;
+    bn_stats_of(s, q, n, eps, mu, is, var);
+    write_stats(c, mu, is, var, n, momentum, mean, invstd, rmean, rvar);
 }
 
 // Deferred running-statistics update of a BatchNorm call that ran with running_mean / running_var = NULL: from the batch
@@ -136,16 +158,35 @@ __global__ __launch_bounds__(256) void bn_running_update_kernel(const float* __r
                                                                 float eps, float momentum) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean[c];
+    if (rmean) rmean[c] = bn_running_mix(rmean[c], mean[c], momentum);
     if (rvar) {
         const double is = (double)invstd[c];
         double var = 1.0 / (is * is) - (double)eps; if (var < 0) var = 0;
-        const double unb = n > 1 ? var * n / (n - 1.0) : var;
-        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
+        rvar[c] = bn_running_mix(rvar[c], (float)bn_unbiased(var, n), momentum);
     }
 }
 
 // -------------------------------------------------------------------------------- forward apply
+// W values of one (image, channel) plane at offset i: y = act(bn(x)) (+ res).  px / pg: the plane of channel c and of its GLU
+// gate channel c + Cy; pr: the residual's plane or NULL
+template <int ACT, int W>
+__device__ __forceinline__ void bn_fwd_vec(const float* __restrict__ px, const float* __restrict__ pg,
+                                           const float* __restrict__ pr, float* __restrict__ py, int i, const BnCoef& ca,
+                                           const BnCoef& cg, float slope) {
+    float v[4], g[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
+    load_vec<W>(px + i, v);
+    if (ACT == MOGAN_ACT_GLU) load_vec<W>(pg + i, g);
+#pragma unroll
+    for (int k = 0; k < W; ++k) o[k] = bn_fwd_elem<ACT>(v[k], g[k], ca, cg, slope);
+    if (pr) {
+        float r[4];
+        load_vec<W>(pr + i, r);
+#pragma unroll
+        for (int k = 0; k < W; ++k) o[k] += r[k];
+    }
+    store_vec<W>(py + i, o);
+}
+
 template <int ACT, bool VEC>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                          const float* __restrict__ invstd,
@@ -153,61 +194,18 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict
                                                          const float* __restrict__ res, float* __restrict__ y, int C,
                                                          int HW, float slope) {
     constexpr int W = VEC ? 4 : 1;
-    constexpr int WA = 4;
     const int Cy = (ACT == MOGAN_ACT_GLU) ? C / 2 : C;
     const int c = blockIdx.y % Cy, b = blockIdx.y / Cy;
     const int i = (blockIdx.x * 256 + threadIdx.x) * W;
     if (i >= HW) return;
-    const float sc = gamma[c] * invstd[c], sh = beta[c] - mean[c] * sc;
-    const float* px = x + ((size_t)b * C + c) * HW + i;
-    float v[WA], o[WA];
-    if (VEC) { const float4 t = *(const float4*)px; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    else v[0] = *px;
-    if (ACT == MOGAN_ACT_GLU) {
-        const int cg = c + Cy;
-        const float sc2 = gamma[cg] * invstd[cg], sh2 = beta[cg] - mean[cg] * sc2;
-        float g[WA];
-        if (VEC) { const float4 t = *(const float4*)(px + (size_t)Cy * HW); g[0] = t.x; g[1] = t.y; g[2] = t.z; g[3] = t.w; }
-        else g[0] = px[(size_t)Cy * HW];
-#pragma unroll
-        for (int k = 0; k < W; ++k) o[k] = (v[k] * sc + sh) * sigmoidf_(g[k] * sc2 + sh2);
-    } else {
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            float t = v[k] * sc + sh;
-            if (ACT == MOGAN_ACT_RELU) t = t > 0.f ? t : 0.f;
-            if (ACT == MOGAN_ACT_LRELU) t = t > 0.f ? t : t * slope;
-            o[k] = t;
-        }
-    }
-    float* py = y + ((size_t)b * Cy + c) * HW + i;
-    if (res) {
-        const float* pr = res + ((size_t)b * Cy + c) * HW + i;
-        if (VEC) { const float4 t = *(const float4*)pr; o[0] += t.x; o[1] += t.y; o[2] += t.z; o[3] += t.w; }
-        else o[0] += *pr;
-    }
-    if (VEC) *(float4*)py = make_float4(o[0], o[1], o[2], o[3]); else *py = o[0];
+    BnCoef ca, cg;
+    bn_coef_pair<ACT>(mean, invstd, gamma, beta, c, Cy, ca, cg);
+    const float* px = x + ((size_t)b * C + c) * HW;
+    bn_fwd_vec<ACT, W>(px, px + (size_t)Cy * HW, res ? res + ((size_t)b * Cy + c) * HW : nullptr,
+                       y + ((size_t)b * Cy + c) * HW, i, ca, cg, slope);
 }
 
 // -------------------------------------------------------------------------------- backward
-// dy_bn (gradient at the BN output) from dy (gradient at the activation output), recomputing the BN output.
-// Non-GLU: channel c.  GLU: pair (c, c+Cy): a = bn_c, g = bn_{c+Cy}; y = a*sig(g).
-template <int ACT>
-__device__ __forceinline__ void act_bwd(float xa, float xg, float dyv, float sc, float sh, float sc2, float sh2,
-                                        float slope, float& da, float& dg, float& xha_scaled_dummy) {
-    (void)xha_scaled_dummy;
-    if (ACT == MOGAN_ACT_GLU) {
-        const float a = xa * sc + sh, s = sigmoidf_(xg * sc2 + sh2);
-        da = dyv * s; dg = dyv * a * s * (1.f - s);
-    } else {
-        const float t = xa * sc + sh;
-        if (ACT == MOGAN_ACT_RELU) da = t > 0.f ? dyv : 0.f;
-        else if (ACT == MOGAN_ACT_LRELU) da = t > 0.f ? dyv : dyv * slope;
-        else da = dyv;
-        dg = 0.f;
-    }
-}
-
 // partial sums per (channel, ys): [sum dy_a, sum dy_a*xhat_a, sum dy_g, sum dy_g*xhat_g]
 template <int ACT>
 __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ dy,
@@ -222,40 +220,25 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
     const int bi = ys / sp.hs, hi = ys % sp.hs;
     const int b0 = bi * sp.bper, b1 = min(B, b0 + sp.bper);
     const int h0 = hi * sp.hper, h1 = min(HW, h0 + sp.hper);
-    const float mu = mean[c], is = invstd[c];
-    const float sc = gamma[c] * is, sh = beta[c] - mu * sc;
-    float mu2 = 0, is2 = 0, sc2 = 0, sh2 = 0;
-    if (ACT == MOGAN_ACT_GLU) { mu2 = mean[c + Cy]; is2 = invstd[c + Cy]; sc2 = gamma[c + Cy] * is2; sh2 = beta[c + Cy] - mu2 * sc2; }
+    BnCoef ca, cg;
+    bn_coef_pair<ACT>(mean, invstd, gamma, beta, c, Cy, ca, cg);
     double acc[4] = {0, 0, 0, 0};
-    float dummy = 0;
     for (int b = b0; b < b1; ++b) {
         const float* pxa = x + ((size_t)b * C + c) * HW;
         const float* pxg = pxa + (size_t)Cy * HW;
         const float* pdy = dy + ((size_t)b * Cy + c) * HW;
         if ((HW & 3) == 0) {                       // (h0, h1 are multiples of 4 then: Split::hper is)
             for (int i = h0 + threadIdx.x * 4; i < h1; i += 1024) {
-                const float4 xa4 = *(const float4*)(pxa + i), dy4 = *(const float4*)(pdy + i);
-                float4 xg4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (ACT == MOGAN_ACT_GLU) xg4 = *(const float4*)(pxg + i);
-                const float xa_[4] = {xa4.x, xa4.y, xa4.z, xa4.w}, xg_[4] = {xg4.x, xg4.y, xg4.z, xg4.w};
-                const float dy_[4] = {dy4.x, dy4.y, dy4.z, dy4.w};
+                float xa[4], xg[4] = {0.f, 0.f, 0.f, 0.f}, d[4];
+                load_vec<4>(pxa + i, xa); load_vec<4>(pdy + i, d);
+                if (ACT == MOGAN_ACT_GLU) load_vec<4>(pxg + i, xg);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float da, dg;
-                    act_bwd<ACT>(xa_[k], xg_[k], dy_[k], sc, sh, sc2, sh2, slope, da, dg, dummy);
-                    acc[0] += da; acc[1] += (double)da * ((xa_[k] - mu) * is);
-                    if (ACT == MOGAN_ACT_GLU) { acc[2] += dg; acc[3] += (double)dg * ((xg_[k] - mu2) * is2); }
-                }
+                for (int k = 0; k < 4; ++k) bn_bwd_accum<ACT>(acc, xa[k], xg[k], d[k], ca, cg, slope);
             }
             continue;
         }
-        for (int i = h0 + threadIdx.x; i < h1; i += 256) {
-            const float xa = pxa[i], xg = (ACT == MOGAN_ACT_GLU) ? pxg[i] : 0.f;
-            float da, dg;
-            act_bwd<ACT>(xa, xg, pdy[i], sc, sh, sc2, sh2, slope, da, dg, dummy);
-            acc[0] += da; acc[1] += (double)da * ((xa - mu) * is);
-            if (ACT == MOGAN_ACT_GLU) { acc[2] += dg; acc[3] += (double)dg * ((xg - mu2) * is2); }
-        }
+        for (int i = h0 + threadIdx.x; i < h1; i += 256)
+            bn_bwd_accum<ACT>(acc, pxa[i], (ACT == MOGAN_ACT_GLU) ? pxg[i] : 0.f, pdy[i], ca, cg, slope);
     }
     block_sum<4>(acc, sh_);
     if (threadIdx.x == 0) {
@@ -277,17 +260,14 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* __re
 #pragma unroll
         for (int k = 0; k < 4; ++k) a[k] += part[((size_t)c * YS + y) * 4 + k];
     sums[c * 2] = (float)a[0]; sums[c * 2 + 1] = (float)a[1];
-    if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)a[0];
-    if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)a[1];
+    bn_write_dparam(dgamma, dbeta, c, (float)a[0], (float)a[1], accumulate);
     if (ACT == MOGAN_ACT_GLU) {
         const int cg = c + Cy;
         sums[cg * 2] = (float)a[2]; sums[cg * 2 + 1] = (float)a[3];
-        if (dbeta) dbeta[cg] = (accumulate ? dbeta[cg] : 0.f) + (float)a[2];
-        if (dgamma) dgamma[cg] = (accumulate ? dgamma[cg] : 0.f) + (float)a[3];
+        bn_write_dparam(dgamma, dbeta, cg, (float)a[2], (float)a[3], accumulate);
     }
 }
 
-// dx = gamma*invstd * (dy_bn - sum_dy/n - xhat * sum_dyxhat/n)
 template <int ACT>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                            const float* __restrict__ mean,
@@ -297,22 +277,19 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ sums, float* __restrict__ dx, int C,
                                                            int HW, float slope, float inv_n) {
     const int Cy = (ACT == MOGAN_ACT_GLU) ? C / 2 : C;
-    const int c = blockIdx.y % Cy, b = blockIdx.y / Cy;
+    const int c = blockIdx.y % Cy, b = blockIdx.y / Cy, cgl = c + Cy;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= HW) return;
-    const float mu = mean[c], is = invstd[c];
-    const float sc = gamma[c] * is, sh = beta[c] - mu * sc;
-    float mu2 = 0, is2 = 0, sc2 = 0, sh2 = 0;
-    if (ACT == MOGAN_ACT_GLU) { mu2 = mean[c + Cy]; is2 = invstd[c + Cy]; sc2 = gamma[c + Cy] * is2; sh2 = beta[c + Cy] - mu2 * sc2; }
+    BnCoef ca, cg;
+    bn_coef_pair<ACT>(mean, invstd, gamma, beta, c, Cy, ca, cg);
     const size_t ia = ((size_t)b * C + c) * HW + i, ig = ia + (size_t)Cy * HW;
     const float xa = x[ia], xg = (ACT == MOGAN_ACT_GLU) ? x[ig] : 0.f;
-    float da, dg, dummy = 0;
-    act_bwd<ACT>(xa, xg, dy[((size_t)b * Cy + c) * HW + i], sc, sh, sc2, sh2, slope, da, dg, dummy);
-    dx[ia] = sc * (da - sums[c * 2] * inv_n - (xa - mu) * is * sums[c * 2 + 1] * inv_n);
-    if (ACT == MOGAN_ACT_GLU) {
-        const int cg = c + Cy;
-        dx[ig] = sc2 * (dg - sums[cg * 2] * inv_n - (xg - mu2) * is2 * sums[cg * 2 + 1] * inv_n);
-    }
+    float s[4] = {sums[c * 2], sums[c * 2 + 1], 0.f, 0.f};
+    if (ACT == MOGAN_ACT_GLU) { s[2] = sums[cgl * 2]; s[3] = sums[cgl * 2 + 1]; }
+    float oa, og;
+    bn_bwd_elem<ACT>(xa, xg, dy[((size_t)b * Cy + c) * HW + i], ca, cg, slope, s, inv_n, oa, og);
+    dx[ia] = oa;
+    if (ACT == MOGAN_ACT_GLU) dx[ig] = og;
 }
 
 
@@ -338,23 +315,21 @@ __device__ __forceinline__ void part_sums(const double* __restrict__ part, int c
 #pragma unroll
     for (int k = 0; k < NV; ++k) a[k] = wave_allsum(a[k]);
 }
-__device__ __forceinline__ void stats_of(const double (&a)[2], double n, float eps, float& mean, float& invstd, double& var) {
-    const double m = a[0] / n;
-    var = a[1] / n - m * m; if (var < 0) var = 0;
-    mean = (float)m; invstd = (float)(1.0 / sqrt(var + (double)eps));
-}
-__device__ __forceinline__ void write_stats(int c, float mean, float invstd, double var, double n, float momentum,
-                                            float* __restrict__ mo, float* __restrict__ io, float* __restrict__ rmean,
-                                            float* __restrict__ rvar) {
-    mo[c] = mean; io[c] = invstd;
-    if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-    if (rvar) {
-        const double unb = n > 1 ? var * n / (n - 1.0) : var;
-        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
-    }
-}
 
 constexpr int FUSED_PER = 4096;     // values of one plane per block
+
+// channel c's statistics from its partial sums; the writer thread leaves them as bn_finalize_kernel would
+__device__ __forceinline__ BnCoef fused_coef(const double* __restrict__ part, int c, int YS, double n, float eps, float momentum,
+                                             const float* __restrict__ gamma, const float* __restrict__ beta, bool wr,
+                                             float* __restrict__ mean_o, float* __restrict__ invstd_o, float* __restrict__ rmean,
+                                             float* __restrict__ rvar) {
+    double a[2], var;
+    float mu, is;
+    part_sums<2, 2>(part, c, YS, a);
+    bn_stats_of(a[0], a[1], n, eps, mu, is, var);
+    if (wr) write_stats(c, mu, is, var, n, momentum, mean_o, invstd_o, rmean, rvar);
+    return bn_coef(mu, is, gamma, beta, c);
+}
 
 template <int ACT>
 __global__ __launch_bounds__(256) void bn_fwd_apply_fused_kernel(const float* __restrict__ x, const double* __restrict__ part,
@@ -367,45 +342,15 @@ __global__ __launch_bounds__(256) void bn_fwd_apply_fused_kernel(const float* __
     const int Cy = (ACT == MOGAN_ACT_GLU) ? C / 2 : C;
     const int c = blockIdx.y % Cy, b = blockIdx.y / Cy;
     const bool wr = writer && blockIdx.x == 0 && b == 0 && threadIdx.x == 0;
-    double a[2], var;
-    float mu, is, mu2 = 0.f, is2 = 0.f;
-    part_sums<2, 2>(part, c, YS, a);
-    stats_of(a, n, eps, mu, is, var);
-    if (wr) write_stats(c, mu, is, var, n, momentum, mean_o, invstd_o, rmean, rvar);
-    const float sc = gamma[c] * is, sh = beta[c] - mu * sc;
-    float sc2 = 0.f, sh2 = 0.f;
-    if (ACT == MOGAN_ACT_GLU) {
-        const int cg = c + Cy;
-        part_sums<2, 2>(part, cg, YS, a);
-        stats_of(a, n, eps, mu2, is2, var);
-        if (wr) write_stats(cg, mu2, is2, var, n, momentum, mean_o, invstd_o, rmean, rvar);
-        sc2 = gamma[cg] * is2; sh2 = beta[cg] - mu2 * sc2;
-    }
+    const BnCoef ca = fused_coef(part, c, YS, n, eps, momentum, gamma, beta, wr, mean_o, invstd_o, rmean, rvar);
+    BnCoef cg = {0.f, 0.f, 0.f, 0.f};
+    if (ACT == MOGAN_ACT_GLU) cg = fused_coef(part, c + Cy, YS, n, eps, momentum, gamma, beta, wr, mean_o, invstd_o, rmean, rvar);
     const float* px = x + ((size_t)b * C + c) * HW;
     float* py = y + ((size_t)b * Cy + c) * HW;
     const float* pr = res ? res + ((size_t)b * Cy + c) * HW : nullptr;
     const int i0 = blockIdx.x * FUSED_PER, i1 = min(HW, i0 + FUSED_PER);
-    for (int i = i0 + threadIdx.x * 4; i < i1; i += 1024) {
-        const float4 t = *(const float4*)(px + i);
-        const float v[4] = {t.x, t.y, t.z, t.w};
-        float o[4];
-        if (ACT == MOGAN_ACT_GLU) {
-            const float4 u = *(const float4*)(px + (size_t)Cy * HW + i);
-            const float g[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = (v[k] * sc + sh) * sigmoidf_(g[k] * sc2 + sh2);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float w = v[k] * sc + sh;
-                if (ACT == MOGAN_ACT_RELU) w = w > 0.f ? w : 0.f;
-                if (ACT == MOGAN_ACT_LRELU) w = w > 0.f ? w : w * slope;
-                o[k] = w;
-            }
-        }
-        if (pr) { const float4 r = *(const float4*)(pr + i); o[0] += r.x; o[1] += r.y; o[2] += r.z; o[3] += r.w; }
-        *(float4*)(py + i) = make_float4(o[0], o[1], o[2], o[3]);
-    }
+    for (int i = i0 + threadIdx.x * 4; i < i1; i += 1024)
+        bn_fwd_vec<ACT, 4>(px, px + (size_t)Cy * HW, pr, py, i, ca, cg, slope);
 }
 
 template <int ACT>
@@ -417,46 +362,31 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fused_kernel(const float* __
                                                                  int YS, float slope, float inv_n, int accumulate, int writer) {
     constexpr int NV = (ACT == MOGAN_ACT_GLU) ? 4 : 2;
     const int Cy = (ACT == MOGAN_ACT_GLU) ? C / 2 : C;
-    const int c = blockIdx.y % Cy, b = blockIdx.y / Cy, cg = c + Cy;
+    const int c = blockIdx.y % Cy, b = blockIdx.y / Cy;
     double a[NV];
     part_sums<NV, 4>(part, c, YS, a);
-    const float s0 = (float)a[0], s1 = (float)a[1];
-    float s2 = 0.f, s3 = 0.f;
-    if (ACT == MOGAN_ACT_GLU) { s2 = (float)a[NV - 2]; s3 = (float)a[NV - 1]; }
+    float s[4] = {(float)a[0], (float)a[1], 0.f, 0.f};
+    if (ACT == MOGAN_ACT_GLU) { s[2] = (float)a[NV - 2]; s[3] = (float)a[NV - 1]; }
     if (writer && blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
-        if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + s0;
-        if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + s1;
-        if (ACT == MOGAN_ACT_GLU) {
-            if (dbeta) dbeta[cg] = (accumulate ? dbeta[cg] : 0.f) + s2;
-            if (dgamma) dgamma[cg] = (accumulate ? dgamma[cg] : 0.f) + s3;
-        }
+        bn_write_dparam(dgamma, dbeta, c, s[0], s[1], accumulate);
+        if (ACT == MOGAN_ACT_GLU) bn_write_dparam(dgamma, dbeta, c + Cy, s[2], s[3], accumulate);
     }
-    const float mu = mean[c], is = invstd[c];
-    const float sc = gamma[c] * is, sh = beta[c] - mu * sc;
-    float mu2 = 0, is2 = 0, sc2 = 0, sh2 = 0;
-    if (ACT == MOGAN_ACT_GLU) { mu2 = mean[cg]; is2 = invstd[cg]; sc2 = gamma[cg] * is2; sh2 = beta[cg] - mu2 * sc2; }
+    BnCoef ca, cg;
+    bn_coef_pair<ACT>(mean, invstd, gamma, beta, c, Cy, ca, cg);
     const float* pxa = x + ((size_t)b * C + c) * HW;
     const float* pxg = pxa + (size_t)Cy * HW;
     const float* pdy = dy + ((size_t)b * Cy + c) * HW;
     float* pda = dx + ((size_t)b * C + c) * HW;
     float* pdg = pda + (size_t)Cy * HW;
     const int i0 = blockIdx.x * FUSED_PER, i1 = min(HW, i0 + FUSED_PER);
-    float dummy = 0;
     for (int i = i0 + threadIdx.x * 4; i < i1; i += 1024) {
-        const float4 xa4 = *(const float4*)(pxa + i), dy4 = *(const float4*)(pdy + i);
-        float4 xg4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ACT == MOGAN_ACT_GLU) xg4 = *(const float4*)(pxg + i);
-        const float xa_[4] = {xa4.x, xa4.y, xa4.z, xa4.w}, xg_[4] = {xg4.x, xg4.y, xg4.z, xg4.w}, dy_[4] = {dy4.x, dy4.y, dy4.z, dy4.w};
-        float oa[4], og[4];
+        float xa[4], xg[4] = {0.f, 0.f, 0.f, 0.f}, d[4], oa[4], og[4];
+        load_vec<4>(pxa + i, xa); load_vec<4>(pdy + i, d);
+        if (ACT == MOGAN_ACT_GLU) load_vec<4>(pxg + i, xg);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float da, dg;
-            act_bwd<ACT>(xa_[k], xg_[k], dy_[k], sc, sh, sc2, sh2, slope, da, dg, dummy);
-            oa[k] = sc * (da - s0 * inv_n - (xa_[k] - mu) * is * s1 * inv_n);
-            og[k] = (ACT == MOGAN_ACT_GLU) ? sc2 * (dg - s2 * inv_n - (xg_[k] - mu2) * is2 * s3 * inv_n) : 0.f;
-        }
-        *(float4*)(pda + i) = make_float4(oa[0], oa[1], oa[2], oa[3]);
-        if (ACT == MOGAN_ACT_GLU) *(float4*)(pdg + i) = make_float4(og[0], og[1], og[2], og[3]);
+        for (int k = 0; k < 4; ++k) bn_bwd_elem<ACT>(xa[k], xg[k], d[k], ca, cg, slope, s, inv_n, oa[k], og[k]);
+        store_vec<4>(pda + i, oa);
+        if (ACT == MOGAN_ACT_GLU) store_vec<4>(pdg + i, og);
     }
 }
 
@@ -464,8 +394,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fused_kernel(const float* __
 // -------------------------------------------------------------------------------- one-launch BatchNorm for small maps
 // B*HW <= SMALL_NE values per channel (<= 16x16 maps at B = 16; BatchNorm1d): ONE block per output channel (GLU: per pair)
 // does what bn_partial + bn_finalize + bn_act_fwd (and bn_bwd_partial + finalize + apply) do in three launches -- pass 1
-// reduces over the channel, pass 2 re-reads the L2-resident values and applies.  Same arithmetic (fp64 sums, float apply).
+// reduces over the channel, pass 2 applies to the values it kept.  Same arithmetic (fp64 sums, float apply).
 constexpr int SMALL_NE = 4096;
+constexpr int SMALL_EPT = SMALL_NE / 256;            // values per thread (and channel of a GLU pair)
+constexpr unsigned SMALL_NONE = 0xFFFFFFFFu;         // offset of a slot beyond the channel's B*HW values
 
 template <int ACT>
 __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -483,17 +415,16 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* __restri
     // running statistics are updated group after group, as G calls would), one launch (the object pathways)
     for (int grp = 0; grp < G; ++grp, x += (size_t)B * C * HW, y += (size_t)B * Cy * HW, mean += C, invstd += C) {
     if (grp) __syncthreads();
+    float v[NCH][SMALL_EPT];
+    unsigned off[SMALL_EPT];
     // a thread's <= 16 values (x2 for GLU) are loaded ONCE, all loads in flight (clamped addresses, no branch), and stay in registers
     // for the apply pass (a `for (e ...)` loop with one dependent load per iteration made this kernel 13-16 us for 4096 values)
-    constexpr int EPT = SMALL_NE / 256;
-    float v[NCH][EPT];
-    unsigned off[EPT];
 #pragma unroll
-    for (int i = 0; i < EPT; ++i) {
+    for (int i = 0; i < SMALL_EPT; ++i) {
         const int e = threadIdx.x + 256 * i;
         const bool ok = e < NE;
         const int b = e / HW, pos = e - b * HW;
-        off[i] = ok ? (unsigned)((b * C + c) * HW + pos) : 0xFFFFFFFFu;
+        off[i] = ok ? (unsigned)((b * C + c) * HW + pos) : SMALL_NONE;
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
             const float t = x[ok ? (size_t)off[i] + (size_t)k * Cy * HW : 0];
@@ -504,7 +435,7 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < 2 * NCH; ++k) acc[k] = 0.0;
 #pragma unroll
-    for (int i = 0; i < EPT; ++i)
+    for (int i = 0; i < SMALL_EPT; ++i)
 #pragma unroll
         for (int k = 0; k < NCH; ++k) { const double t = v[k][i]; acc[2 * k] += t; acc[2 * k + 1] += t * t; }
     block_sum<2 * NCH>(acc, sh);
@@ -512,33 +443,24 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* __restri
         const double n = (double)NE;
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
-            const int ch = c + k * Cy;
-            const double m = acc[2 * k] / n;
-            double var = acc[2 * k + 1] / n - m * m; if (var < 0) var = 0;
-            const float mu = (float)m, is = (float)(1.0 / sqrt(var + (double)eps));
-            mean[ch] = mu; invstd[ch] = is;
-            if (rmean) rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * mu;
-            if (rvar) {
-                const double unb = n > 1 ? var * n / (n - 1.0) : var;
-                rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unb;
-            }
+            float mu, is;
+            double var;
+            bn_stats_of(acc[2 * k], acc[2 * k + 1], n, eps, mu, is, var);
+            write_stats(c + k * Cy, mu, is, var, n, momentum, mean, invstd, rmean, rvar);
             st[2 * k] = mu; st[2 * k + 1] = is;
         }
     }
     __syncthreads();
-    const float sc = gamma[c] * st[1], shf = beta[c] - st[0] * sc;
-    float sc2 = 0.f, sh2 = 0.f;
-    if (ACT == MOGAN_ACT_GLU) { sc2 = gamma[c + Cy] * st[3]; sh2 = beta[c + Cy] - st[2] * sc2; }
+    const BnCoef ca = bn_coef(st[0], st[1], gamma, beta, c);
+    BnCoef cg = {0.f, 0.f, 0.f, 0.f};
+    if (ACT == MOGAN_ACT_GLU) cg = bn_coef(st[2], st[3], gamma, beta, c + Cy);
 #pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-        if (off[i] == 0xFFFFFFFFu) continue;
+    for (int i = 0; i < SMALL_EPT; ++i) {
+        if (off[i] == SMALL_NONE) continue;
         const int e = threadIdx.x + 256 * i;
         const int b = e / HW, pos = e - b * HW;
         const size_t iy = ((size_t)b * Cy + c) * HW + pos;
-        float t = v[0][i] * sc + shf;
-        if (ACT == MOGAN_ACT_GLU) t = t * sigmoidf_(v[NCH - 1][i] * sc2 + sh2);
-        if (ACT == MOGAN_ACT_RELU) t = t > 0.f ? t : 0.f;
-        if (ACT == MOGAN_ACT_LRELU) t = t > 0.f ? t : t * slope;
+        float t = bn_fwd_elem<ACT>(v[0][i], v[NCH - 1][i], ca, cg, slope);
         if (res) t += res[iy];
         y[iy] = t;
     }
@@ -559,22 +481,19 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
     for (int grp = 0; grp < G; ++grp, x += (size_t)B * C * HW, dy += (size_t)B * Cy * HW, dx += (size_t)B * C * HW, mean += C,
              invstd += C, accumulate = 1) {           // (d gamma / d beta: the groups' contributions add up)
     if (grp) __syncthreads();
-    const float mu = mean[c], is = invstd[c];
-    const float sc = gamma[c] * is, sh = beta[c] - mu * sc;
-    float mu2 = 0, is2 = 0, sc2 = 0, sh2 = 0;
-    if (ACT == MOGAN_ACT_GLU) { mu2 = mean[c + Cy]; is2 = invstd[c + Cy]; sc2 = gamma[c + Cy] * is2; sh2 = beta[c + Cy] - mu2 * sc2; }
+    BnCoef ca, cg;
+    bn_coef_pair<ACT>(mean, invstd, gamma, beta, c, Cy, ca, cg);
     double acc[4] = {0, 0, 0, 0};
-    float dummy = 0;
     // x (both halves for GLU) and dy of a thread's <= 16 elements: loaded once, all in flight, kept for the second pass
-    constexpr int EPT = SMALL_NE / 256, NCH = (ACT == MOGAN_ACT_GLU) ? 2 : 1;
-    float xv[NCH][EPT], dv[EPT];
-    unsigned off[EPT];
+    constexpr int NCH = (ACT == MOGAN_ACT_GLU) ? 2 : 1;
+    float xv[NCH][SMALL_EPT], dv[SMALL_EPT];
+    unsigned off[SMALL_EPT];
 #pragma unroll
-    for (int i = 0; i < EPT; ++i) {
+    for (int i = 0; i < SMALL_EPT; ++i) {
         const int e = threadIdx.x + 256 * i;
         const bool ok = e < NE;
         const int b = e / HW, pos = e - b * HW;
-        off[i] = ok ? (unsigned)((b * C + c) * HW + pos) : 0xFFFFFFFFu;
+        off[i] = ok ? (unsigned)((b * C + c) * HW + pos) : SMALL_NONE;
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
             const float t = x[ok ? (size_t)off[i] + (size_t)k * Cy * HW : 0];
@@ -584,43 +503,30 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
         dv[i] = ok ? t : 0.f;
     }
 #pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-        if (off[i] == 0xFFFFFFFFu) continue;
-        const float xa = xv[0][i], xg = xv[NCH - 1][i];
-        float da, dg;
-        act_bwd<ACT>(xa, xg, dv[i], sc, sh, sc2, sh2, slope, da, dg, dummy);
-        acc[0] += da; acc[1] += (double)da * ((xa - mu) * is);
-        if (ACT == MOGAN_ACT_GLU) { acc[2] += dg; acc[3] += (double)dg * ((xg - mu2) * is2); }
+    for (int i = 0; i < SMALL_EPT; ++i) {
+        if (off[i] == SMALL_NONE) continue;
+        bn_bwd_accum<ACT>(acc, xv[0][i], xv[NCH - 1][i], dv[i], ca, cg, slope);
     }
     block_sum<4>(acc, sh_);
     if (threadIdx.x == 0) {
         sums[0] = (float)acc[0]; sums[1] = (float)acc[1]; sums[2] = (float)acc[2]; sums[3] = (float)acc[3];
-        if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + sums[0];
-        if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + sums[1];
-        if (ACT == MOGAN_ACT_GLU) {
-            if (dbeta) dbeta[c + Cy] = (accumulate ? dbeta[c + Cy] : 0.f) + sums[2];
-            if (dgamma) dgamma[c + Cy] = (accumulate ? dgamma[c + Cy] : 0.f) + sums[3];
-        }
+        bn_write_dparam(dgamma, dbeta, c, sums[0], sums[1], accumulate);
+        if (ACT == MOGAN_ACT_GLU) bn_write_dparam(dgamma, dbeta, c + Cy, sums[2], sums[3], accumulate);
     }
     __syncthreads();
     const float inv_n = 1.f / ((float)B * (float)HW);
+    const float s[4] = {sums[0], sums[1], sums[2], sums[3]};
 #pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-        if (off[i] == 0xFFFFFFFFu) continue;
+    for (int i = 0; i < SMALL_EPT; ++i) {
+        if (off[i] == SMALL_NONE) continue;
         const size_t ia = off[i], ig = ia + (size_t)Cy * HW;
-        const float xa = xv[0][i], xg = xv[NCH - 1][i];
-        float da, dg;
-        act_bwd<ACT>(xa, xg, dv[i], sc, sh, sc2, sh2, slope, da, dg, dummy);
-        dx[ia] = sc * (da - sums[0] * inv_n - (xa - mu) * is * sums[1] * inv_n);
-        if (ACT == MOGAN_ACT_GLU) dx[ig] = sc2 * (dg - sums[2] * inv_n - (xg - mu2) * is2 * sums[3] * inv_n);
+        float oa, og;
+        bn_bwd_elem<ACT>(xv[0][i], xv[NCH - 1][i], dv[i], ca, cg, slope, s, inv_n, oa, og);
+        dx[ia] = oa;
+        if (ACT == MOGAN_ACT_GLU) dx[ig] = og;
     }
     }
 }
-
-// (BatchNorm1d, HW == 1, keeps its thread-per-channel kernels: a block per channel would be 16 values wide)
-static bool bn_fused_env() { return true; }
-static bool bn_fused_ok(int HW) { return (HW & 3) == 0 && HW >= 64 && bn_fused_env(); }
-static bool bn_small_ok(int B, int C, int HW) { return HW >= 16 && (long long)B * HW <= SMALL_NE && C <= 65535 * 2; }
 
 // -------------------------------------------------------------------------------- eval affine
 template <int ACT, bool BWD>
@@ -632,80 +538,83 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= HW) return;
     const size_t idx = (size_t)blockIdx.y * HW + i;
-    const float sc = scale[c], t = x[idx] * sc + shift[c];
+    const BnCoef k = {0.f, 0.f, scale[c], shift[c]};
     if (!BWD) {
-        float o = t;
-        if (ACT == MOGAN_ACT_RELU) o = t > 0.f ? t : 0.f;
-        if (ACT == MOGAN_ACT_LRELU) o = t > 0.f ? t : t * slope;
-        out[idx] = o;
+        out[idx] = bn_fwd_elem<ACT>(x[idx], 0.f, k, k, slope);
     } else {
-        float d = dy[idx];
-        if (ACT == MOGAN_ACT_RELU) d = t > 0.f ? d : 0.f;
-        if (ACT == MOGAN_ACT_LRELU) d = t > 0.f ? d : d * slope;
-        out[idx] = d * sc;
+        float d, dg;
+        act_bwd<ACT>(x[idx], 0.f, dy[idx], k, k, slope, d, dg);
+        out[idx] = d * k.sc;
     }
 }
 
+// -------------------------------------------------------------------------------- host side
 static inline int ok_launch() { return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH; }
 
-template <int ACT>
-static int bn_bwd_impl(const float* x, const float* dy, const float* mean, const float* invstd, const float* gamma,
-                       const float* beta, float* dx, float* dgamma, float* dbeta, int B, int C, int HW, float slope,
-                       int accumulate, void* ws, hipStream_t stream) {
-    const int Cy = ACT == MOGAN_ACT_GLU ? C / 2 : C;
-    if (bn_small_ok(B, C, HW)) {           // small map: one launch (bn_small_bwd_kernel)
-        hipLaunchKernelGGL((bn_small_bwd_kernel<ACT>), dim3(Cy), dim3(256), 0, stream, x, dy, mean, invstd, gamma, beta, dx,
-                           dgamma, dbeta, B, C, HW, slope, accumulate, 1);
-        return ok_launch();
+static bool bn_shape_ok(int B, int C, int HW, int act = MOGAN_ACT_NONE) {
+    return B > 0 && C > 0 && HW > 0 && !(act == MOGAN_ACT_GLU && (C & 1));
+}
+// path selection (BatchNorm1d, HW == 1, keeps its thread-per-channel kernels: a block per channel would be 16 values wide)
+static bool bn_fused_ok(int HW) { return (HW & 3) == 0 && HW >= 64; }
+static bool bn_small_ok(int B, int C, int HW) { return HW >= 16 && (long long)B * HW <= SMALL_NE && C <= 65535 * 2; }
+
+// f(std::integral_constant<int, ACT>) for the activation code `act`: the one place a kernel template meets the runtime code.
+// GLU_OK = false: the kernels of the caller have no GLU form
+template <bool GLU_OK = true, typename F>
+static int with_act(int act, F&& f) {
+    switch (act) {
+        case MOGAN_ACT_NONE: return f(std::integral_constant<int, MOGAN_ACT_NONE>{});
+        case MOGAN_ACT_RELU: return f(std::integral_constant<int, MOGAN_ACT_RELU>{});
+        case MOGAN_ACT_LRELU: return f(std::integral_constant<int, MOGAN_ACT_LRELU>{});
+        case MOGAN_ACT_GLU:
+            if constexpr (GLU_OK) return f(std::integral_constant<int, MOGAN_ACT_GLU>{});
+            return MOGAN_ERR_SHAPE;
+        default: return MOGAN_ERR_SHAPE;
     }
-    Split s = make_split(B, C, HW);
-    const int YS = s.bs * s.hs;
-    double* part = (double*)ws;
-    float* sums = (float*)((char*)ws + (size_t)C * YS * 4 * sizeof(double));
-    hipLaunchKernelGGL((bn_bwd_partial_kernel<ACT>), dim3(Cy, YS), dim3(256), 0, stream, x, dy, mean, invstd, gamma,
-                       beta, B, C, HW, s, slope, part);
-    const float inv_n = 1.f / ((float)B * (float)HW);
+}
+
+// the apply grids carry (image, channel) in gridDim.y <= 65535: f(b0, nb) for consecutive ranges of whole images
+template <typename F>
+static int for_batch_chunks(int B, int Cy, F&& f) {
     const int bchunk = 65535 / Cy;
     if (bchunk < 1) return MOGAN_ERR_SHAPE;
-    if (bn_fused_ok(HW)) {                 // finalize folded into the apply pass: two launches
-        for (int b0 = 0; b0 < B; b0 += bchunk) {
-            const int nb = B - b0 < bchunk ? B - b0 : bchunk;
-            hipLaunchKernelGGL((bn_bwd_apply_fused_kernel<ACT>), dim3((HW + FUSED_PER - 1) / FUSED_PER, nb * Cy), dim3(256), 0, stream,
-                               x + (size_t)b0 * C * HW, dy + (size_t)b0 * Cy * HW, mean, invstd, gamma, beta, (const double*)part,
-                               dx + (size_t)b0 * C * HW, dgamma, dbeta, C, HW, YS, slope, inv_n, accumulate, b0 == 0 ? 1 : 0);
-        }
-        return ok_launch();
-    }
-    hipLaunchKernelGGL((bn_bwd_finalize_kernel<ACT>), dim3((Cy + 255) / 256), dim3(256), 0, stream,
-                       (const double*)part, C, YS, sums, dgamma, dbeta, accumulate);
-    for (int b0 = 0; b0 < B; b0 += bchunk) {
-        const int nb = B - b0 < bchunk ? B - b0 : bchunk;
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<ACT>), dim3((HW + 255) / 256, nb * Cy), dim3(256), 0, stream,
-                           x + (size_t)b0 * C * HW, dy + (size_t)b0 * Cy * HW, mean, invstd, gamma, beta,
-                           (const float*)sums, dx + (size_t)b0 * C * HW, C, HW, slope, inv_n);
-    }
+    for (int b0 = 0; b0 < B; b0 += bchunk) f(b0, B - b0 < bchunk ? B - b0 : bchunk);
     return ok_launch();
+}
+
+// the one-launch path: G groups of B images (G == 1: one BatchNorm call)
+static int launch_small_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y, float* mean,
+                            float* invstd, float* running_mean, float* running_var, int B, int C, int HW, int act, float slope,
+                            float eps, float momentum, int G, hipStream_t stream) {
+    return with_act(act, [&](auto A) {
+        constexpr int ACT = decltype(A)::value;
+        hipLaunchKernelGGL((bn_small_fwd_kernel<ACT>), dim3(ACT == MOGAN_ACT_GLU ? C / 2 : C), dim3(256), 0, stream, x, gamma, beta,
+                           residual, y, mean, invstd, running_mean, running_var, B, C, HW, eps, momentum, slope, G);
+        return ok_launch();
+    });
+}
+static int launch_small_bwd(const float* x, const float* dy, const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, float* dx, float* dgamma, float* dbeta, int B, int C, int HW, int act, float slope,
+                            int accumulate, int G, hipStream_t stream) {
+    return with_act(act, [&](auto A) {
+        constexpr int ACT = decltype(A)::value;
+        hipLaunchKernelGGL((bn_small_bwd_kernel<ACT>), dim3(ACT == MOGAN_ACT_GLU ? C / 2 : C), dim3(256), 0, stream, x, dy, mean,
+                           invstd, gamma, beta, dx, dgamma, dbeta, B, C, HW, slope, accumulate, G);
+        return ok_launch();
+    });
 }
 
 template <bool BWD>
 static int affine_impl(const float* x, const float* dy, const float* scale, const float* shift, float* out, int B,
                        int C, int HW, int act, float slope, hipStream_t stream) {
-    if (B <= 0 || C <= 0 || HW <= 0) return MOGAN_ERR_SHAPE;
-    const int bchunk = 65535 / C;
-    if (bchunk < 1) return MOGAN_ERR_SHAPE;
-    for (int b0 = 0; b0 < B; b0 += bchunk) {
-        const int nb = B - b0 < bchunk ? B - b0 : bchunk;
-        dim3 grid((HW + 255) / 256, nb * C);
-        const size_t off = (size_t)b0 * C * HW;
-        const float* pdy = dy ? dy + off : nullptr;
-        switch (act) {
-            case MOGAN_ACT_NONE: hipLaunchKernelGGL((affine_act_kernel<MOGAN_ACT_NONE, BWD>), grid, dim3(256), 0, stream, x + off, pdy, scale, shift, out + off, C, HW, slope); break;
-            case MOGAN_ACT_RELU: hipLaunchKernelGGL((affine_act_kernel<MOGAN_ACT_RELU, BWD>), grid, dim3(256), 0, stream, x + off, pdy, scale, shift, out + off, C, HW, slope); break;
-            case MOGAN_ACT_LRELU: hipLaunchKernelGGL((affine_act_kernel<MOGAN_ACT_LRELU, BWD>), grid, dim3(256), 0, stream, x + off, pdy, scale, shift, out + off, C, HW, slope); break;
-            default: return MOGAN_ERR_SHAPE;
-        }
-    }
-    return ok_launch();
+    if (!bn_shape_ok(B, C, HW)) return MOGAN_ERR_SHAPE;
+    return with_act<false>(act, [&](auto A) {
+        return for_batch_chunks(B, C, [&](int b0, int nb) {
+            const size_t off = (size_t)b0 * C * HW;
+            hipLaunchKernelGGL((affine_act_kernel<decltype(A)::value, BWD>), dim3((HW + 255) / 256, nb * C), dim3(256), 0, stream,
+                               x + off, dy ? dy + off : nullptr, scale, shift, out + off, C, HW, slope);
+        });
+    });
 }
 
 }  // namespace
@@ -713,14 +622,14 @@ static int affine_impl(const float* x, const float* dy, const float* scale, cons
 extern "C" {
 
 size_t mogan_bn_ws_bytes(int B, int C, int HW) {
-    if (B <= 0 || C <= 0 || HW <= 0) return 0;
+    if (!bn_shape_ok(B, C, HW)) return 0;
     const Split s = make_split(B, C, HW);
     return (size_t)C * s.bs * s.hs * 4 * sizeof(double) + (size_t)C * 2 * sizeof(float) + 64;
 }
 
 int mogan_bn_stats(const float* x, int B, int C, int HW, float eps, float momentum, float* mean, float* invstd,
                    float* running_mean, float* running_var, void* ws, size_t ws_bytes, hipStream_t stream) {
-    if (B <= 0 || C <= 0 || HW <= 0) return MOGAN_ERR_SHAPE;
+    if (!bn_shape_ok(B, C, HW)) return MOGAN_ERR_SHAPE;
     if (!ws || ws_bytes < mogan_bn_ws_bytes(B, C, HW)) return MOGAN_ERR_WS;
     double* part = (double*)ws;
     int YS = 1;
@@ -745,56 +654,34 @@ int mogan_bn_running_update(const float* mean, const float* invstd, float* runni
     return ok_launch();
 }
 
-// statistics + apply in one call: small maps (B*HW <= 4096 values per channel) take ONE launch, larger ones the three of
-// mogan_bn_stats + mogan_bn_act_fwd.  mean / invstd are written for the backward as by mogan_bn_stats.
+// statistics + apply in one call, by the path the shape selects (file head).  mean / invstd are written for the backward as by
+// mogan_bn_stats.
 int mogan_bn_act_fwd_fused(const float* x, const float* gamma, const float* beta, const float* residual, float* running_mean,
                            float* running_var, float* mean, float* invstd, float* y, int B, int C, int HW, int act, float slope,
                            float eps, float momentum, void* ws, size_t ws_bytes, hipStream_t stream) {
-    if (B <= 0 || C <= 0 || HW <= 0 || (act == MOGAN_ACT_GLU && (C & 1))) return MOGAN_ERR_SHAPE;
+    if (!bn_shape_ok(B, C, HW, act)) return MOGAN_ERR_SHAPE;
     const int Cy = act == MOGAN_ACT_GLU ? C / 2 : C;
-    if (!bn_small_ok(B, C, HW) && bn_fused_ok(HW) && Cy <= 65535) {
-        if (!ws || ws_bytes < mogan_bn_ws_bytes(B, C, HW)) return MOGAN_ERR_WS;
-        const Split s = make_split(B, C, HW);
-        const int YS = s.bs * s.hs;
-        if (YS > 65535) return MOGAN_ERR_SHAPE;
-        double* part = (double*)ws;
-        hipLaunchKernelGGL(bn_partial_kernel, dim3(C, YS), dim3(256), 0, stream, x, B, C, HW, s, part);
-        const int bchunk = 65535 / Cy;
-        for (int b0 = 0; b0 < B; b0 += bchunk) {
-            const int nb = B - b0 < bchunk ? B - b0 : bchunk;
-            const dim3 grid((HW + FUSED_PER - 1) / FUSED_PER, nb * Cy);
-#define MOGAN_FUSED_CASE(A) case A: hipLaunchKernelGGL((bn_fwd_apply_fused_kernel<A>), grid, dim3(256), 0, stream,                 \
-                                                       x + (size_t)b0 * C * HW, (const double*)part, gamma, beta,                     \
-                                                       residual ? residual + (size_t)b0 * Cy * HW : nullptr, y + (size_t)b0 * Cy * HW, \
-                                                       mean, invstd, running_mean, running_var, C, HW, YS, (double)B * HW, eps,      \
-                                                       momentum, slope, b0 == 0 ? 1 : 0); break;
-            switch (act) {
-                MOGAN_FUSED_CASE(MOGAN_ACT_NONE)
-                MOGAN_FUSED_CASE(MOGAN_ACT_RELU)
-                MOGAN_FUSED_CASE(MOGAN_ACT_LRELU)
-                MOGAN_FUSED_CASE(MOGAN_ACT_GLU)
-                default: return MOGAN_ERR_SHAPE;
-            }
-#undef MOGAN_FUSED_CASE
-        }
-        return ok_launch();
-    }
-    if (!bn_small_ok(B, C, HW)) {
+    if (bn_small_ok(B, C, HW))
+        return launch_small_fwd(x, gamma, beta, residual, y, mean, invstd, running_mean, running_var, B, C, HW, act, slope, eps,
+                                momentum, 1, stream);
+    if (!bn_fused_ok(HW) || Cy > 65535) {
         int rc = mogan_bn_stats(x, B, C, HW, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes, stream);
         return rc ? rc : mogan_bn_act_fwd(x, mean, invstd, gamma, beta, residual, y, B, C, HW, act, slope, stream);
     }
-#define MOGAN_SMALL_CASE(A) case A: hipLaunchKernelGGL((bn_small_fwd_kernel<A>), dim3(Cy), dim3(256), 0, stream, x, gamma, beta, \
-                                                       residual, y, mean, invstd, running_mean, running_var, B, C, HW, eps,   \
-                                                       momentum, slope, 1); break;
-    switch (act) {
-        MOGAN_SMALL_CASE(MOGAN_ACT_NONE)
-        MOGAN_SMALL_CASE(MOGAN_ACT_RELU)
-        MOGAN_SMALL_CASE(MOGAN_ACT_LRELU)
-        MOGAN_SMALL_CASE(MOGAN_ACT_GLU)
-        default: return MOGAN_ERR_SHAPE;
-    }
-#undef MOGAN_SMALL_CASE
-    return ok_launch();
+    if (!ws || ws_bytes < mogan_bn_ws_bytes(B, C, HW)) return MOGAN_ERR_WS;
+    const Split s = make_split(B, C, HW);
+    const int YS = s.bs * s.hs;
+    if (YS > 65535) return MOGAN_ERR_SHAPE;
+    double* part = (double*)ws;
+    hipLaunchKernelGGL(bn_partial_kernel, dim3(C, YS), dim3(256), 0, stream, x, B, C, HW, s, part);
+    return with_act(act, [&](auto A) {
+        return for_batch_chunks(B, Cy, [&](int b0, int nb) {
+            hipLaunchKernelGGL((bn_fwd_apply_fused_kernel<decltype(A)::value>), dim3((HW + FUSED_PER - 1) / FUSED_PER, nb * Cy),
+                               dim3(256), 0, stream, x + (size_t)b0 * C * HW, (const double*)part, gamma, beta,
+                               residual ? residual + (size_t)b0 * Cy * HW : nullptr, y + (size_t)b0 * Cy * HW, mean, invstd,
+                               running_mean, running_var, C, HW, YS, (double)B * HW, eps, momentum, slope, b0 == 0 ? 1 : 0);
+        });
+    });
 }
 
 // G BatchNorm(train) + activation calls on the G groups of B images of one (G*B, C, HW) tensor in ONE launch each way: group g is
@@ -808,94 +695,72 @@ int mogan_bn_act_grouped_eligible(int G, int B, int C, int HW) {
 int mogan_bn_act_grouped_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* mean,
                              float* invstd, float* y, int G, int B, int C, int HW, int act, float slope, float eps, float momentum,
                              hipStream_t stream) {
-    if (!mogan_bn_act_grouped_eligible(G, B, C, HW) || (act == MOGAN_ACT_GLU && (C & 1))) return MOGAN_ERR_SHAPE;
-    const int Cy = act == MOGAN_ACT_GLU ? C / 2 : C;
-#define MOGAN_GRP_CASE(A) case A: hipLaunchKernelGGL((bn_small_fwd_kernel<A>), dim3(Cy), dim3(256), 0, stream, x, gamma, beta, \
-                                                     (const float*)nullptr, y, mean, invstd, running_mean, running_var, B, C, HW, eps, \
-                                                     momentum, slope, G); break;
-    switch (act) {
-        MOGAN_GRP_CASE(MOGAN_ACT_NONE)
-        MOGAN_GRP_CASE(MOGAN_ACT_RELU)
-        MOGAN_GRP_CASE(MOGAN_ACT_LRELU)
-        MOGAN_GRP_CASE(MOGAN_ACT_GLU)
-        default: return MOGAN_ERR_SHAPE;
-    }
-#undef MOGAN_GRP_CASE
-    return ok_launch();
+    if (!mogan_bn_act_grouped_eligible(G, B, C, HW) || !bn_shape_ok(B, C, HW, act)) return MOGAN_ERR_SHAPE;
+    return launch_small_fwd(x, gamma, beta, nullptr, y, mean, invstd, running_mean, running_var, B, C, HW, act, slope, eps, momentum,
+                            G, stream);
 }
 
 int mogan_bn_act_grouped_bwd(const float* x, const float* dy, const float* mean, const float* invstd, const float* gamma, const float* beta,
                              float* dx, float* dgamma, float* dbeta, int G, int B, int C, int HW, int act, float slope, int accumulate,
                              hipStream_t stream) {
-    if (!mogan_bn_act_grouped_eligible(G, B, C, HW) || (act == MOGAN_ACT_GLU && (C & 1))) return MOGAN_ERR_SHAPE;
-    const int Cy = act == MOGAN_ACT_GLU ? C / 2 : C;
-#define MOGAN_GRP_CASE(A) case A: hipLaunchKernelGGL((bn_small_bwd_kernel<A>), dim3(Cy), dim3(256), 0, stream, x, dy, mean, invstd, gamma, \
-                                                     beta, dx, dgamma, dbeta, B, C, HW, slope, accumulate, G); break;
-    switch (act) {
-        MOGAN_GRP_CASE(MOGAN_ACT_NONE)
-        MOGAN_GRP_CASE(MOGAN_ACT_RELU)
-        MOGAN_GRP_CASE(MOGAN_ACT_LRELU)
-        MOGAN_GRP_CASE(MOGAN_ACT_GLU)
-        default: return MOGAN_ERR_SHAPE;
-    }
-#undef MOGAN_GRP_CASE
-    return ok_launch();
+    if (!mogan_bn_act_grouped_eligible(G, B, C, HW) || !bn_shape_ok(B, C, HW, act)) return MOGAN_ERR_SHAPE;
+    return launch_small_bwd(x, dy, mean, invstd, gamma, beta, dx, dgamma, dbeta, B, C, HW, act, slope, accumulate, G, stream);
 }
-
-#define MOGAN_FWD_CASE(A)                                                                                           \
-    case A:                                                                                                         \
-        if (vec) hipLaunchKernelGGL((bn_act_fwd_kernel<A, true>), grid, dim3(256), 0, stream, x, mean, invstd,      \
-                                    gamma, beta, residual, y, C, HW, slope);                                        \
-        else hipLaunchKernelGGL((bn_act_fwd_kernel<A, false>), grid, dim3(256), 0, stream, x, mean, invstd, gamma,  \
-                                beta, residual, y, C, HW, slope);                                                   \
-        break;
 
 int mogan_bn_act_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                      const float* residual, float* y, int B, int C, int HW, int act, float slope, hipStream_t stream) {
-    if (B <= 0 || C <= 0 || HW <= 0 || (act == MOGAN_ACT_GLU && (C & 1))) return MOGAN_ERR_SHAPE;
+    if (!bn_shape_ok(B, C, HW, act)) return MOGAN_ERR_SHAPE;
     const int Cy = act == MOGAN_ACT_GLU ? C / 2 : C;
-    const bool vec = (HW & 3) == 0;
-    if ((long long)B * Cy > 65535) {
-        // fold: gridDim.y limit -- loop over batch chunks
-        const int bchunk = 65535 / Cy;
-        if (bchunk < 1) return MOGAN_ERR_SHAPE;
-        for (int b0 = 0; b0 < B; b0 += bchunk) {
-            const int nb = B - b0 < bchunk ? B - b0 : bchunk;
-            int rc = mogan_bn_act_fwd(x + (size_t)b0 * C * HW, mean, invstd, gamma, beta,
-                                      residual ? residual + (size_t)b0 * Cy * HW : nullptr, y + (size_t)b0 * Cy * HW, nb,
-                                      C, HW, act, slope, stream);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    const int per = vec ? 1024 : 256;
-    dim3 grid((HW + per - 1) / per, B * Cy);
-    switch (act) {
-        MOGAN_FWD_CASE(MOGAN_ACT_NONE)
-        MOGAN_FWD_CASE(MOGAN_ACT_RELU)
-        MOGAN_FWD_CASE(MOGAN_ACT_LRELU)
-        MOGAN_FWD_CASE(MOGAN_ACT_GLU)
-        default: return MOGAN_ERR_SHAPE;
-    }
-    return ok_launch();
+    return with_act(act, [&](auto A) {
+        return for_batch_chunks(B, Cy, [&](int b0, int nb) {
+            constexpr int ACT = decltype(A)::value;
+            const float* px = x + (size_t)b0 * C * HW;
+            const float* pr = residual ? residual + (size_t)b0 * Cy * HW : nullptr;
+            float* py = y + (size_t)b0 * Cy * HW;
+            if ((HW & 3) == 0)
+                hipLaunchKernelGGL((bn_act_fwd_kernel<ACT, true>), dim3((HW + 1023) / 1024, nb * Cy), dim3(256), 0, stream, px, mean,
+                                   invstd, gamma, beta, pr, py, C, HW, slope);
+            else
+                hipLaunchKernelGGL((bn_act_fwd_kernel<ACT, false>), dim3((HW + 255) / 256, nb * Cy), dim3(256), 0, stream, px, mean,
+                                   invstd, gamma, beta, pr, py, C, HW, slope);
+        });
+    });
 }
 
 int mogan_bn_act_bwd(const float* x, const float* dy, const float* mean, const float* invstd, const float* gamma,
                      const float* beta, float* dx, float* dgamma, float* dbeta, int B, int C, int HW, int act,
                      float slope, int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
-    if (B <= 0 || C <= 0 || HW <= 0 || (act == MOGAN_ACT_GLU && (C & 1))) return MOGAN_ERR_SHAPE;
+    if (!bn_shape_ok(B, C, HW, act)) return MOGAN_ERR_SHAPE;
     if (!ws || ws_bytes < mogan_bn_ws_bytes(B, C, HW)) return MOGAN_ERR_WS;
-    {
-        const Split s = make_split(B, C, HW);
-        if (s.bs * s.hs > 65535) return MOGAN_ERR_SHAPE;
-    }
-    switch (act) {
-        case MOGAN_ACT_NONE: return bn_bwd_impl<MOGAN_ACT_NONE>(x, dy, mean, invstd, gamma, beta, dx, dgamma, dbeta, B, C, HW, slope, accumulate, ws, stream);
-        case MOGAN_ACT_RELU: return bn_bwd_impl<MOGAN_ACT_RELU>(x, dy, mean, invstd, gamma, beta, dx, dgamma, dbeta, B, C, HW, slope, accumulate, ws, stream);
-        case MOGAN_ACT_LRELU: return bn_bwd_impl<MOGAN_ACT_LRELU>(x, dy, mean, invstd, gamma, beta, dx, dgamma, dbeta, B, C, HW, slope, accumulate, ws, stream);
-        case MOGAN_ACT_GLU: return bn_bwd_impl<MOGAN_ACT_GLU>(x, dy, mean, invstd, gamma, beta, dx, dgamma, dbeta, B, C, HW, slope, accumulate, ws, stream);
-        default: return MOGAN_ERR_SHAPE;
-    }
+    const Split s = make_split(B, C, HW);
+    const int YS = s.bs * s.hs;
+    if (YS > 65535) return MOGAN_ERR_SHAPE;
+    if (bn_small_ok(B, C, HW))
+        return launch_small_bwd(x, dy, mean, invstd, gamma, beta, dx, dgamma, dbeta, B, C, HW, act, slope, accumulate, 1, stream);
+    const int Cy = act == MOGAN_ACT_GLU ? C / 2 : C;
+    double* part = (double*)ws;
+    float* sums = (float*)((char*)ws + (size_t)C * YS * 4 * sizeof(double));
+    const float inv_n = 1.f / ((float)B * (float)HW);
+    return with_act(act, [&](auto A) {
+        constexpr int ACT = decltype(A)::value;
+        hipLaunchKernelGGL((bn_bwd_partial_kernel<ACT>), dim3(Cy, YS), dim3(256), 0, stream, x, dy, mean, invstd, gamma,
+                           beta, B, C, HW, s, slope, part);
+        if (Cy > 65535) return MOGAN_ERR_SHAPE;
+        if (bn_fused_ok(HW))                   // finalize folded into the apply pass: two launches
+            return for_batch_chunks(B, Cy, [&](int b0, int nb) {
+                hipLaunchKernelGGL((bn_bwd_apply_fused_kernel<ACT>), dim3((HW + FUSED_PER - 1) / FUSED_PER, nb * Cy), dim3(256), 0,
+                                   stream, x + (size_t)b0 * C * HW, dy + (size_t)b0 * Cy * HW, mean, invstd, gamma, beta,
+                                   (const double*)part, dx + (size_t)b0 * C * HW, dgamma, dbeta, C, HW, YS, slope, inv_n, accumulate,
+                                   b0 == 0 ? 1 : 0);
+            });
+        hipLaunchKernelGGL((bn_bwd_finalize_kernel<ACT>), dim3((Cy + 255) / 256), dim3(256), 0, stream,
+                           (const double*)part, C, YS, sums, dgamma, dbeta, accumulate);
+        return for_batch_chunks(B, Cy, [&](int b0, int nb) {
+            hipLaunchKernelGGL((bn_bwd_apply_kernel<ACT>), dim3((HW + 255) / 256, nb * Cy), dim3(256), 0, stream,
+                               x + (size_t)b0 * C * HW, dy + (size_t)b0 * Cy * HW, mean, invstd, gamma, beta,
+                               (const float*)sums, dx + (size_t)b0 * C * HW, C, HW, slope, inv_n);
+        });
+    });
 }
 
 int mogan_affine_act_fwd(const float* x, const float* scale, const float* shift, float* y, int B, int C, int HW,
@@ -910,11 +775,11 @@ int mogan_affine_act_bwd(const float* x, const float* dy, const float* scale, co
 // backward of y = relu(scale*conv + shift) given the OUTPUT y: dx = dy * scale[c] * (y > 0)
 int mogan_affine_relu_bwd_out(const float* y, const float* dy, const float* scale, float* dx, int B, int C, int HW,
                               hipStream_t stream) {
-    if (B <= 0 || C <= 0 || HW <= 0) return MOGAN_ERR_SHAPE;
+    if (!bn_shape_ok(B, C, HW)) return MOGAN_ERR_SHAPE;
     const long long n = (long long)B * C * HW;
     hipLaunchKernelGGL(affine_relu_bwd_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, y, dy, scale, dx,
                        n, C, HW);
-    return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH;
+    return ok_launch();
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@
 #include "../../include/mogan_hip.h"
 #include "mogan_internal.h"
 #include "mogan_mma.h"
+#include "mogan_bn.h"
 #include <type_traits>
 #ifndef PK_NSET
 #define PK_NSET 3
@@ -500,14 +501,8 @@ __global__ __launch_bounds__(256) void xtpack_kernel(const XtP p) {
 // conv -> BatchNorm(train) -> LeakyReLU/ReLU of a deep layer has B*OH*OW <= 2048 values per channel: ONE block computes the
 // batch statistics of 8 channels, applies them and hands the next layer its pixel panel -- instead of split-K reduce,
 // bn_partial, bn_finalize, bn_act_fwd and apack (5 launches).  32 lanes (half a wave) own a channel, its values stay in
-// registers between the statistics and the apply step; arithmetic as mogan_norm.hip (fp64 sums, biased variance for the
-// normalisation, unbiased for running_var).
-template <int ACT>
-__device__ __forceinline__ float act_apply(float t, float slope) {
-    if (ACT == MOGAN_ACT_RELU) return t > 0.f ? t : 0.f;
-    if (ACT == MOGAN_ACT_LRELU) return t > 0.f ? t : t * slope;
-    return t;
-}
+// registers between the statistics and the apply step; the arithmetic is mogan_bn.h's, as in mogan_norm.hip (fp64 sums, biased
+// variance for the normalisation, unbiased for running_var).
 __device__ __forceinline__ double half_wave_sum(double v) {          // all 32 lanes of the half get the sum
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -587,26 +582,24 @@ __global__ __launch_bounds__(256 * GT) void deep_tail_fwd_kernel(const TailP p) 
     }
     s1 = half_wave_sum(s1); s2 = half_wave_sum(s2);
     const double n = (double)NE;
-    const double m = s1 / n;
-    double var = s2 / n - m * m; if (var < 0) var = 0;
-    const float mu = (float)m, is = (float)(1.0 / sqrt(var + (double)p.eps));
+    float mu, is;
+    double var;
+    bn_stats_of(s1, s2, n, p.eps, mu, is, var);
     if (j == 0) {
         p.mean[grp * p.C + c] = mu; p.invstd[grp * p.C + c] = is;
-        const double unb = n > 1 ? var * n / (n - 1.0) : var;
         if (GT == 1) {
-            if (p.rmean) p.rmean[c] = (1.f - p.momentum) * p.rmean[c] + p.momentum * mu;
-            if (p.rvar) p.rvar[c] = (1.f - p.momentum) * p.rvar[c] + p.momentum * (float)unb;
+            bn_running_update(p.rmean, p.rvar, c, mu, var, n, p.momentum);
         } else {
-            S[(grp * 8 + chl) * 2] = mu; S[(grp * 8 + chl) * 2 + 1] = (float)unb;
+            S[(grp * 8 + chl) * 2] = mu; S[(grp * 8 + chl) * 2 + 1] = (float)bn_unbiased(var, n);
         }
     }
-    const float sc = p.gamma[c] * is, sh = p.beta[c] - mu * sc;
+    const BnCoef k = bn_coef(mu, is, p.gamma, p.beta, c);
     const int NT = NE * GT;
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
         const int e = j + 32 * i;
         if (e < NE) {
-            const float t = act_apply<ACT>(v[i] * sc + sh, p.slope);
+            const float t = bn_fwd_elem<ACT>(v[i], 0.f, k, k, p.slope);
             p.z[idx[i]] = t;
             if (p.zpanel) L[chl * NT + grp * NE + e] = t;
         }
@@ -615,8 +608,8 @@ __global__ __launch_bounds__(256 * GT) void deep_tail_fwd_kernel(const TailP p) 
     if (GT > 1 && grp == 0 && j == 0) {                // the groups' running-statistics updates, in call order
         float rm = p.rmean ? p.rmean[c] : 0.f, rv = p.rvar ? p.rvar[c] : 0.f;
         for (int g = 0; g < GT; ++g) {
-            rm = (1.f - p.momentum) * rm + p.momentum * S[(g * 8 + chl) * 2];
-            rv = (1.f - p.momentum) * rv + p.momentum * S[(g * 8 + chl) * 2 + 1];
+            rm = bn_running_mix(rm, S[(g * 8 + chl) * 2], p.momentum);
+            rv = bn_running_mix(rv, S[(g * 8 + chl) * 2 + 1], p.momentum);
         }
         if (p.rmean) p.rmean[c] = rm;
         if (p.rvar) p.rvar[c] = rv;
@@ -637,8 +630,7 @@ __global__ __launch_bounds__(256 * GT) void deep_tail_bwd_kernel(const TailBwdP 
     const int tid = threadIdx.x & 255, grp = threadIdx.x >> 8, chl = tid >> 5, j = tid & 31;
     const int c0 = blockIdx.x * 8, c = c0 + chl;
     const int NE = p.B * p.HW, b0 = grp * p.B, NT = NE * GT;
-    const float mu = p.mean[grp * p.C + c], is = p.invstd[grp * p.C + c];
-    const float sc = p.gamma[c] * is, sh = p.beta[c] - mu * sc;
+    const BnCoef k = bn_coef(p.mean[grp * p.C + c], p.invstd[grp * p.C + c], p.gamma, p.beta, c);
     float g[EPT], xh[EPT];
     double a0 = 0.0, a1 = 0.0;
 #pragma unroll
@@ -648,12 +640,10 @@ __global__ __launch_bounds__(256 * GT) void deep_tail_bwd_kernel(const TailBwdP 
         if (e < NE) {
             const int b = e / p.HW, pos = e - b * p.HW;
             const size_t idx = ((size_t)(b0 + b) * p.C + c) * p.HW + pos;
-            const float xa = p.y[idx], d = p.dz[idx];
-            const float t = xa * sc + sh;
-            float da = d;
-            if (ACT == MOGAN_ACT_RELU) da = t > 0.f ? d : 0.f;
-            if (ACT == MOGAN_ACT_LRELU) da = t > 0.f ? d : d * p.slope;
-            g[i] = da; xh[i] = (xa - mu) * is;
+            const float xa = p.y[idx];
+            float da, dgate;
+            act_bwd<ACT>(xa, 0.f, p.dz[idx], k, k, p.slope, da, dgate);
+            g[i] = da; xh[i] = bn_xhat(k, xa);
             a0 += da; a1 += (double)da * xh[i];
         }
     }
@@ -661,8 +651,7 @@ __global__ __launch_bounds__(256 * GT) void deep_tail_bwd_kernel(const TailBwdP 
     const float f0 = (float)a0, f1 = (float)a1;
     if (j == 0) {
         if (GT == 1) {
-            if (p.dbeta) p.dbeta[c] = (p.accumulate ? p.dbeta[c] : 0.f) + f0;
-            if (p.dgamma) p.dgamma[c] = (p.accumulate ? p.dgamma[c] : 0.f) + f1;
+            bn_write_dparam(p.dgamma, p.dbeta, c, f0, f1, p.accumulate);
         } else {
             S[(grp * 8 + chl) * 2] = f0; S[(grp * 8 + chl) * 2 + 1] = f1;
         }
@@ -673,7 +662,7 @@ __global__ __launch_bounds__(256 * GT) void deep_tail_bwd_kernel(const TailBwdP 
         const int e = j + 32 * i;
         if (e < NE) {
             const int b = e / p.HW, pos = e - b * p.HW;
-            const float d = sc * (g[i] - f0 * inv_n - xh[i] * f1 * inv_n);
+            const float d = bn_dx(k.sc, g[i], xh[i], f0, f1, inv_n);
             p.dy[((size_t)(b0 + b) * p.C + c) * p.HW + pos] = d;
             if (p.dypanel) L[chl * NT + grp * NE + e] = d;
         }

@@ -1074,129 +1074,83 @@ def _bchw(x):
 
 
 class BNActFn(torch.autograd.Function):
-    """Training-mode BatchNorm1d/2d fused with GLU / LeakyReLU / ReLU and an optional residual add
-    (model.py:52-54,72-80,96-101,366-373,577-611).  Updates the running statistics in place like
-    nn.BatchNorm does (momentum 0.1, unbiased variance)."""
+    """`groups` training-mode BatchNorm1d/2d calls fused with GLU / LeakyReLU / ReLU on the groups of B images of one
+    (groups*B, C, ...) tensor (model.py:52-54,72-80,96-101,366-373,577-611).  Every group has its own batch statistics and updates
+    the running statistics in place like nn.BatchNorm does (momentum 0.1, unbiased variance), group after group.  groups == 1 is the
+    plain call, which may add a residual; groups > 1 are the per-object calls of the object pathways (model.py:395-407, 662-672;
+    SURVEY F11) and the [real; fake] batch of a discriminator update (miscc/losses.py:136-174).
+    Launches: where bn_groups_ok, all groups in ONE launch each way.  Otherwise the entry points of the plain call once per group on
+    the group's slice of x / y (the groups are contiguous: no copies, no concatenation): small maps (<= 4096 values per channel)
+    take ONE launch (a block per channel reduces, finalises and applies), larger ones two (partial sums; apply with the reduction
+    of the partial sums folded in: per wave, an xor-butterfly, no barrier -- round 2's version of that fold, every block
+    re-reducing behind a barrier, was 3 % slower in the step and dropped; this one is +0.3 %), planes whose size is not a
+    multiple of 4 three."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, act, slope, eps, momentum):
-        x, gamma, beta = _c(x), _c(gamma), _c(beta)
-        B, C, HW = _bchw(x)
-        dev = x.device
-        stats = torch.empty((2, C), dtype=torch.float32, device=dev)
-        need = lib.bn_ws_bytes(B, C, HW)
-        wsp, wsn = workspace(dev)
-        if need > wsn:
-            raise lib.MoganHipError("workspace too small for bn (%d > %d)" % (need, wsn))
-        # one call: small maps (<= 4096 values per channel) take ONE launch (a block per channel reduces, finalises and applies),
-        # larger ones two (partial sums; apply with the reduction of the partial sums folded in: per wave, an xor-butterfly, no
-        # barrier -- round 2's version of that fold, every block re-reducing behind a barrier, was 3 % slower in the step and
-        # dropped; this one is +0.3 %), planes whose size is not a multiple of 4 three.
-        Cy = C // 2 if act == ACT_GLU else C
-        y = torch.empty((B, Cy) + tuple(x.shape[2:]), dtype=torch.float32, device=dev)
-        res = _c(residual) if residual is not None else None
-        if BN_DEFER is not None:
-            BN_DEFER.append((stats[0], stats[1], B * HW, running_mean, running_var, eps, momentum))
-            running_mean = running_var = None
-        call("mogan_bn_act_fwd_fused", ptr(x), ptr(gamma), ptr(beta), ptr(res), ptr(running_mean), ptr(running_var),
-             ptr(stats[0]), ptr(stats[1]), ptr(y), B, C, HW, act, slope, eps, momentum, wsp, wsn, stream_ptr())
-        if ACT_TRACE is not None and act in (ACT_RELU, ACT_LRELU):
-            ACT_TRACE.append((act, y))
-        ctx.save_for_backward(x, gamma, beta, stats)
-        ctx.cfg = (act, slope, residual is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, gamma, beta, stats = ctx.saved_tensors
-        act, slope, has_res = ctx.cfg
-        dy = _c(dy)
-        B, C, HW = _bchw(x)
-        dx = torch.empty_like(x)
-        gg, gb = _grad_buf(gamma), _grad_buf(beta)
-        direct = gg is not None and gb is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]
-        wsp, wsn = workspace(x.device)
-        if direct:
-            dg, db = gg, gb
-        else:
-            dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
-            dg, db = dgb[0], dgb[1]
-        call("mogan_bn_act_bwd", ptr(x), ptr(dy), ptr(stats[0]), ptr(stats[1]), ptr(gamma), ptr(beta), ptr(dx),
-             ptr(dg), ptr(db), B, C, HW, act, slope, 1 if direct else 0, wsp, wsn, stream_ptr())
-        if direct:
-            _grad_hit(gg)
-            _grad_hit(gb)
-            dg = db = None
-        return dx, dg, db, (dy if has_res else None), None, None, None, None, None, None
-
-
-class BNActGroupedFn(torch.autograd.Function):
-    """`groups` training-mode BatchNorm(+activation) calls on the groups of B images of one (groups*B, C, ...) tensor: own batch
-    statistics per group, running statistics updated group after group (the per-object BatchNorm calls of the object pathways,
-    model.py:395-407, 662-672; SURVEY F11 -- and, round 5, the [real; fake] batch of a discriminator update,
-    miscc/losses.py:136-174).  One launch each way where a group has <= 4096 values per channel; larger maps: the two-launch
-    kernels of BNActFn once per group on the group's slice of x / y (the groups are contiguous: no copies, no concatenation)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, act, slope, eps, momentum, groups):
+    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, act, slope, eps, momentum, groups):
         x, gamma, beta = _c(x), _c(gamma), _c(beta)
         N, C, HW = _bchw(x)
         B = N // groups
-        stats = torch.empty((2, groups, C), dtype=torch.float32, device=x.device)
+        dev = x.device
+        stats = torch.empty((2, groups, C), dtype=torch.float32, device=dev)
         Cy = C // 2 if act == ACT_GLU else C
-        y = torch.empty((N, Cy) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        y = torch.empty((N, Cy) + tuple(x.shape[2:]), dtype=torch.float32, device=dev)
         one = bn_groups_ok(x, groups)
         if BN_DEFER is not None:
-            raise lib.MoganHipError("deferred running statistics: one BatchNorm call per launch only")
+            if groups > 1:
+                raise lib.MoganHipError("deferred running statistics: one BatchNorm call per launch only")
+            BN_DEFER.append((stats[0, 0], stats[1, 0], B * HW, running_mean, running_var, eps, momentum))
+            running_mean = running_var = None
         if one:
             call("mogan_bn_act_grouped_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), ptr(stats[0]),
                  ptr(stats[1]), ptr(y), groups, B, C, HW, act, slope, eps, momentum, stream_ptr())
         else:
-            wsp, wsn = workspace(x.device)
-            if lib.bn_ws_bytes(B, C, HW) > wsn:
-                raise lib.MoganHipError("workspace too small for bn")
+            need = lib.bn_ws_bytes(B, C, HW)
+            wsp, wsn = workspace(dev)
+            if need > wsn:
+                raise lib.MoganHipError("workspace too small for bn (%d > %d)" % (need, wsn))
+            res = _c(residual) if residual is not None else None
             for g in range(groups):
-                call("mogan_bn_act_fwd_fused", ptr(x[g * B:(g + 1) * B]), ptr(gamma), ptr(beta), None, ptr(running_mean),
+                call("mogan_bn_act_fwd_fused", ptr(x[g * B:(g + 1) * B]), ptr(gamma), ptr(beta), ptr(res), ptr(running_mean),
                      ptr(running_var), ptr(stats[0, g]), ptr(stats[1, g]), ptr(y[g * B:(g + 1) * B]), B, C, HW, act, slope, eps,
                      momentum, wsp, wsn, stream_ptr())
         if ACT_TRACE is not None and act in (ACT_RELU, ACT_LRELU):
             _trace(act, y, groups)                       # (one entry per reference call, in call order)
         ctx.save_for_backward(x, gamma, beta, stats)
-        ctx.cfg = (act, slope, groups, one)
+        ctx.cfg = (act, slope, groups, one, residual is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gamma, beta, stats = ctx.saved_tensors
-        act, slope, groups, one = ctx.cfg
+        act, slope, groups, one, has_res = ctx.cfg
         dy = _c(dy)
         N, C, HW = _bchw(x)
         B = N // groups
         dx = torch.empty_like(x)
         gg, gb = _grad_buf(gamma), _grad_buf(beta)
         direct = gg is not None and gb is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]
+        loop_adds = groups > 1 and not one                   # (the per-group calls accumulate: into zeros, if into a buffer of ours)
         if direct:
             dg, db = gg, gb
-        elif one:
-            dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
-            dg, db = dgb[0], dgb[1]
         else:
-            dgb = torch.zeros((2, C), dtype=torch.float32, device=x.device)      # (the per-group calls accumulate)
+            dgb = (torch.zeros if loop_adds else torch.empty)((2, C), dtype=torch.float32, device=x.device)
             dg, db = dgb[0], dgb[1]
+        accumulate = 1 if direct or loop_adds else 0
         if one:
             call("mogan_bn_act_grouped_bwd", ptr(x), ptr(dy), ptr(stats[0]), ptr(stats[1]), ptr(gamma), ptr(beta), ptr(dx),
-                 ptr(dg), ptr(db), groups, B, C, HW, act, slope, 1 if direct else 0, stream_ptr())
+                 ptr(dg), ptr(db), groups, B, C, HW, act, slope, accumulate, stream_ptr())
         else:
             wsp, wsn = workspace(x.device)
             for g in range(groups):
                 call("mogan_bn_act_bwd", ptr(x[g * B:(g + 1) * B]), ptr(dy[g * B:(g + 1) * B]), ptr(stats[0, g]), ptr(stats[1, g]),
-                     ptr(gamma), ptr(beta), ptr(dx[g * B:(g + 1) * B]), ptr(dg), ptr(db), B, C, HW, act, slope, 1, wsp, wsn,
-                     stream_ptr())
+                     ptr(gamma), ptr(beta), ptr(dx[g * B:(g + 1) * B]), ptr(dg), ptr(db), B, C, HW, act, slope, accumulate, wsp,
+                     wsn, stream_ptr())
         if direct:
             _grad_hit(gg)
             _grad_hit(gb)
             dg = db = None
-        return dx, dg, db, None, None, None, None, None, None, None
+        return dx, dg, db, (dy if has_res else None), None, None, None, None, None, None, None
 
 
 def bn_groups_ok(x, groups):
@@ -1208,12 +1162,9 @@ def bn_groups_ok(x, groups):
 
 def bn_act(x, gamma, beta, running_mean, running_var, act=ACT_NONE, slope=0.2, residual=None, eps=1e-5,
            momentum=0.1, groups=1):
-    if groups > 1:
-        assert residual is None
-        return BNActGroupedFn.apply(x, gamma, beta, running_mean, running_var, act, float(slope), float(eps), float(momentum),
-                                    int(groups))
-    return BNActFn.apply(x, gamma, beta, residual, running_mean, running_var, act, float(slope), float(eps),
-                         float(momentum))
+    assert groups == 1 or residual is None
+    return BNActFn.apply(x, gamma, beta, residual, running_mean, running_var, act, float(slope), float(eps), float(momentum),
+                         int(groups))
 
 
 class AffineActFn(torch.autograd.Function):

@@ -241,9 +241,12 @@ def test_group_sum():
 
 
 # one-launch path (<= 4096 values per channel), two-launch path (HW % 4 == 0: finalize folded into the apply pass; (3,4,96,96): three
-# tiles per plane, the last one partial), three-launch path ((20,4,15,15): odd plane size beyond the one-launch limit)
+# tiles per plane, the last one partial), three-launch path ((20,4,15,15): odd plane size beyond the one-launch limit).  The two
+# 2000-channel shapes have more (image, channel) planes than a grid's y extent: the apply kernels go out in batch chunks of 32 + 32 + 2
+# images (GLU, 1000 output channels: 65 + 1) -- (66,2000,8,8) on the two-launch path, (66,2000,3,3) on the three-launch path (a plane
+# of 9 values is below the one-launch floor of 16, and odd)
 @pytest.mark.parametrize("shape", [(4, 8, 8, 8), (3, 6, 15, 15), (16, 24), (2, 10, 64, 64), (5, 4, 3, 3), (16, 6, 16, 16), (17, 6, 16, 16),
-                                   (3, 4, 96, 96), (20, 4, 15, 15)])
+                                   (3, 4, 96, 96), (20, 4, 15, 15), (66, 2000, 8, 8), (66, 2000, 3, 3)])
 @pytest.mark.parametrize("act", ["none", "relu", "lrelu", "glu"])
 @pytest.mark.parametrize("res", [False, True])
 def test_bn_act(shape, act, res):
@@ -270,6 +273,25 @@ def test_bn_act(shape, act, res):
     _check(xd.grad, x.grad, 2e-5, "dx"); _check(gd.grad, gm.grad, 2e-5, "dgamma"); _check(bd.grad, bt.grad, 2e-5, "dbeta")
     if res:
         _check(rd.grad, r.grad, 1e-7, "dres")
+
+
+# (66,1000,3,3): 66000 (image, channel) planes, two batch chunks (65 + 1 images)
+@pytest.mark.parametrize("shape", [(3, 6, 5, 7), (66, 1000, 3, 3)])
+@pytest.mark.parametrize("act", ["none", "relu", "lrelu"])
+def test_affine_act(shape, act):
+    """mogan_affine_act_fwd / _bwd: the eval-mode BatchNorm affine + activation of the frozen trunk, y and dx against fp64 (the
+    tolerances test_bn_act uses for y and dx)."""
+    C = shape[1]
+    x = T("afx%s" % (shape,), shape, 1.5, 0.3).requires_grad_(True)
+    scale, shift = T("afs%d" % C, (C,), 0.5, 1.0), T("afb%d" % C, (C,), 0.3)
+    ref = _act_ref(x.double() * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1), act)
+    g = T("afg%s%s" % (shape, act), shape)
+    ref.backward(g.double())
+    xd = x.detach().to(DEV).requires_grad_(True)
+    y = ops.affine_act(xd, scale.to(DEV), shift.to(DEV), ACTS[act], 0.2)
+    y.backward(g.to(DEV))
+    _check(y, ref, 5e-6, "y")
+    _check(xd.grad, x.grad, 2e-5, "dx")
 
 
 @pytest.mark.parametrize("act", ["relu", "lrelu", "tanh", "sigmoid", "glu"])
