@@ -372,7 +372,8 @@ int mogan_bn_running_update(const float* mean, const float* invstd, float* runni
 /* mogan_bn_stats + mogan_bn_act_fwd in one call (training-mode BatchNorm + activation, model.py:48-81, 575-613): maps with
  * B*HW <= 4096 values per channel (and HW >= 16) take ONE launch -- a block per output channel reduces, finalises and applies --,
  * larger ones the three launches of the two calls above; mean / invstd [C] are written for mogan_bn_act_bwd either way (which
- * takes the matching one-launch kernel for the same shapes).  ws as for mogan_bn_stats. */
+ * takes the matching one-launch kernel for the same shapes).  ws as for mogan_bn_stats on the larger maps (MOGAN_ERR_WS, nothing
+ * written, where it is NULL or short); the one-launch shapes do not need it and do not look at it (NULL / 0 is fine there). */
 int mogan_bn_act_fwd_fused(const float* x, const float* gamma, const float* beta, const float* residual, float* running_mean,
                            float* running_var, float* mean, float* invstd, float* y, int B, int C, int HW, int act, float slope,
                            float eps, float momentum, void* ws, size_t ws_bytes, hipStream_t stream);

@@ -551,8 +551,9 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
 // -------------------------------------------------------------------------------- host side
 static inline int ok_launch() { return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH; }
 
+// (an activation code with_act has no kernel for is refused here, before an entry point's first launch)
 static bool bn_shape_ok(int B, int C, int HW, int act = MOGAN_ACT_NONE) {
-    return B > 0 && C > 0 && HW > 0 && !(act == MOGAN_ACT_GLU && (C & 1));
+    return B > 0 && C > 0 && HW > 0 && act >= MOGAN_ACT_NONE && act <= MOGAN_ACT_GLU && !(act == MOGAN_ACT_GLU && (C & 1));
 }
 // path selection (BatchNorm1d, HW == 1, keeps its thread-per-channel kernels: a block per channel would be 16 values wide)
 static bool bn_fused_ok(int HW) { return (HW & 3) == 0 && HW >= 64; }
@@ -664,7 +665,8 @@ int mogan_bn_act_fwd_fused(const float* x, const float* gamma, const float* beta
     if (bn_small_ok(B, C, HW))
         return launch_small_fwd(x, gamma, beta, residual, y, mean, invstd, running_mean, running_var, B, C, HW, act, slope, eps,
                                 momentum, 1, stream);
-    if (!bn_fused_ok(HW) || Cy > 65535) {
+    if (Cy > 65535) return MOGAN_ERR_SHAPE;           // (no apply grid holds one image: for_batch_chunks would say so after the statistics)
+    if (!bn_fused_ok(HW)) {
         int rc = mogan_bn_stats(x, B, C, HW, eps, momentum, mean, invstd, running_mean, running_var, ws, ws_bytes, stream);
         return rc ? rc : mogan_bn_act_fwd(x, mean, invstd, gamma, beta, residual, y, B, C, HW, act, slope, stream);
     }
@@ -738,6 +740,7 @@ int mogan_bn_act_bwd(const float* x, const float* dy, const float* mean, const f
     if (bn_small_ok(B, C, HW))
         return launch_small_bwd(x, dy, mean, invstd, gamma, beta, dx, dgamma, dbeta, B, C, HW, act, slope, accumulate, 1, stream);
     const int Cy = act == MOGAN_ACT_GLU ? C / 2 : C;
+    if (Cy > 65535) return MOGAN_ERR_SHAPE;
     double* part = (double*)ws;
     float* sums = (float*)((char*)ws + (size_t)C * YS * 4 * sizeof(double));
     const float inv_n = 1.f / ((float)B * (float)HW);
@@ -745,7 +748,6 @@ int mogan_bn_act_bwd(const float* x, const float* dy, const float* mean, const f
         constexpr int ACT = decltype(A)::value;
         hipLaunchKernelGGL((bn_bwd_partial_kernel<ACT>), dim3(Cy, YS), dim3(256), 0, stream, x, dy, mean, invstd, gamma,
                            beta, B, C, HW, s, slope, part);
-        if (Cy > 65535) return MOGAN_ERR_SHAPE;
         if (bn_fused_ok(HW))                   // finalize folded into the apply pass: two launches
             return for_batch_chunks(B, Cy, [&](int b0, int nb) {
                 hipLaunchKernelGGL((bn_bwd_apply_fused_kernel<ACT>), dim3((HW + FUSED_PER - 1) / FUSED_PER, nb * Cy), dim3(256), 0,

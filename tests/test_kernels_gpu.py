@@ -7,7 +7,10 @@ Stated tolerances (fp32 tensors and accumulators; products on the bf16 MFMA pipe
                           message).  The per-element bound of the convolutions -- |got - fp64| <= TOL * (the same sum over the
                           absolute terms), every element written, nothing outside touched -- is
                           tests/test_conv_entry_points_gpu.py, on the same geometries (tests/conv_cases.py)
-  BN / activations / STN / attention / softmax / pooling   max-abs <= 2e-5 (values are O(1))
+  BN / activations / STN / attention / softmax / pooling   max-abs <= 2e-5 (values are O(1)).  The per-element bound of the batch-norm,
+                          affine, activation and bias entry points -- every output against fp64 within TOL * S, statistics and
+                          running buffers included, in guarded memory, on one shape per path of the dispatch -- is
+                          tests/test_bn_entry_points_gpu.py (tests/bn_cases.py)
   Adam                    max-abs <= 1e-6 on O(1) parameters after three steps
 """
 import os
