@@ -676,6 +676,19 @@ int mogan_damsm_words_bwd_text(const float* words, const int32_t* cap_lens, cons
 int mogan_damsm_sent_bwd_text(const float* cnn, const float* rnn, const float* dsim, int B, int Bc, int C, float gamma3,
                               float eps, float* drnn, hipStream_t stream);
 
+/* R-precision ranking (the AttnGAN paper's text-image metric; the reference has no code for it -- DESIGN.md section 9c).
+ * Query q = image code code[q] (C floats).  Candidate 0 = pos[q] (its caption's sentence code), candidates 1..Rn = rows
+ * idx[q, r-1] of bank (N, C).
+ *   score[q, r] = <code_q, cand_r> / max(|code_q| * |cand_r|, eps)          (miscc/losses.py cosine_similarity)
+ *   rank[q]     = number of r in 1..Rn with score[q, r] > score[q, 0]       (0 = retrieved first; a tie counts for the match,
+ *                                                                            as argmax's first index does)
+ * One launch, one block per query; fp32 fmaf chains over lane-strided channels; every candidate, pos included, runs through the
+ * same instruction sequence, so equal candidate bits give equal score bits, and the same inputs give the same bits on every call.
+ * idx entries are clamped to [0, N-1] (as the caption kernels clamp token ids).  score (Q, Rn+1) is nullable; rank (Q) int32.
+ * MOGAN_ERR_SHAPE before any HIP call: Q, Rn, C or N <= 0, Rn > 1023, N > 2^31-1, a NULL code / pos / bank / idx / rank. */
+int mogan_retrieval_rank(const float* code, const float* pos, const float* bank, const int32_t* idx, int Q, int Rn, int C,
+                         long long N, float eps, float* score, int32_t* rank, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

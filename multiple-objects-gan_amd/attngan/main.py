@@ -46,6 +46,11 @@ def parse_args(argv=None):
     parser.add_argument('--sampling', action='store_true',
                         help='evaluation (TRAIN.FLAG False): one image per caption of the whole split (sampling()) '
                              'instead of the 25 rows of sample()')
+    parser.add_argument('--r_precision', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): R-precision of TRAIN.NET_G under the DAMSM pair TRAIN.NET_E over the '
+                             'split (condGANTrainer.r_precision) -> <NET_G minus .pth>/<split>/r_precision.json')
+    parser.add_argument('--real', action='store_true',
+                        help='with --r_precision: score the real images instead of generated ones (the ceiling of the encoder pair)')
     return parser.parse_args(argv)
 
 
@@ -97,7 +102,7 @@ def main(argv=None):
         output_dir = args.resume
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
-    with_bbox = evaluate and not args.sampling
+    with_bbox = evaluate and not (args.sampling or args.r_precision)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -118,6 +123,8 @@ def main(argv=None):
         algo.train()
     elif args.sampling:
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
+    elif args.r_precision:
+        algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:

@@ -139,6 +139,38 @@ class DAMSMEngine:
             self.text_encoder.train(was)
         return [float(v) / max(n, 1) for v in tot.tolist()]
 
+    def retrieval(self, loader, dataset, n_mismatched=99, seed=0):
+        """R-precision of the REAL images of `loader` under the two encoders as they are now (attngan/retrieval.py, DESIGN.md
+        section 9c): every caption of `dataset` encoded once, each image's code ranked against its batch caption and
+        `n_mismatched` captions of other images (hip/ops.retrieval_rank).  Eval mode, no gradients, one read-back; the text
+        encoder is left in the mode it was found in.  None, with a note, when the split has too few captions of other images."""
+        from .retrieval import SentenceBank, dataset_captions, draw_mismatched, eligible, fold_stats
+        captions, image_index, keys = dataset_captions(dataset)
+        if not eligible(image_index, n_mismatched):
+            print('R-precision skipped: the validation split has fewer than %d captions of other images' % n_mismatched)
+            return None
+        was = self.text_encoder.training
+        self.text_encoder.eval()
+        rng, ranks = np.random.RandomState(seed), []
+        try:
+            bank = SentenceBank.build(self.text_encoder, captions, image_index, cfg.TEXT.WORDS_NUM, seed,
+                                      key_to_image={k: i for i, k in enumerate(keys)})
+            with torch.no_grad():
+                for data in loader:
+                    lens, order = torch.sort(data[2], 0, True)
+                    batch_keys = [data[4][i] for i in order.tolist()]
+                    caps = data[1][order].squeeze(-1).to(self.device)
+                    _, code2048 = self.trunk(data[0][-1][order].to(self.device, non_blocking=True))
+                    code = self.image_encoder.emb_cnn_code(code2048)
+                    _, sent = self.text_encoder(caps, lens, self.text_encoder.init_hidden(caps.shape[0]))
+                    idx = draw_mismatched(bank.image_index, bank.images_of(batch_keys), n_mismatched, rng)
+                    ranks.append(ops.retrieval_rank(code, sent, bank.bank, idx))
+        finally:
+            self.text_encoder.train(was)
+        if not ranks:
+            return None
+        return fold_stats(torch.cat(ranks).cpu().numpy(), 1)["r_precision"]
+
     def decay_lr(self):
         """once per epoch: * 0.98, floored at ENCODER_LR / 10"""
         self.opt.lr = max(self.opt.lr * LR_DECAY, self.base_lr / 10.0)
@@ -227,6 +259,9 @@ def main(argv=None):
         val = engine.evaluate(loader_val)
         print('| epoch %3d | %d batches | %.1f s | lr %.6f | w_loss %.4f %.4f | s_loss %.4f %.4f | |g| %.3f | valid w %.4f %.4f '
               's %.4f %.4f' % (epoch, n, time.time() - t0, engine.opt.lr, w0, w1, s0, s1, norm, val[0], val[1], val[2], val[3]))
+        rp = engine.retrieval(loader_val, dataset_val, seed=args.manualSeed)
+        if rp is not None:
+            print('| epoch %3d | valid R-precision %.4f (real images, 99 mismatched captions)' % (epoch, rp))
         engine.decay_lr()
         if epoch % interval == 0 or epoch == cfg.TRAIN.MAX_EPOCH - 1:
             print('Save encoders to:', ', '.join(engine.save(model_dir, epoch)))

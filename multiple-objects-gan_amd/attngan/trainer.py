@@ -1546,6 +1546,102 @@ class condGANTrainer(object):
             print('Load text encoder from:', cfg.TRAIN.NET_E)
         return netG, text_encoder.to(self.device).eval()
 
+    def _load_image_encoder(self):
+        """The image encoder that TRAIN.NET_E's text encoder was trained with: the `image_encoder` twin of its path, by
+        build_models' rule and with its error.  The heads are TEXT.EMBEDDING_DIM wide as in training (outside training the
+        reference's constructor fixes them at 256, model.py:213, which is the same thing for the published pairs only)."""
+        nef = cfg.TEXT.EMBEDDING_DIM
+        image_encoder = CNN_ENCODER(nef, pretrained=False)
+        if image_encoder.nef != nef:
+            image_encoder.nef = nef
+            image_encoder.emb_features = type(image_encoder.emb_features)(768, nef, kernel_size=1, stride=1, padding=0, bias=False)
+            image_encoder.emb_cnn_code = type(image_encoder.emb_cnn_code)(2048, nef)
+            image_encoder.init_trainable_weights()
+        if cfg.TRAIN.NET_E != '':
+            img_path = cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder')
+            for path in (cfg.TRAIN.NET_E, img_path):
+                if not os.path.isfile(path):
+                    raise FileNotFoundError("DAMSM encoder checkpoint not found: %s (cwd %s)" % (path, os.getcwd()))
+            image_encoder.load_state_dict(torch.load(img_path, map_location='cpu'))
+            print('Load image encoder from:', img_path)
+        for p in image_encoder.parameters():
+            p.requires_grad = False
+        return image_encoder.to(self.device).eval()
+
+    def r_precision(self, split_dir, num_samples=30000, n_mismatched=99, folds=10, seed=100, real=False, return_codes=False):
+        """R-precision of the checkpoint TRAIN.NET_G under the DAMSM pair TRAIN.NET_E: one 256x256 image per
+        caption of the data loader (EMA generator, eval mode, seeded noise) -- or, with real=True, the real 256x256 image: the
+        ceiling the encoder pair allows --, its image code ranked against its own caption and `n_mismatched` captions of other
+        images of the split (hip/ops.retrieval_rank, one launch per batch; the ranks stay on the device until the end).
+        `seed` fixes the noise, the mismatched draws, the bank's long-caption subsets and, with an empty NET_E, the random-init
+        encoders.  A split with fewer than `n_mismatched` captions of other images is ranked against as many as it has.
+        Writes <NET_G minus .pth>/<split>/r_precision.json and returns its content; with return_codes also a dict of host
+        tensors: the image codes "code", "pos", "idx", the ranks "rank" and the "bank" the rows of idx point into."""
+        import json
+        from .datasets import prepare_data
+        from .retrieval import SentenceBank, draw_mismatched, fold_stats
+        if cfg.TRAIN.NET_G == '':
+            print('Error: the path for model NET_G is not found!')
+            return None
+        if split_dir == 'test':
+            split_dir = 'valid'
+        torch.manual_seed(seed)
+        netG, text_encoder = self._load_eval_models()
+        image_encoder = self._load_image_encoder()
+        save_dir = '%s/%s' % (cfg.TRAIN.NET_G[:cfg.TRAIN.NET_G.rfind('.pth')], split_dir)
+        mkdir_p(save_dir)
+        bank = SentenceBank.from_dataset(text_encoder, self.data_loader.dataset, cfg.TEXT.WORDS_NUM, seed)
+        usable = len(bank) - int(np.bincount(bank.image_index).max())       # captions of other images, for the fullest image
+        if usable < 1:
+            raise ValueError("r_precision: the split holds no caption of another image to rank against")
+        if n_mismatched > usable:
+            print("R-precision: the split has %d captions of other images per query, not %d -- ranking against %d (a smaller "
+                  "candidate set gives a HIGHER figure; the JSON records it)" % (usable, n_mismatched, usable))
+            n_mismatched = usable
+        rng = np.random.RandomState(seed)
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(seed)
+        ranks, codes, poss, idxs, n = [], [], [], [], 0
+        for data in self.data_loader:
+            if n >= num_samples:
+                break
+            imgs, captions, cap_lens, class_ids, keys, (tm, tmi), label_one_hot = prepare_data(data, self.device)
+            B = captions.shape[0]
+            with torch.no_grad():
+                words_embs, sent_emb = text_encoder(captions, cap_lens.cpu(), text_encoder.init_hidden(B))
+                sent_emb = sent_emb.contiguous()
+                if real:
+                    img = imgs[-1]
+                else:
+                    mask = (captions == 0)
+                    if mask.size(1) > words_embs.size(2):
+                        mask = mask[:, :words_embs.size(2)]
+                    noise = torch.randn(B, cfg.GAN.Z_DIM, device=self.device, generator=gen)
+                    eps = torch.randn(B, cfg.GAN.CONDITION_DIM, device=self.device, generator=gen)
+                    fake_imgs, _, _, _ = netG(noise, sent_emb, words_embs.contiguous(), mask, tmi, label_one_hot, eps=eps)
+                    img = fake_imgs[-1]
+                code = image_encoder(img)[1]
+                idx = draw_mismatched(bank.image_index, bank.images_of(keys), n_mismatched, rng)
+                ranks.append(ops.retrieval_rank(code, sent_emb, bank.bank, idx))
+            if return_codes:
+                codes.append(code); poss.append(sent_emb); idxs.append(torch.from_numpy(idx))
+            n += B
+        if not ranks:
+            raise ValueError("r_precision: the data loader gave no batch")
+        rank = torch.cat(ranks)[:num_samples].cpu()                      # the one read-back
+        out = fold_stats(rank.numpy(), folds)
+        out.update({"n_mismatched": int(n_mismatched), "seed": int(seed), "real": bool(real), "NET_G": cfg.TRAIN.NET_G,
+                    "NET_E": cfg.TRAIN.NET_E})
+        with open('%s/r_precision.json' % save_dir, 'w') as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+        print("R-precision (%s images, %d queries, %d mismatched): %.4f, folds %.4f +- %.4f -> %s/r_precision.json"
+              % ("real" if real else "generated", out["n"], n_mismatched, out["r_precision"], out["mean"], out["std"], save_dir))
+        if return_codes:
+            k = rank.numel()
+            return out, {"code": torch.cat(codes)[:k].cpu(), "pos": torch.cat(poss)[:k].cpu(), "idx": torch.cat(idxs)[:k],
+                         "rank": rank, "bank": bank.bank.cpu()}
+        return out
+
     def sample(self, split_dir, num_samples=25, draw_bbox=False):
         """trainer.py:474-579 (what main.py:158 runs for B_VALIDATION): for the first `num_samples` batches of an
         eval-mode loader take the FIRST sample of the sorted batch, generate nine 256x256 images for its caption /

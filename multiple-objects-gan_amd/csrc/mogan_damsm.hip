@@ -569,6 +569,53 @@ __global__ __launch_bounds__(NT2) void damsm_sent_bwd_text_kernel(const float* _
     }
 }
 
+// ---------------------------------------------------------------------------------------------- R-precision ranking
+// score[q, r] = <code_q, cand_r> / max(|code_q| |cand_r|, eps), cand_0 = pos[q], cand_r = bank[idx[q, r - 1]]; rank[q] = number of
+// r >= 1 with score[q, r] > score[q, 0].  Block per query, wave per candidate stripe as in damsm_sent_fwd_kernel.  EVERY candidate,
+// the match included, runs through the one loop body below (only its row pointer differs), so two candidates with the same bits get
+// the same score bits whichever wave or stripe they fall to: the tie rule (a tie counts for the match) rests on that.
+constexpr int RANK_MAX = 1023;    // mismatched candidates per query: RANK_MAX + 1 scores = 4 KiB of LDS
+__global__ __launch_bounds__(NT2) void retrieval_rank_kernel(const float* __restrict__ code, const float* __restrict__ pos,
+                                                            const float* __restrict__ bank, const int32_t* __restrict__ idx,
+                                                            int Rn, int C, int N, float eps, float* __restrict__ score,
+                                                            int32_t* __restrict__ rank) {
+    __shared__ float sc[RANK_MAX + 1];
+    __shared__ float n0s;
+    __shared__ int cnt[NT2 / 64];
+    const int q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* xb = code + (size_t)q * C;
+    if (wave == 0) {                                          // the query's norm, once per block
+        float n0 = 0.f;
+        for (int c = lane; c < C; c += 64) n0 = fmaf(xb[c], xb[c], n0);
+        n0 = sqrtf(wave_sum(n0));
+        if (lane == 0) n0s = n0;
+    }
+    __syncthreads();
+    const float n0 = n0s;
+    const int32_t* iq = idx + (size_t)q * Rn;
+    for (int r = wave; r <= Rn; r += NT2 / 64) {
+        const float* cr = pos + (size_t)q * C;
+        if (r > 0) cr = bank + (size_t)min(max(iq[r - 1], 0), N - 1) * C;
+        float d = 0.f, n1 = 0.f;
+        for (int c = lane; c < C; c += 64) { const float v = cr[c]; d = fmaf(xb[c], v, d); n1 = fmaf(v, v, n1); }
+        d = wave_sum(d); n1 = sqrtf(wave_sum(n1));
+        const float s = d / fmaxf(n0 * n1, eps);
+        if (lane == 0) {
+            sc[r] = s;
+            if (score) score[(size_t)q * (Rn + 1) + r] = s;
+        }
+    }
+    __syncthreads();
+    const float s0 = sc[0];
+    int above = 0;
+    for (int r = 1 + (int)threadIdx.x; r <= Rn; r += NT2) above += sc[r] > s0 ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o, 64);
+    if (lane == 0) cnt[wave] = above;
+    __syncthreads();
+    if (threadIdx.x == 0) rank[q] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
 // out[0] = sum_k w[k] * (*in[k])  (k < n <= 8): sums of 0-dim loss terms without a chain of scalar launches
 struct ScalarSumP { const float* in[8]; float w[8]; int n; };
 __global__ void scalar_sum_kernel(ScalarSumP p, float* __restrict__ out) {
@@ -669,6 +716,15 @@ int mogan_damsm_sent_bwd_text(const float* cnn, const float* rnn, const float* d
     if (B <= 0 || Bc <= 0 || C <= 0 || (size_t)B * 2 * sizeof(float) > 64 * 1024) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(damsm_sent_bwd_text_kernel, dim3(Bc), dim3(NT2), (size_t)B * 2 * sizeof(float), stream, cnn, rnn, dsim, B,
                        Bc, C, gamma3, eps, drnn);
+    return ok_launch();
+}
+
+int mogan_retrieval_rank(const float* code, const float* pos, const float* bank, const int32_t* idx, int Q, int Rn, int C,
+                         long long N, float eps, float* score, int32_t* rank, hipStream_t stream) {
+    if (!code || !pos || !bank || !idx || !rank) return MOGAN_ERR_SHAPE;
+    if (Q <= 0 || Rn <= 0 || C <= 0 || N <= 0 || Rn > RANK_MAX || N > 2147483647LL) return MOGAN_ERR_SHAPE;
+    hipLaunchKernelGGL(retrieval_rank_kernel, dim3(Q), dim3(NT2), 0, stream, code, pos, bank, idx, Rn, C, (int)N, eps, score,
+                       rank);
     return ok_launch();
 }
 

@@ -1721,6 +1721,35 @@ def damsm_sent(cnn, rnn, labels, mask, gamma3, eps=1e-8):
     return DamsmSentFn.apply(cnn, rnn, labels, mask, float(gamma3), float(eps))
 
 
+def retrieval_rank(code, pos, bank, idx, eps=1e-8, want_scores=False):
+    """R-precision ranking in ONE launch (mogan_retrieval_rank): for every query q the cosine of the image code code[q] (Q, C) with
+    its own sentence code pos[q] (candidate 0) and with the bank rows idx[q, :] (Q, Rn) of bank (N, C); rank[q] (int32) = how many
+    mismatched candidates score strictly higher than the match (0 = retrieved first; a tie counts for the match).  No gradient.
+    idx: an int32 device tensor (entries outside [0, N) are clamped by the kernel), or a host array (numpy), which is checked
+    against [0, N) here -- IndexError -- and uploaded.  Returns rank, or (rank, score (Q, Rn + 1)) with want_scores."""
+    import numpy as np
+    code, pos, bank = _c(code.detach()), _c(pos.detach()), _c(bank.detach())
+    if code.dim() != 2 or pos.shape != code.shape or bank.dim() != 2 or bank.shape[1] != code.shape[1]:
+        raise ValueError("retrieval_rank: code (Q, C), pos (Q, C), bank (N, C) expected, got %s, %s, %s"
+                         % (tuple(code.shape), tuple(pos.shape), tuple(bank.shape)))
+    Q, C, N = code.shape[0], code.shape[1], bank.shape[0]
+    if isinstance(idx, np.ndarray):
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= N):
+            raise IndexError("retrieval_rank: idx holds rows outside [0, %d): min %d, max %d" % (N, idx.min(), idx.max()))
+        ptr(code)                                            # (a host tensor raises here, before anything is uploaded)
+        idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(code.device)
+    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != Q:
+        raise ValueError("retrieval_rank: idx must be int32 (Q, Rn), got %s %s" % (idx.dtype, tuple(idx.shape)))
+    if not (pos.device == bank.device == idx.device == code.device):
+        raise ValueError("retrieval_rank: code, pos, bank and idx must be on one device")
+    idx = idx if idx.is_contiguous() else idx.contiguous()
+    rank = torch.empty((Q,), dtype=torch.int32, device=code.device)
+    score = torch.empty((Q, idx.shape[1] + 1), dtype=torch.float32, device=code.device) if want_scores else None
+    call("mogan_retrieval_rank", ptr(code), ptr(pos), ptr(bank), ptr(idx), Q, idx.shape[1], C, N, float(eps), ptr(score),
+         ptr(rank), stream_ptr())
+    return (rank, score) if want_scores else rank
+
+
 class ScalarSumFn(torch.autograd.Function):
     """sum_k w_k * x_k over up to 8 zero-dim device scalars in ONE launch (forward) / one launch (backward): the loss sums
     of miscc/losses.py:169-174,203,221 and trainer.py:330 otherwise cost a chain of 0-dim aten kernels each way."""
