@@ -5,6 +5,7 @@ autograd tape; all arithmetic on tensors happens inside the HIP kernels.  Every 
 (MoganHipError) if the library is missing or an input is not on the GPU -- there is no fallback.
 """
 import contextlib
+import ctypes
 import os
 
 import torch
@@ -324,34 +325,75 @@ def invalidate_all_packs():
     _PK_GLOBAL[0] += 1
 
 
+class WeightImage:
+    """ONE derived device buffer of one weight -- a packed panel, a prepared filter image or the K of an up-convolution:
+    `buf` was built from weight version `version` in global epoch `epoch` on stream `stream` (raw handle), `captured` = inside a
+    hipGraph capture; `event` was recorded right behind the build.  `geom` = (stride, ph, pw) of a packed panel, else None."""
+    __slots__ = ("buf", "version", "epoch", "event", "stream", "captured", "geom")
+
+    def __init__(self, buf, geom=None):
+        self.buf, self.geom = buf, geom
+        self.version = self.epoch = -1
+        self.event = self.stream = None
+        self.captured = False
+
+    def invalidate(self):
+        self.version = -1
+
+    def ready(self, cell):
+        """False: stale, older than the weight version cell[0] or than the global epoch -- the caller rebuilds the buffer on the
+        current stream (no wait follows).  True: current, and ordered before a use on the current stream"""
+        if self.version != cell[0] or self.epoch != _PK_GLOBAL[0]:
+            return False
+        if self.stream != stream_ptr() and (self.captured or not lib._capturing()):
+            # built on another stream: order behind that build (a capturing stream must not wait for an event recorded
+            # outside its capture -- and need not: the device is synchronised before a capture begins)
+            torch.cuda.current_stream().wait_event(self.event)
+        return True
+
+
+def _stamp(st, built):
+    """the launch just queued on the current stream (handle `st`) built the images of `built`, (WeightImage, version cell)
+    pairs: they are current now, and ONE event orders their uses on other streams behind it"""
+    ev = torch.cuda.Event()
+    ev.record()
+    cap = bool(lib._capturing())
+    for im, cell in built:
+        im.version, im.epoch, im.event, im.stream, im.captured = cell[0], _PK_GLOBAL[0], ev, st, cap
+
+
+def _group_args(n, pointers, ints):
+    """the array arguments of a grouped launch with n members: a void* array per list of `pointers`, an int array per list of `ints`"""
+    VP, CI = ctypes.c_void_p * n, ctypes.c_int * n
+    return [ctypes.cast(VP(*v), ctypes.c_void_p) for v in pointers] + [ctypes.cast(CI(*v), ctypes.c_void_p) for v in ints]
+
+
 class WeightPacks:
-    """Packed copies of ONE convolution weight: slot[dgrad] = [buffer, version, global epoch, geometry, event, stream,
-    packed inside a hipGraph capture]."""
+    """The derived images of ONE convolution weight, a WeightImage each, kept current by the weight's owner (version cell)."""
 
     def __init__(self, w, version_cell=None):
         self.w = w
         self.cell = version_cell if version_cell is not None else [0]
+        # packed panels of the deep layers: slots[dgrad], geom = the convolution geometry they were packed for;
+        # elig[(dgrad, geometry)] = does the call take the packed kernels
         self.slots = {}
         self.elig = {}
-        # prepared Winograd filter images (round 6; include/mogan_hip.h "Prepared filter images"): wino[dgrad] = [buffer, version,
-        # global epoch, event, stream, prepared inside a capture]; wbytes[(dgrad, geometry)] = image size, 0 = not a Winograd layer
+        # prepared filter images (include/mogan_hip.h "Prepared filter images"): wino[dgrad]; wbytes[(dgrad, geometry)] = image
+        # size, 0 = the geometry takes a kernel without one
         self.wino = {}
         self.wbytes = {}
-        # upsample + conv3x3 as the transposed 4x4 s2 convolution (mogan_upconv3x3_*): the virtual filters K = T w T^t of this weight
-        # version, [buffer (Cin, Cout, 4, 4), version, global epoch, event, stream, built inside a capture], and a child WeightPacks
-        # over K (same version cell) that holds the filter images of the kernels running the virtual convolution
+        # upsample + conv3x3 as the transposed 4x4 s2 convolution (mogan_upconv3x3_*): k4 = the virtual filters K = T w T^t of this
+        # weight version (buf: (Cin, Cout, 4, 4)), and k4pk = a child WeightPacks over K (same version cell) that holds the
+        # filter images of the kernels running the virtual convolution
         self.k4 = None
         self.k4pk = None
 
     def _pack(self, dgrad, slot):
         Cout, Cin, KH, KW = self.w.shape
         st = stream_ptr()
-        stride, ph, pw = slot[3]
-        call("mogan_pk_weight_pack", ptr(self.w), slot[0].data_ptr(), Cout, Cin, KH, KW, stride, ph, pw, dgrad, st)
-        slot[1], slot[2] = self.cell[0], _PK_GLOBAL[0]
-        ev = torch.cuda.Event()
-        ev.record()
-        slot[4], slot[5], slot[6] = ev, st, bool(lib._capturing())
+        stride, ph, pw = slot.geom
+        call("mogan_pk_weight_pack", ptr(self.w), slot.buf.data_ptr(), Cout, Cin, KH, KW, stride, ph, pw, dgrad, st)
+        _stamp(st, [(slot, self.cell)])
         PK_STATS["packs"] += 1
 
     def repack(self):
@@ -359,87 +401,15 @@ class WeightPacks:
         read of the master where both are in use (mogan_pk_weight_pack_both)"""
         s0, s1 = self.slots.get(0), self.slots.get(1)
         Cout, Cin, KH, KW = self.w.shape
-        if s0 is not None and s1 is not None and s0[3] == s1[3] and Cin % 32 == 0 and Cout % 32 == 0:
-            stride, ph, pw = s0[3]
+        if s0 is not None and s1 is not None and s0.geom == s1.geom and Cin % 32 == 0 and Cout % 32 == 0:
+            stride, ph, pw = s0.geom
             st = stream_ptr()
-            call("mogan_pk_weight_pack_both", ptr(self.w), s0[0].data_ptr(), s1[0].data_ptr(), Cout, Cin, KH, KW, stride, ph, pw, st)
-            ev = torch.cuda.Event()
-            ev.record()
-            cap = bool(lib._capturing())
-            for slot in (s0, s1):
-                slot[1], slot[2], slot[4], slot[5], slot[6] = self.cell[0], _PK_GLOBAL[0], ev, st, cap
+            call("mogan_pk_weight_pack_both", ptr(self.w), s0.buf.data_ptr(), s1.buf.data_ptr(), Cout, Cin, KH, KW, stride, ph, pw, st)
+            _stamp(st, [(s0, self.cell), (s1, self.cell)])
             PK_STATS["packs"] += 1
             return
         for dgrad, slot in self.slots.items():
             self._pack(dgrad, slot)
-
-    # -- Winograd images -------------------------------------------------------------------------------------------------
-    def wino_stale(self):
-        """(dgrad, slot) of every image in use that is older than the weight"""
-        return [(d, sl) for d, sl in self.wino.items() if sl[1] != self.cell[0] or sl[2] != _PK_GLOBAL[0]]
-
-    def _wino_mark(self, sl, ev, st, cap):
-        sl[1], sl[2], sl[3], sl[4], sl[5] = self.cell[0], _PK_GLOBAL[0], ev, st, cap
-
-    def wino_pointer(self, dgrad, B, Hs, Ws, stride, ph, pw, up):
-        """device pointer of this weight's prepared filter image for the direction, current and ordered before a use on the
-        current stream -- or None: the convolution takes a kernel without one (or the library is a native-fp32 build).  The kind
-        of image follows the filter size: the Winograd kernels' for 3x3 s1, dconv2_fwd_kernel's for 4x4 s2 (mogan_conv_prep_bytes)"""
-        key = (dgrad, B, Hs, Ws, stride, ph, pw, up)
-        nb = self.wbytes.get(key)
-        if nb is None:
-            Cout, Cin, KH, KW = self.w.shape
-            nb = self.wbytes[key] = int(lib.load().mogan_conv_prep_bytes(B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, dgrad))
-        if not nb:
-            return None
-        sl = self.wino.get(dgrad)
-        if sl is None or sl[0].numel() < nb:
-            sl = self.wino[dgrad] = [torch.empty(nb, dtype=torch.uint8, device=self.w.device), -1, -1, None, None, False]
-        if sl[1] != self.cell[0] or sl[2] != _PK_GLOBAL[0]:
-            wino_prep([(self, dgrad, sl)])
-        elif sl[4] != stream_ptr() and (sl[5] or not lib._capturing()):
-            torch.cuda.current_stream().wait_event(sl[3])
-        return sl[0].data_ptr()
-
-    # -- K of the up-convolution --------------------------------------------------------------------------------------------
-    def k4_stale(self):
-        return self.k4 is not None and (self.k4[1] != self.cell[0] or self.k4[2] != _PK_GLOBAL[0])
-
-    def k4_build(self):
-        """K = T w T^t of the current weight on the current stream (one launch)"""
-        Cout, Cin = int(self.w.shape[0]), int(self.w.shape[1])
-        st = stream_ptr()
-        call("mogan_upconv3x3_k4", ptr(self.w), self.k4[0].data_ptr(), Cout, Cin, st)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.k4[1], self.k4[2], self.k4[3], self.k4[4], self.k4[5] = self.cell[0], _PK_GLOBAL[0], ev, st, bool(lib._capturing())
-        PK_STATS["k4_builds"] = PK_STATS.get("k4_builds", 0) + 1
-
-    def upconv_pointers(self, dgrad, B, Hs, Ws):
-        """(K pointer, filter-image pointer or None) for the up-convolution of an (B, Cin, Hs, Ws) input with this 3x3 weight:
-        direction 0 (forward) runs the DATA GRADIENT of the virtual 4x4 s2 convolution C4 (in = Cout, out = Cin) on 2Hs x 2Ws,
-        direction 1 its forward.  Both current and ordered before a use on the current stream."""
-        Cout, Cin = int(self.w.shape[0]), int(self.w.shape[1])
-        if self.k4 is None:
-            k = torch.empty((Cin, Cout, 4, 4), dtype=torch.float32, device=self.w.device)
-            self.k4 = [k, -1, -1, None, None, False]
-            self.k4pk = WeightPacks(k, self.cell)
-        if self.k4_stale():
-            self.k4_build()
-        elif self.k4[4] != stream_ptr() and (self.k4[5] or not lib._capturing()):
-            torch.cuda.current_stream().wait_event(self.k4[3])
-        img = self.k4pk.wino_pointer(0 if dgrad else 1, B, 2 * Hs, 2 * Ws, 2, 1, 1, 0) if D2_PREP else None
-        return self.k4[0].data_ptr(), img
-
-    def _fresh(self, key, slot):
-        """make the copy in `slot` current for a use on the current stream"""
-        if slot[1] != self.cell[0] or slot[2] != _PK_GLOBAL[0]:
-            self._pack(key, slot)
-        elif slot[5] != stream_ptr() and (slot[6] or not lib._capturing()):
-            # packed on another stream: order behind that pack (a capturing stream must not wait for an event recorded
-            # outside its capture -- and need not: the device is synchronised before a capture begins)
-            torch.cuda.current_stream().wait_event(slot[4])
-        return slot[0].data_ptr()
 
     def pointer(self, dgrad, B, Hs, Ws, stride, ph, pw):
         """device pointer of the packed copy for this call's geometry, or None: take the unpacked kernels"""
@@ -454,69 +424,101 @@ class WeightPacks:
         if slot is None:
             nbytes = int(lib.load().mogan_pk_weight_bytes(Cout, Cin, KH, KW, stride, dgrad))
             buf = torch.empty(nbytes, dtype=torch.uint8, device=self.w.device)
-            slot = self.slots[dgrad] = [buf, -1, -1, (stride, ph, pw), None, None, False]
-        elif slot[3] != (stride, ph, pw):
+            slot = self.slots[dgrad] = WeightImage(buf, (stride, ph, pw))
+        elif slot.geom != (stride, ph, pw):
             return None                                   # one weight, two convolution geometries: not a case of the step
-        return self._fresh(dgrad, slot)
+        if not slot.ready(self.cell):
+            self._pack(dgrad, slot)
+        return slot.buf.data_ptr()
+
+    def wino_pointer(self, dgrad, B, Hs, Ws, stride, ph, pw, up):
+        """device pointer of this weight's prepared filter image for the direction, current and ordered before a use on the
+        current stream -- or None: the convolution takes a kernel without one (or the library is a native-fp32 build).  The kind
+        of image follows the filter size: the Winograd kernels' for 3x3 s1, dconv2_fwd_kernel's for 4x4 s2 (mogan_conv_prep_bytes)"""
+        key = (dgrad, B, Hs, Ws, stride, ph, pw, up)
+        nb = self.wbytes.get(key)
+        if nb is None:
+            Cout, Cin, KH, KW = self.w.shape
+            nb = self.wbytes[key] = int(lib.load().mogan_conv_prep_bytes(B, Cin, Hs, Ws, Cout, KH, KW, stride, ph, pw, up, dgrad))
+        if not nb:
+            return None
+        im = self.wino.get(dgrad)
+        if im is None or im.buf.numel() < nb:
+            im = self.wino[dgrad] = WeightImage(torch.empty(nb, dtype=torch.uint8, device=self.w.device))
+        if not im.ready(self.cell):
+            wino_prep([(self, dgrad, im)])
+        return im.buf.data_ptr()
+
+    def k4_build(self):
+        """K = T w T^t of the current weight on the current stream (one launch)"""
+        Cout, Cin = int(self.w.shape[0]), int(self.w.shape[1])
+        st = stream_ptr()
+        call("mogan_upconv3x3_k4", ptr(self.w), self.k4.buf.data_ptr(), Cout, Cin, st)
+        _stamp(st, [(self.k4, self.cell)])
+        PK_STATS["k4_builds"] = PK_STATS.get("k4_builds", 0) + 1
+
+    def upconv_pointers(self, dgrad, B, Hs, Ws):
+        """(K pointer, filter-image pointer or None) for the up-convolution of an (B, Cin, Hs, Ws) input with this 3x3 weight:
+        direction 0 (forward) runs the DATA GRADIENT of the virtual 4x4 s2 convolution C4 (in = Cout, out = Cin) on 2Hs x 2Ws,
+        direction 1 its forward.  Both current and ordered before a use on the current stream."""
+        if self.k4 is None:
+            Cout, Cin = int(self.w.shape[0]), int(self.w.shape[1])
+            self.k4 = WeightImage(torch.empty((Cin, Cout, 4, 4), dtype=torch.float32, device=self.w.device))
+            self.k4pk = WeightPacks(self.k4.buf, self.cell)
+        if not self.k4.ready(self.cell):
+            self.k4_build()
+        img = self.k4pk.wino_pointer(0 if dgrad else 1, B, 2 * Hs, 2 * Ws, 2, 1, 1, 0) if D2_PREP else None
+        return self.k4.buf.data_ptr(), img
+
+    def invalidate(self, version_cell):
+        """a new owner's version counter rules from now on: every image is stale"""
+        self.cell = version_cell
+        for im in list(self.slots.values()) + list(self.wino.values()):
+            im.invalidate()
+        if self.k4 is not None:
+            self.k4.invalidate()
+            self.k4pk.invalidate(version_cell)
 
 
 def wino_prep(items):
-    """(WeightPacks, dgrad, slot) triples -> their prepared filter images rebuilt on the current stream in one launch per kind
+    """(WeightPacks, dgrad, image) triples -> their prepared filter images rebuilt on the current stream in one launch per kind
     (mogan_conv_prep_group: the Winograd images of the 3x3 weights, dconv2's images of the 4x4 s2 weights)"""
-    import ctypes
     n = len(items)
     if not n:
         return
-    VP, CI = ctypes.c_void_p * n, ctypes.c_int * n
-    ws = VP(*[it[0].w.data_ptr() for it in items])
-    ps = VP(*[it[2][0].data_ptr() for it in items])
-    co = CI(*[int(it[0].w.shape[0]) for it in items])
-    ci = CI(*[int(it[0].w.shape[1]) for it in items])
-    kh = CI(*[int(it[0].w.shape[2]) for it in items])
-    dg = CI(*[int(it[1]) for it in items])
+    ws = [[pk.w.data_ptr() for pk, _, _ in items], [im.buf.data_ptr() for _, _, im in items]]
+    shapes = [pk.w.shape for pk, _, _ in items]
+    ints = [[s[i] for s in shapes] for i in (0, 1, 2)] + [[int(d) for _, d, _ in items]]        # Cout, Cin, KH, direction
     st = stream_ptr()
-    call("mogan_conv_prep_group", n, ctypes.cast(ws, ctypes.c_void_p), ctypes.cast(ps, ctypes.c_void_p), ctypes.cast(co, ctypes.c_void_p),
-         ctypes.cast(ci, ctypes.c_void_p), ctypes.cast(kh, ctypes.c_void_p), ctypes.cast(dg, ctypes.c_void_p), st)
-    ev = torch.cuda.Event()
-    ev.record()
-    cap = bool(lib._capturing())
-    for pk, _, sl in items:
-        pk._wino_mark(sl, ev, st, cap)
+    call("mogan_conv_prep_group", n, *_group_args(n, ws, ints), st)
+    _stamp(st, [(im, pk.cell) for pk, _, im in items])
     PK_STATS["wino_preps"] = PK_STATS.get("wino_preps", 0) + 1
 
 
 def k4_build_group(pks):
     """K = T w T^t of every pack in `pks` on the current stream in one launch (mogan_upconv3x3_k4_group)"""
-    import ctypes
     n = len(pks)
     if not n:
         return
-    VP, CI = ctypes.c_void_p * n, ctypes.c_int * n
-    ws = VP(*[pk.w.data_ptr() for pk in pks])
-    ks = VP(*[pk.k4[0].data_ptr() for pk in pks])
-    co = CI(*[int(pk.w.shape[0]) for pk in pks])
-    ci = CI(*[int(pk.w.shape[1]) for pk in pks])
+    ws = [[pk.w.data_ptr() for pk in pks], [pk.k4.buf.data_ptr() for pk in pks]]
+    shapes = [pk.w.shape for pk in pks]
     st = stream_ptr()
-    call("mogan_upconv3x3_k4_group", n, ctypes.cast(ws, ctypes.c_void_p), ctypes.cast(ks, ctypes.c_void_p), ctypes.cast(co, ctypes.c_void_p),
-         ctypes.cast(ci, ctypes.c_void_p), st)
-    ev = torch.cuda.Event()
-    ev.record()
-    cap = bool(lib._capturing())
-    for pk in pks:
-        pk.k4[1], pk.k4[2], pk.k4[3], pk.k4[4], pk.k4[5] = pk.cell[0], _PK_GLOBAL[0], ev, st, cap
+    call("mogan_upconv3x3_k4_group", n, *_group_args(n, ws, [[s[i] for s in shapes] for i in (0, 1)]), st)
+    _stamp(st, [(pk.k4, pk.cell) for pk in pks])
     PK_STATS["k4_builds"] = PK_STATS.get("k4_builds", 0) + 1
 
 
 def repack_all(packs):
     """Every derived weight image of a bucket brought up to date on the current stream (the owner changed the weights): the
-    packed panels pack by pack, the Winograd filter images of all of them in one launch."""
+    packed panels pack by pack, the virtual filters of the up-convolutions in one launch, then the prepared filter images of
+    all weights -- those built from the virtual filters among them -- in one launch."""
     items, k4s = [], []
     for pk in packs:
         pk.repack()
-        items += [(pk, d, sl) for d, sl in pk.wino.items()]
+        items += [(pk, d, im) for d, im in pk.wino.items()]
         if pk.k4 is not None:                  # the virtual filters of an up-convolution, then the images built from them
             k4s.append(pk)
-            items += [(pk.k4pk, d, sl) for d, sl in pk.k4pk.wino.items()]
+            items += [(pk.k4pk, d, im) for d, im in pk.k4pk.wino.items()]
     k4_build_group(k4s)
     wino_prep(items)
 
@@ -545,15 +547,7 @@ def attach_packs(w, version_cell=None):
     if pk is None:
         pk = w._mogan_pk = WeightPacks(w, version_cell)
     elif version_cell is not None and pk.cell is not version_cell:
-        # a new owner (a second FlatAdam over the same network): its version counter rules from now on
-        pk.cell = version_cell
-        for slot in list(pk.slots.values()) + list(pk.wino.values()):
-            slot[1] = -1
-        if pk.k4 is not None:
-            pk.k4[1] = -1
-            pk.k4pk.cell = version_cell
-            for slot in pk.k4pk.wino.values():
-                slot[1] = -1
+        pk.invalidate(version_cell)         # a new owner (a second FlatAdam over the same network)
     return pk
 
 
@@ -879,7 +873,7 @@ def deep_block_eligible(x, w, stride, ph, pw, act, groups=1):
         pk = w._mogan_pk
         for d in (0, 1):
             slot = pk.slots.get(d)
-            if slot is not None and slot[3] != (stride, ph, pw):
+            if slot is not None and slot.geom != (stride, ph, pw):
                 return False
     return e
 

@@ -962,7 +962,7 @@ def test_dconv2_prepared_filter_images(case):
     torch.cuda.synchronize()
     ntk = int(bool(nb[0])) + int(bool(nb[1]))
     assert sorted(pk.wino) == [d for d in (0, 1) if nb[d]] and ops.PK_STATS.get("wino_preps", 0) == before + ntk
-    assert all(pk.wino[d][0].numel() >= nb[d] for d in pk.wino)
+    assert all(pk.wino[d].buf.numel() >= nb[d] for d in pk.wino)
     assert torch.equal(y, y_ref) and torch.equal(dx, dx_ref)
     assert torch.equal(ops.conv2d_forward(x, w, 2, 1, 1, 0), y_ref) and ops.PK_STATS.get("wino_preps", 0) == before + ntk
     with torch.no_grad():
@@ -1053,6 +1053,55 @@ def test_prepared_images_of_both_kinds_in_one_call():
         a, b = run(pk.w), run(w * 2.0)
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     assert ops.PK_STATS.get("wino_preps", 0) == n0 + 1
+
+
+@pytest.mark.parametrize("kind, case", [("wino", (2, 96, 16, 32, 192)), ("dconv2", (3, 64, 32, 32, 96)), ("upconv", (2, 192, 16, 16, 96))])
+def test_images_built_on_one_stream_and_used_on_another(kind, case):
+    """The owner builds a weight's images on ITS stream (behind the optimizer step); a convolution on another stream has to be
+    ordered behind that build by the image's event and by nothing else.  Winograd images (both directions), dconv2's images and
+    the K of an up-convolution with its image: built on the default stream and used on a side stream, rebuilt by repack_all on the
+    default stream and used on the side stream with no stream wait in between -- the bits of the same weight without an owner."""
+    B, Cin, H, W, Cout = case
+    k, s, up = {"wino": (3, 1, 0), "dconv2": (4, 2, 0), "upconv": (3, 1, 1)}[kind]
+    OH, OW = (2 * H, 2 * W) if up else (H // s, W // s)
+    x = T("sx%s" % (case,), (B, Cin, H, W)).to(DEV)
+    w0 = T("sw%s" % (case,), (Cout, Cin, k, k), 0.2).to(DEV)
+    g = T("sg%s" % (case,), (B, Cout, OH, OW)).to(DEV)
+
+    def run(wt):
+        return ops.conv2d_forward(x, wt, s, 1, 1, up), ops.conv2d_dgrad(g, wt, x.shape, s, 1, 1, up)
+
+    def builds():
+        return ops.PK_STATS.get("wino_preps", 0), ops.PK_STATS.get("k4_builds", 0)
+
+    ref0, ref1 = run(w0.clone()), run(w0 * -0.5)                  # no owner, default stream: per-call transforms
+    w = w0.clone()
+    pk = ops.attach_packs(w)
+    here = run(w)
+    images = lib.load().mogan_mfma_form() != 1                    # the native-fp32 build has no prepared images
+    if images:
+        assert (pk.k4 is not None and sorted(pk.k4pk.wino) == [0, 1]) if up else sorted(pk.wino) == [0, 1]
+    n = builds()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        there = run(w)
+    assert builds() == n                                          # used, not rebuilt
+    torch.cuda.current_stream().wait_stream(side)                 # (the owner overwrites what the side stream is reading)
+    with torch.no_grad():
+        w.mul_(-0.5)
+    pk.cell[0] += 1
+    ops.repack_all([pk])
+    n = builds()
+    if images or up:                                              # (with no image at all nothing orders the side stream behind w.mul_)
+        with torch.cuda.stream(side):
+            after = run(w)
+        assert builds() == n
+    torch.cuda.synchronize()
+    for got in (here, there):
+        assert torch.equal(got[0], ref0[0]) and torch.equal(got[1], ref0[1])
+    if images or up:
+        assert torch.equal(after[0], ref1[0]) and torch.equal(after[1], ref1[1])
 
 
 
