@@ -1,4 +1,6 @@
 """Parameter holders and the fused nn.Sequential used by model.py / inception.py."""
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -36,6 +38,22 @@ class BNCallCounter:
 
     def hit(self, m):
         self.calls[self.index[id(m)]] += 1
+
+    @contextlib.contextmanager
+    def recording(self):
+        """The calls made inside the block do not count for the step: they go into the list handed out (filled when the block
+        ends) -- what one replay of a hipGraph captured in the block stands for, or nothing (a warm-up that is undone)."""
+        before, made = list(self.calls), []
+        try:
+            yield made
+        finally:
+            made.extend(a - c for a, c in zip(self.calls, before))
+            self.calls = before
+
+    def add(self, made):
+        """a replay happened: count the calls recorded at its capture"""
+        for j, n in enumerate(made):
+            self.calls[j] += n
 
     def flush(self):
         if self._cached != self.calls:                  # first step (or a changed call pattern): eager only

@@ -20,6 +20,7 @@ MI355X-first differences (results identical to the reference's single-GPU step o
   * the whole device part of the step can be captured into one hipGraph (`use_graph=True`) -- the
     step is a few thousand short launches at 4x4..16x16 resolution that are otherwise launch-bound.
 """
+import dataclasses
 import glob
 import logging
 import os
@@ -458,6 +459,130 @@ def create_engine_streams(n_discriminators=3, touch=True):
     return made
 
 
+@dataclasses.dataclass(eq=False)
+class CapturedBranch:
+    """One discriminator branch as hipGraphs of one memory pool: gR = zero_grad + the real half; gU = the fake half up to the
+    finished gradient [+ gA]; gA = Adam, re-pack, the generator-step forward through the updated D_i and its image gradient -- a
+    graph of its own, replayed behind the bucket's all-reduce, under data parallelism only (else None).  errD, g_loss, g_img
+    (= d g_loss_i / d fake_i): the static results, outside the pool; calls: the BatchNorm calls one replay of the branch stands for."""
+    gR: torch.cuda.CUDAGraph
+    gU: torch.cuda.CUDAGraph
+    gA: torch.cuda.CUDAGraph
+    errD: torch.Tensor
+    g_loss: torch.Tensor
+    g_img: torch.Tensor
+    calls: list = None
+
+
+@dataclasses.dataclass(eq=False)
+class CapturedGenerator:
+    """The generator for one shape of the text tensors: gF = its forward on the `static` inputs, fake = the (detached) images it
+    writes.  Forward only (gB None): live = (fake images, mu, logvar) carrying the autograd tape recorded at capture.  With gB =
+    backward + Adam/EMA: errG, kl = that graph's static results.  calls: the BatchNorm calls one step's replays stand for."""
+    gF: torch.cuda.CUDAGraph
+    static: dict
+    gB: torch.cuda.CUDAGraph = None
+    fake: list = None
+    live: tuple = None
+    errG: torch.Tensor = None
+    kl: torch.Tensor = None
+    calls: list = None
+
+
+class EagerBranches:
+    """What the discriminator branches of ONE step execute (TrainEngine.device_step says when, and on which stream), as eager
+    launches.  result(i) = (errD_i, g_loss_i, d g_loss_i / d fake_i) for the generator update: here g_loss_i is live -- its tape
+    leads through D_i to the generator -- and there is no image gradient."""
+    # host order: the heads largest-first, the tails smallest-first behind ALL heads -- the collectives of one process group
+    # execute in issue order, and D64's / D128's all-reduce must not queue behind the event of D256's longer backward
+    UPDATE_BEHIND_FAKE = False
+
+    def __init__(self, eng, real_labels, fake_labels):
+        self.eng, self.labels = eng, (real_labels, fake_labels)
+        self.early, self.errD, self.g_loss = {}, {}, {}
+
+    def real(self, i, b):
+        """zero_grad + the real-image half of D_i's update.  Split form (miscc/losses.split_d_loss; opt-in): the real-image terms
+        of the loss are evaluated AND back-propagated here -- kept: ("split", R, pending running-statistics updates); otherwise
+        only D_i(real) is evaluated and its features are kept (None with the paired pass)."""
+        from .miscc.losses import _call_d, paired
+        eng, D = self.eng, self.eng.netsD[i]
+        eng.optDs[i].zero_grad()
+        if paired(D):                            # D_i(real) rides with D_i(fake) as one [real; fake] pass (losses.D_PAIR)
+            self.early[i] = None
+        elif eng.split_d:
+            errR, pend = discriminator_loss_real(D, b["imgs"][i], b["sent_emb"], **eng._d_kw(i, b))
+            with ops.wgrad_overlap():
+                errR.backward()
+            self.early[i] = ("split", errR.detach(), pend)
+        elif i == 0:
+            self.early[i] = _call_d(D, b["imgs"][i], b["label_one_hot"], b["tm"], b["tmi"])
+        else:
+            self.early[i] = _call_d(D, b["imgs"][i], None, None, None)
+
+    def fake(self, i, b, fake_imgs):
+        """the fake-image half up to the finished gradient (split form: errD_i = R + F), or the whole loss on D_i(real)'s features"""
+        eng, early = self.eng, self.early[i]
+        if isinstance(early, tuple):
+            errD = discriminator_loss_fake(eng.netsD[i], fake_imgs[i], b["sent_emb"], early[2], **eng._d_kw(i, b))
+        else:
+            errD = eng._d_loss(i, b, fake_imgs, *self.labels, early)
+        with ops.wgrad_overlap():
+            errD.backward()
+        self.errD[i] = ops.scalar_sum([early[1], errD.detach()]) if isinstance(early, tuple) else errD.detach()
+
+    def update(self, i, b, fake_imgs):
+        """all-reduce, Adam, then the generator-step forward through the updated D_i"""
+        eng = self.eng
+        eng._opt_step(eng.optDs[i], eng._allreduce_async(eng.optDs[i]))
+        for p in eng.netsD[i].parameters():          # G step: no weight gradients of the Ds
+            p.requires_grad_(False)
+        self.g_loss[i] = generator_d_branch(eng.netsD[i], fake_imgs[i], b["sent_emb"], **eng._d_kw(i, b))
+
+    def result(self, i):
+        return self.errD[i], self.g_loss[i], None
+
+
+class ReplayedBranches:
+    """The same four methods on what the engine captured (TrainEngine._bg): copies into the static inputs and replays of the
+    CapturedBranch of D_i.  The results are clones of the static ones (the branch's next replay rewrites those) and carry no
+    tape: d g_loss_i / d fake_i comes with them."""
+    # host order: each branch issues the rest of its update right behind its gradient (gU, the bucket's all-reduce, gA in one go)
+    UPDATE_BEHIND_FAKE = True
+
+    def __init__(self, eng, bg):
+        self.eng, self.static, self.branches = eng, bg["static"], bg["branches"]
+
+    def real(self, i, b):
+        st = self.static
+        st["imgs"][i].copy_(b["imgs"][i])
+        if i == 0:
+            for k in ("label_one_hot", "tm", "tmi"):
+                st[k].copy_(b[k])
+        if self.eng.split_d:
+            st["sent"][i].copy_(b["sent_emb"])
+        self.branches[i].gR.replay()
+
+    def fake(self, i, b, fake_imgs):
+        self.static["fake"][i].copy_(fake_imgs[i].detach())
+        self.branches[i].gU.replay()
+
+    def update(self, i, b, fake_imgs):
+        eng, br = self.eng, self.branches[i]
+        if br.gA is not None:                          # data parallel: sum the bucket over the ranks, then Adam and the rest
+            red = eng.reducers.get(id(eng.optDs[i]))
+            if red is not None:
+                red.reduce_now()
+            elif not eng._debug_no_ar:
+                allreduce_flat(eng.optDs[i].g, None, eng.comm, eng._bucket_name(eng.optDs[i]))
+            br.gA.replay()
+        eng.bn_counter.add(br.calls)
+
+    def result(self, i):
+        br = self.branches[i]
+        return br.errD.clone(), br.g_loss.clone(), br.g_img
+
+
 class TrainEngine:
     """Device-side state of one rank: networks, flat optimizers, DP communicator, optional hipGraph."""
 
@@ -479,7 +604,6 @@ class TrainEngine:
         # Inception/DAMSM branch) run on side streams so that their many small launches overlap; captured, they
         # become parallel branches of the hipGraph.  MOGAN_STREAMS=0 keeps everything on one stream.
         self.graph_encoder = os.environ.get("MOGAN_GRAPH_ENCODER", "1") != "0" and not use_graph
-        self.early_damsm_bwd = True      # the DAMSM / Inception data gradient does not wait for errG_total.backward()
         self._enc_graphs = {}
         self.multi_stream = os.environ.get("MOGAN_STREAMS", "1") != "0"
         # Branch graphs (single process, multi-stream, not the whole-step graph): every discriminator branch -- D_i(real);
@@ -507,8 +631,16 @@ class TrainEngine:
         gmode = os.environ.get("MOGAN_G_GRAPHS", "2")
         self.g_fwd_only = gmode == "2"
         self.g_graphs = self.branch_graphs and gmode != "0" and (self.g_fwd_only or not self.distributed)
-        self._bg = None
+        self._bg = None                  # what the first replaying step captured: {"B": batch size, "static": input tensors,
+        #                                  "branches": [CapturedBranch per D_i], "G": {text shapes: CapturedGenerator}}
         self._g_refused = set()
+        self._g_cap_stream = None        # capture stream of the generator's forward graph (_g_capture)
+        self._split_target = None        # split-K block target last handed to the library (device_step)
+        self._tx_next = self._tx_ready = self._text_ev = None        # text embeddings one step ahead (prefetch_text)
+        # diagnostics (_phase): `phase_times` = True (tools/phase_times.py) -> device-synchronised wall time per phase in _ph;
+        # MOGAN_CHAIN_EVENTS=1 -> main-stream events at the phase boundaries in _chain (chain_report)
+        self.phase_times, self._ph, self._ph_last, self._ph_name = False, {}, None, None
+        self._chain_events, self._chain = bool(os.environ.get("MOGAN_CHAIN_EVENTS")), []
         if torch.cuda.is_available() and self.multi_stream and not use_graph:
             create_engine_streams(len(netsD))       # (a no-op when the entry point has done it before the process group came up)
         # the discriminator loss in two halves: the real-image terms evaluated and back-propagated ahead of the generator's
@@ -522,7 +654,6 @@ class TrainEngine:
         for i in range(len(netsD))[::-1]:
             ops.precreate_wgrad_stream(self.side[i])
         ops.precreate_wgrad_stream(torch.cuda.current_stream())
-        self.comm_stream = None          # collectives are issued on the branch streams (see _allreduce_async)
         self.comm = CommStats()          # per-bucket all-reduce / exposed time (enabled by bench.py for N > 1)
         self._debug_no_ar = bool(os.environ.get("MOGAN_DEBUG_NO_ALLREDUCE"))   # diagnostic: cost of the collectives' ordering
         if self.distributed and self.world > 1:
@@ -629,74 +760,32 @@ class TrainEngine:
     def _d_kw(self, i, b):
         return dict(local_labels=b["label_one_hot"], transf_matrices=b["tm"], transf_matrices_inv=b["tmi"]) if i == 0 else {}
 
-    def _d_real(self, i, b, sent_emb=None):
-        """zero_grad + the real-image half of D_i's update: independent of the generator, so it runs beside the G forward (and the
-        tail of the previous step).  Split form (miscc/losses.split_d_loss; opt-in, off by default): the real-image terms of the loss are
-        evaluated AND back-propagated here -- returns ("split", R, pending running-statistics updates); otherwise only D_i(real)
-        is evaluated and its features are returned (None with the paired pass)."""
-        from .miscc.losses import _call_d, paired
-        self.optDs[i].zero_grad()
-        if paired(self.netsD[i]):                # D_i(real) rides with D_i(fake) as one [real; fake] pass (losses.D_PAIR)
-            return None
-        if self.split_d:
-            errR, pend = discriminator_loss_real(self.netsD[i], b["imgs"][i], b["sent_emb"] if sent_emb is None else sent_emb,
-                                                 **self._d_kw(i, b))
-            with ops.wgrad_overlap():
-                errR.backward()
-            return ("split", errR.detach(), pend)
-        if i == 0:
-            return _call_d(self.netsD[i], b["imgs"][i], b["label_one_hot"], b["tm"], b["tmi"])
-        return _call_d(self.netsD[i], b["imgs"][i], None, None, None)
-
-    def _d_fake(self, i, b, fake_imgs, early, sent_emb=None):
-        """the fake-image half (split form): F, its backward; returns errD_i = R + F (detached)"""
-        _, errR, pend = early
-        errF = discriminator_loss_fake(self.netsD[i], fake_imgs[i], b["sent_emb"] if sent_emb is None else sent_emb, pend,
-                                       **self._d_kw(i, b))
-        with ops.wgrad_overlap():
-            errF.backward()
-        return ops.scalar_sum([errR, errF.detach()])
-
     def _d_loss(self, i, b, fake_imgs, real_labels, fake_labels, real_features=None):
-        kw = dict(local_labels=b["label_one_hot"], transf_matrices=b["tm"],
-                  transf_matrices_inv=b["tmi"]) if i == 0 else {}
         return discriminator_loss(self.netsD[i], b["imgs"][i], fake_imgs[i], b["sent_emb"], real_labels,
-                                  fake_labels, None, real_features=real_features, **kw)
-
-    def _d_update(self, i, b, fake_imgs, real_labels, fake_labels, real_features=None):
-        """[zero_grad,] loss, backward, (all-reduce,) Adam of D_i on the current stream."""
-        if real_features is None:
-            self.optDs[i].zero_grad()
-        errD = self._d_loss(i, b, fake_imgs, real_labels, fake_labels, real_features)
-        with ops.wgrad_overlap():
-            errD.backward()
-        self._opt_step(self.optDs[i], self._allreduce_async(self.optDs[i]))
-        return errD.detach()
+                                  fake_labels, None, real_features=real_features, **self._d_kw(i, b))
 
     # -- the reference loop body -------------------------------------------------------------------
     def _phase(self, name):
-        """MOGAN_PHASE_TIMES=1: device-synchronised wall time per phase of the step (diagnostic; serialises the phases).
-        MOGAN_CHAIN_EVENTS=1: an event on the MAIN stream at every phase boundary instead (no synchronisation, the step runs
-        as usual); chain_report() turns them into the time the main stream -- the generator's dependency chain -- spent in
-        each phase, waits for the side branches included."""
-        if os.environ.get("MOGAN_CHAIN_EVENTS"):
+        """`phase_times` = True: device-synchronised wall time per phase of the step (diagnostic; serialises the phases).
+        MOGAN_CHAIN_EVENTS=1 (read at construction): an event on the MAIN stream at every phase boundary instead (no
+        synchronisation, the step runs as usual); chain_report() turns them into the time the main stream -- the generator's
+        dependency chain -- spent in each phase, waits for the side branches included."""
+        if self._chain_events:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
-            self._chain = getattr(self, "_chain", [])
             self._chain.append((name, ev))
             return
-        if not getattr(self, "phase_times", False):       # (diagnostic attribute, tools/phase_times.py: host-synchronised phase times)
+        if not self.phase_times:
             return
         torch.cuda.synchronize()
         now = time.perf_counter()
-        if getattr(self, "_ph_last", None) is not None:
-            self._ph = getattr(self, "_ph", {})
+        if self._ph_last is not None:
             self._ph[self._ph_name] = self._ph.get(self._ph_name, 0.0) + (now - self._ph_last) * 1e3
         self._ph_last, self._ph_name = now, name
 
     def chain_report(self, skip=5):
         """mean milliseconds between consecutive MOGAN_CHAIN_EVENTS events over the recorded steps (after `skip` steps)"""
-        ch = getattr(self, "_chain", [])
+        ch = self._chain
         torch.cuda.synchronize()
         names = []
         for n, _ in ch:
@@ -717,123 +806,111 @@ class TrainEngine:
 
     def device_step(self, b):
         """trainer.py:291-342 given the text embeddings; `b` holds device tensors:
-        imgs[3], z, eps, words_embs, sent_emb, mask, cap_lens, tm, tmi, label_one_hot."""
-        netG, netsD = self.netG, self.netsD
+        imgs[3], z, eps, words_embs, sent_emb, mask, cap_lens, tm, tmi, label_one_hot.
+        The one statement of the step's schedule.  Side by side: fork the real halves of the D updates onto their streams; text;
+        generator forward; D256's branch; the Inception/DAMSM branch; D128's and D64's; next batch's text; join; generator update;
+        logs -- eager or with the branches (and the generator) replayed.  On one stream: the reference loop body."""
+        netsD, nD = self.netsD, len(self.netsD)
         B = b["z"].shape[0]
-        from ..hip import lib
         # split-K block target of this engine's streams (per stream, include/mogan_hip.h): 384 when the branches run side by
         # side, 768 when one stream has the GPU to itself
         target = int(os.environ.get("MOGAN_SPLIT_TARGET", 384 if self.multi_stream else 768))
-        if getattr(self, "_split_target", None) != target:
+        if self._split_target != target:
             self._split_target = target
-            from ..hip import ops as _ops
-            streams = [torch.cuda.current_stream()] + list(self.side)
-            streams += [_ops._wgrad_streams[s.cuda_stream] for s in streams if s.cuda_stream in _ops._wgrad_streams]
             # streams this engine does not own (torch's internal capture stream of the encoder graph) follow the default
+            from ..hip import lib
             lib.call("mogan_gemm_set_split_target", target)
         real_labels = b["z"].new_ones(B)
         fake_labels = b["z"].new_zeros(B)
         match_labels = b["match_labels"]
-        real_feat = {}
-        if self.branch_graphs and (self._bg is None or self._bg["B"] == B):     # (a ragged last batch runs eagerly)
-            return self._branch_graph_step(b, real_labels, fake_labels, match_labels)
-        if self.multi_stream:
-            # D_i(real) depends neither on the generator nor on the text encoder: it runs beside them.  With an
-            # `inputs_ready` event (recorded by the caller once the batch tensors are on the device) the D branches
-            # do not even wait for the main stream, i.e. they also overlap the tail of the previous step (G backward,
-            # Adam): only their own stream order (D_i's previous Adam) and the input batch matter.
-            cur0 = torch.cuda.current_stream()
+        replayed = self.branch_graphs and (self._bg is None or self._bg["B"] == B)     # (a ragged last batch runs eagerly)
+        if replayed and self._bg is None:
+            self._bg_first_use(b)
+        cur = torch.cuda.current_stream()
+        out, parts = {}, {}
+        gg = damsm_grad = None           # the captured generator variant in use / the DAMSM branch's image gradient
+        # (captured branches live on their streams whatever `multi_stream` says at the moment)
+        side_by_side = self.multi_stream or replayed
+        if side_by_side:
+            # What a discriminator branch executes: eager launches, or copies into static buffers and graph replays.
+            run = ReplayedBranches(self, self._bg) if replayed else EagerBranches(self, real_labels, fake_labels)
+            # The real half of D_i's update depends neither on the generator nor on the text encoder (split form: on the
+            # sentence embedding): it runs beside them.  With an `inputs_ready` event (recorded by the caller once the batch
+            # tensors are on the device) the D branches do not even wait for the main stream, i.e. they also overlap the tail
+            # of the previous step (G backward, Adam): only their own stream order (D_i's previous Adam) and the input batch matter.
             ready = b.get("inputs_ready")
             text_ev = self._text_first(b, ready) if self.split_d else None     # (the real half needs the sentence embedding)
-            for i in range(len(netsD))[::-1]:
+            for i in range(nD)[::-1]:
+                s = self.side[i]
                 if ready is not None:
-                    self.side[i].wait_event(ready)
+                    s.wait_event(ready)
                     if text_ev is not None:
-                        self.side[i].wait_event(text_ev)
+                        s.wait_event(text_ev)
                 else:
-                    self.side[i].wait_stream(cur0)
-                with torch.cuda.stream(self.side[i]):
-                    real_feat[i] = self._d_real(i, b)
+                    s.wait_stream(cur)
+                with torch.cuda.stream(s):
+                    run.real(i, b)
             if ready is not None:
-                cur0.wait_event(ready)
+                cur.wait_event(ready)
         self._phase("text+Gfwd")
-        if "words_embs" not in b:        # trainer.py:281-289 (eager path: after the fork above)
+        if "words_embs" not in b:        # trainer.py:281-289 (behind the fork above)
             b["words_embs"], b["sent_emb"], b["mask"] = self._text_for(b)
-        fake_imgs, _, mu, logvar = netG(b["z"], b["sent_emb"], b["words_embs"], b["mask"], b["tmi"],
-                                        b["label_one_hot"], b.get("eps"))
-        out = {}
-        # The three D updates are independent of each other (own parameters, own fake image), so they run
-        # largest-first: D256's 643 MB gradient all-reduce then overlaps the D128 and D64 forward/backward and
-        # each optimizer step waits only for its own bucket.  Same results as the reference order 0,1,2.
-        order = list(range(len(netsD)))[::-1]
-        cur = torch.cuda.current_stream()
-        nD = len(netsD)
-        if self.multi_stream:
-            # One branch per discriminator: its update (zero_grad, loss, backward, all-reduce, Adam) and then -- on the
-            # same stream, hence behind its own Adam and independent of the other Ds -- the G-step forward through it.
-            # The Inception/DAMSM branch only needs the fake image, so it starts right after D256's branch was queued
-            # and overlaps the D updates (and, for N>1, D256's 643 MB gradient all-reduce).  The branches meet again
-            # where the generator loss is summed; autograd replays each branch's backward on its own stream.
-            parts = {}
-
-            def d_head(i):          # D_i: loss on (real, fake), backward -- up to the point where the gradient is complete
+        if replayed:
+            # the sentence embedding the captured graphs read (main stream; the branches wait for it below).  .data: the copy must
+            # not move the version counter of a tensor the forward-only generator graph's autograd tape has saved
+            self._bg["static"]["sent_emb"].data.copy_(b["sent_emb"])
+            gg = self._g_graph_for(b)
+        fake_imgs, mu, logvar = self._g_forward(b, gg)
+        if side_by_side:
+            # One branch per discriminator: its update (loss, backward, all-reduce, Adam) and then -- on the same stream, hence
+            # behind its own Adam and independent of the other Ds -- the G-step forward through it.  The three updates are
+            # independent of each other (own parameters, own fake image), so they run largest-first: D256's 643 MB gradient
+            # all-reduce then overlaps the D128 and D64 forward/backward and each optimizer step waits only for its own
+            # bucket.  Same results as the reference order 0,1,2.  The Inception/DAMSM branch only needs the fake image, so it
+            # starts right after D256's branch was queued and overlaps the D updates.  The branches meet again where the
+            # generator loss is summed.
+            def head(i):            # D_i up to the point where its gradient is complete [+ the rest of the branch]
                 s = self.side[i]
                 s.wait_stream(cur)
                 with torch.cuda.stream(s):
-                    early = real_feat.get(i)
-                    if isinstance(early, tuple):
-                        out["errD%d" % i] = self._d_fake(i, b, fake_imgs, early)
-                    else:
-                        errD = self._d_loss(i, b, fake_imgs, real_labels, fake_labels, early)
-                        with ops.wgrad_overlap():
-                            errD.backward()
-                        out["errD%d" % i] = errD.detach()
+                    run.fake(i, b, fake_imgs)
+                    if run.UPDATE_BEHIND_FAKE:
+                        run.update(i, b, fake_imgs)
 
-            def d_tail(i):          # all-reduce, Adam, then the G-step forward through the updated D_i
-                with torch.cuda.stream(self.side[i]):
-                    self._opt_step(self.optDs[i], self._allreduce_async(self.optDs[i]))
-                    for p in netsD[i].parameters():          # G step: no weight gradients of the Ds
-                        p.requires_grad_(False)
-                    kw = dict(local_labels=b["label_one_hot"], transf_matrices=b["tm"],
-                              transf_matrices_inv=b["tmi"]) if i == 0 else {}
-                    parts["g_loss%d" % i] = generator_d_branch(netsD[i], fake_imgs[i], b["sent_emb"], **kw)
-
-            # host order: the largest D first (its work starts early), the Inception/DAMSM branch right behind it; the
-            # tails smallest-first -- the collectives of one process group execute in issue order, and D64's / D128's
-            # all-reduce must not queue behind the event of D256's longer backward
             self._phase("D heads + Inception")
-            d_head(order[0])
+            head(nD - 1)
             s = self.side[nD]
             s.wait_stream(cur)
-            damsm_grad = None
             with torch.cuda.stream(s):
                 # The DAMSM terms depend on the fake image and the frozen encoders only -- not on the Ds -- so their
                 # backward (Inception data gradient, ~6 ms of short launches) does not have to wait for errG_total:
                 # it runs here, beside the D updates, on a detached leaf; its image gradient joins the generator's
                 # backward below as a second root (d errG / d img256 = D256 path + this; two terms, same sum).
-                img = fake_imgs[nD - 1]
-                if self.early_damsm_bwd:
-                    img = img.detach().requires_grad_(True)
-                w_loss, s_loss = generator_damsm_branch(
-                    self._encoder(img), img, b["words_embs"], b["sent_emb"], match_labels, b["cap_lens"],
-                    b.get("class_ids"), B)
-                if self.early_damsm_bwd:
-                    damsm_grad, = torch.autograd.grad(ops.scalar_sum([w_loss, s_loss]), img)
-                    w_loss, s_loss = w_loss.detach(), s_loss.detach()
-                parts["w_loss"], parts["s_loss"] = w_loss, s_loss
-            for i in order[1:]:
-                d_head(i)
+                img = fake_imgs[nD - 1].detach().requires_grad_(True)
+                w_loss, s_loss = generator_damsm_branch(self._encoder(img), img, b["words_embs"], b["sent_emb"], match_labels,
+                                                        b["cap_lens"], b.get("class_ids"), B)
+                damsm_grad, = torch.autograd.grad(ops.scalar_sum([w_loss, s_loss]), img)
+                parts["w_loss"], parts["s_loss"] = w_loss.detach(), s_loss.detach()
+            for i in range(nD - 1)[::-1]:
+                head(i)
             self._phase("D tails + G-step D fwd")
-            for i in order[::-1]:
-                d_tail(i)
+            if not run.UPDATE_BEHIND_FAKE:
+                for i in range(nD):
+                    with torch.cuda.stream(self.side[i]):
+                        run.update(i, b, fake_imgs)
             self._text_in_window()
             for s in self.side:
                 cur.wait_stream(s)
             self._phase("G backward")
-            self.optG.zero_grad()
-            errG_total = generator_total(parts, nD)
+            g_imgs = [None] * nD
+            for i in range(nD):
+                out["errD%d" % i], parts["g_loss%d" % i], g_imgs[i] = run.result(i)
+            if not replayed:
+                self.optG.zero_grad()
+                errG_d = generator_total(parts, nD)
         else:
-            prev = None
+            # largest-first: D256's gradient all-reduce overlaps the D128 and D64 forward/backward
+            prev, order = None, list(range(nD))[::-1]
             for i in order:
                 self.optDs[i].zero_grad()
                 errD = self._d_loss(i, b, fake_imgs, real_labels, fake_labels)
@@ -850,31 +927,110 @@ class TrainEngine:
             for d in netsD:
                 for p in d.parameters():
                     p.requires_grad_(False)
-            errG_total, parts = generator_loss(netsD, self.image_encoder, fake_imgs, real_labels, b["words_embs"],
-                                               b["sent_emb"], match_labels, b["cap_lens"], b.get("class_ids"), None,
-                                               local_labels=b["label_one_hot"], transf_matrices=b["tm"],
-                                               transf_matrices_inv=b["tmi"], return_logs=False)
-        kl_loss = KL_loss(mu, logvar)
-        errG_total = ops.scalar_sum([errG_total, kl_loss])          # trainer.py:330
-        with ops.wgrad_overlap():
-            if self.multi_stream and damsm_grad is not None:
-                torch.autograd.backward([errG_total, fake_imgs[nD - 1]], [None, damsm_grad])
-            else:
-                errG_total.backward()
-        for d in netsD:
-            for p in d.parameters():
-                p.requires_grad_(True)
+            errG_d, parts = generator_loss(netsD, self.image_encoder, fake_imgs, real_labels, b["words_embs"],
+                                           b["sent_emb"], match_labels, b["cap_lens"], b.get("class_ids"), None,
+                                           return_logs=False, **self._d_kw(0, b))
+        # The generator update, in the form the branches' results and the generator's forward call for
+        fwd_replayed = gg is not None
+        bwd_replayed = fwd_replayed and gg.gB is not None
+        if bwd_replayed:
+            # a replayed backward + Adam/EMA: the graph reads the branches' static results and static copies of the DAMSM branch's
+            gs = gg.static
+            gs["damsm_grad"].copy_(damsm_grad)
+            gs["w_loss"].copy_(parts["w_loss"])
+            gs["s_loss"].copy_(parts["s_loss"])
+            gg.gB.replay()
+            self.bn_counter.add(gg.calls)
+            errG_total, kl_loss = gg.errG, gg.kl
+        elif replayed:
+            # the gradient list: d g_loss_i / d fake_i of the replayed branches are the roots of the generator's backward
+            self.optG.zero_grad()
+            kl_loss = KL_loss(mu, logvar)
+            errG_total = ops.scalar_sum([generator_total(parts, nD), kl_loss.detach()])          # the logged value
+            g_imgs[nD - 1] = ops.add(g_imgs[nD - 1], damsm_grad)       # d errG / d img256 = D256 path + DAMSM path
+            with ops.wgrad_overlap():
+                torch.autograd.backward(list(fake_imgs) + [kl_loss], g_imgs + [None], retain_graph=fwd_replayed)
+                if fwd_replayed:
+                    # the tape of a replayed forward was recorded on the capture stream and autograd runs its nodes THERE; the gradient
+                    # kernels write the parameters' .grad buffers directly (no AccumulateGrad node, hence no end-of-backward stream
+                    # synchronisation by the engine): the main stream -- Adam -- has to wait for that stream itself
+                    cur.wait_stream(self._g_cap_stream)
+        else:
+            # a live tape through g_loss_i (autograd replays each branch's backward on the branch's stream)
+            kl_loss = KL_loss(mu, logvar)
+            errG_total = ops.scalar_sum([errG_d, kl_loss])          # trainer.py:330
+            with ops.wgrad_overlap():
+                if damsm_grad is not None:
+                    torch.autograd.backward([errG_total, fake_imgs[nD - 1]], [None, damsm_grad])
+                else:
+                    errG_total.backward()
+            for d in netsD:                                      # (the G step took no weight gradients of the Ds)
+                for p in d.parameters():
+                    p.requires_grad_(True)
         self._phase("G adam")
-        self._opt_step(self.optG, self._allreduce_async(self.optG))       # Adam + EMA in one launch
+        if not bwd_replayed:
+            self._opt_step(self.optG, self._allreduce_async(self.optG))       # Adam + EMA in one launch
         self.bn_counter.flush()                                           # all num_batches_tracked, one launch
-        out.update(errG=errG_total.detach(), kl=kl_loss.detach(), fake64=fake_imgs[0].detach(),
-                   fake_last=fake_imgs[-1].detach())
+        # Logs.  What a replayed graph wrote is cloned: its next replay rewrites it.
+        def keep(t, graph_output):
+            return t.detach().clone() if graph_output else t.detach()
+
+        out.update(errG=keep(errG_total, bwd_replayed), kl=keep(kl_loss, fwd_replayed), fake64=keep(fake_imgs[0], fwd_replayed),
+                   fake_last=keep(fake_imgs[-1], fwd_replayed))
         out.update({k: v.detach() for k, v in parts.items()})
         self._phase("end")
         return out
 
+    def _g_forward(self, b, gg):
+        """The generator's forward, once per step: eager, or -- gg: the captured variant for this batch's text shapes -- the
+        replay of its forward graph on refreshed static inputs.  Returns fake_imgs, mu, logvar; the latter two are None when
+        the backward is replayed as well (its graph holds them)."""
+        if gg is None:
+            fake_imgs, _, mu, logvar = self.netG(b["z"], b["sent_emb"], b["words_embs"], b["mask"], b["tmi"],
+                                                 b["label_one_hot"], b.get("eps"))
+            return fake_imgs, mu, logvar
+        gs = gg.static
+        # (.data: see device_step)
+        for k in ("z", "words_embs", "mask", "tmi", "label_one_hot"):
+            gs[k].data.copy_(b[k])
+        if b.get("eps") is not None:
+            gs["eps"].data.copy_(b["eps"])
+        else:
+            gs["eps"].data.normal_()                    # model.py:333-338: drawn per forward
+        gg.gF.replay()
+        if gg.gB is not None:
+            return gg.fake, None, None
+        self.bn_counter.add(gg.calls)                   # (forward + backward graphs: counted behind the backward's replay)
+        return gg.live                                  # forward-only graph: the live outputs carry the captured autograd graph
+
     # -- branch graphs -----------------------------------------------------------------------------------------------
     _BG_KEYS = ("sent_emb", "label_one_hot", "tm", "tmi")
+
+    def _bg_first_use(self, b):
+        """The first step that replays the branches: warm-up (allocator, workspaces, packed weight copies), capture -- and undo,
+        none of it may train: two eager steps on this batch, put back."""
+        snap = self._snapshot()
+        self.branch_graphs = False
+        try:
+            with self.bn_counter.recording():
+                wb = {k: v for k, v in b.items() if k != "inputs_ready"}
+                # the warm-up draws random numbers (CA_NET's eps when the batch carries none): the generators are put back
+                # afterwards, so a run with branch graphs sees the same random stream as one without from step 1 on
+                with torch.random.fork_rng(devices=[b["z"].device]):
+                    for _ in range(2):
+                        self.device_step(dict(wb))
+                    with torch.no_grad():
+                        if "words_embs" not in b:
+                            b["words_embs"], b["sent_emb"], b["mask"] = self.encode_text(b["captions"], b["cap_lens_cpu"])
+                        fk, _, _, _ = self.netG(b["z"], b["sent_emb"], b["words_embs"], b["mask"], b["tmi"], b["label_one_hot"],
+                                                b.get("eps"))
+                self._bg = self._bg_capture(b, fk)
+                for o in [self.optG] + self.optDs:
+                    o.repack_on_touch = True
+        finally:
+            self.branch_graphs = True
+        self._restore(snap)
+        torch.cuda.synchronize()
 
     def _bg_capture(self, b, fake_imgs):
         """Capture the discriminator branches on their streams (see __init__).  Static inputs: the real images, the fake
@@ -882,29 +1038,26 @@ class TrainEngine:
         The forward of D_i(real) and the rest live in two graphs of one memory pool so that D_i(real) can be replayed early,
         beside the generator's forward."""
         from ..hip import lib as _lib
-        from .miscc.losses import _call_d, paired
         netsD, nD = self.netsD, len(self.netsD)
         st = {k: b[k].clone() for k in self._BG_KEYS}
         st["imgs"] = [t.clone() for t in b["imgs"]]
         st["fake"] = [t.detach().clone() for t in fake_imgs]
         st["sent"] = [b["sent_emb"].clone() for _ in self.netsD]       # split form: a copy per branch, written on ITS stream
-        split = self.split_d
         B = b["z"].shape[0]
-        real_labels, fake_labels = b["z"].new_ones(B), b["z"].new_zeros(B)
-        bg = {"static": st, "gR": [], "gU": [], "gA": [], "out": [], "calls": [], "B": B}
+        labels = b["z"].new_ones(B), b["z"].new_zeros(B)
+        bg = {"B": B, "static": st, "branches": [], "G": {}}
         torch.cuda.synchronize()
-        counter = self.bn_counter
         # no collective may be captured: the reducers' hooks (armed by zero_grad) stay silent while the backward is recorded
-        hooks = [(o, o.on_zero) for o in self.optDs if getattr(o, "on_zero", None) is not None]
+        hooks = [(o, o.on_zero) for o in self.optDs if o.on_zero is not None]
         for o, _ in hooks:
             o.on_zero = None
             self.reducers[id(o)].active = False
         for i in range(nD):
             s = self.side[i]
             # (weight gradients stay in line inside the branch graphs: a forked graph replays slowly, 47.1 vs 42.1 ms per step, round 3)
-            kw = dict(local_labels=st["label_one_hot"], transf_matrices=st["tm"], transf_matrices_inv=st["tmi"]) if i == 0 else {}
+            sb = dict(st, sent_emb=st["sent"][i]) if self.split_d else st      # the static batch as branch i reads it
+            kw = self._d_kw(i, st)
             pool = torch.cuda.graph_pool_handle()
-            calls0 = list(counter.calls)
             gR, gU = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             gA = torch.cuda.CUDAGraph() if self.distributed else None
             # The branch's results (errD_i, g_loss_i, d g_loss_i / d fake_i) are read by the MAIN stream during the generator's
@@ -912,42 +1065,37 @@ class TrainEngine:
             # gR shares the private memory pool of gU / gA, so results living INSIDE that pool could be overwritten by gR's
             # temporaries.  They are therefore copied, as the last nodes of the graph, into buffers allocated here, outside the
             # pool; gR never touches those, and the next gU / gA writes them only behind `s.wait_stream(main)` of step k+1.
-            res = (torch.empty((), dtype=torch.float32, device=st["fake"][i].device),
-                   torch.empty((), dtype=torch.float32, device=st["fake"][i].device), torch.empty_like(st["fake"][i]))
-            with _lib.capture_guard():
-                with torch.cuda.graph(gR, pool=pool, stream=s):
-                    feat = self._d_real(i, st, st["sent"][i])          # (zero_grad; D_i(real) or the whole real half)
-                def tail(errD):
-                    # Adam (+ re-pack), then the generator-step forward through the updated D_i and its image gradient
-                    self._opt_step(self.optDs[i], None)
-                    for p in netsD[i].parameters():
-                        p.requires_grad_(False)
-                    leaf = st["fake"][i].detach().requires_grad_(True)
-                    g_loss = generator_d_branch(netsD[i], leaf, st["sent"][i] if split else st["sent_emb"], **kw)
-                    g_img, = torch.autograd.grad(g_loss, leaf)
-                    for p in netsD[i].parameters():
-                        p.requires_grad_(True)
-                    for dst, src in zip(res, (errD.detach(), g_loss.detach(), g_img)):
-                        dst.copy_(src)
-                    return res
+            br = CapturedBranch(gR=gR, gU=gU, gA=gA, errD=torch.empty((), dtype=torch.float32, device=st["fake"][i].device),
+                                g_loss=torch.empty((), dtype=torch.float32, device=st["fake"][i].device),
+                                g_img=torch.empty_like(st["fake"][i]))
+            eager = EagerBranches(self, *labels)               # what the graphs record: the eager branch on the static batch
 
+            def tail():
+                # Adam (+ re-pack), then the generator-step forward through the updated D_i and its image gradient
+                self._opt_step(self.optDs[i], None)
+                for p in netsD[i].parameters():
+                    p.requires_grad_(False)
+                leaf = st["fake"][i].detach().requires_grad_(True)
+                g_loss = generator_d_branch(netsD[i], leaf, sb["sent_emb"], **kw)
+                g_img, = torch.autograd.grad(g_loss, leaf)
+                for p in netsD[i].parameters():
+                    p.requires_grad_(True)
+                for dst, src in ((br.errD, eager.errD[i]), (br.g_loss, g_loss.detach()), (br.g_img, g_img)):
+                    dst.copy_(src)
+
+            with self.bn_counter.recording() as calls, _lib.capture_guard():      # (`calls` is filled when the block ends)
+                with torch.cuda.graph(gR, pool=pool, stream=s):
+                    eager.real(i, sb)                                  # (zero_grad; D_i(real) or the whole real half)
                 with torch.cuda.graph(gU, pool=pool, stream=s):
-                    if isinstance(feat, tuple):
-                        errD = self._d_fake(i, st, st["fake"], feat, st["sent"][i])
-                    else:
-                        errD = discriminator_loss(netsD[i], st["imgs"][i], st["fake"][i], st["sent_emb"], real_labels,
-                                                  fake_labels, None, real_features=feat, **kw)
-                        with ops.wgrad_overlap():
-                            errD.backward()
+                    eager.fake(i, sb, st["fake"])
                     if gA is None:
-                        out = tail(errD)
+                        tail()
                 if gA is not None:
                     with torch.cuda.graph(gA, pool=pool, stream=s):      # replayed behind the bucket's all-reduce
-                        out = tail(errD.detach())
-            del feat, errD
-            bg["gR"].append(gR); bg["gU"].append(gU); bg["gA"].append(gA); bg["out"].append(out)
-            bg["calls"].append([a - c for a, c in zip(counter.calls, calls0)])     # BatchNorm calls the replays stand for
-            counter.calls = calls0
+                        tail()
+            del eager
+            br.calls = calls
+            bg["branches"].append(br)
         for o, h in hooks:
             o.on_zero = h
         torch.cuda.synchronize()
@@ -964,55 +1112,52 @@ class TrainEngine:
         gs["eps"] = b["eps"].clone() if b.get("eps") is not None else torch.randn(B, cfg.GAN.CONDITION_DIM, device=dev)
         gs["damsm_grad"] = torch.zeros_like(st["fake"][nD - 1])
         gs["w_loss"], gs["s_loss"] = torch.zeros((), device=dev), torch.zeros((), device=dev)
-        if getattr(self, "_g_cap_stream", None) is None:
+        if self._g_cap_stream is None:
             # the capture stream: one per process (not a fresh pool stream per engine: torch's pool has 32 and cycles).  With the
             # forward-only graph the eager backward's nodes RUN on this stream (autograd executes a node where its forward was
             # recorded): its weight gradients use the main stream's weight-gradient side stream, as an eager generator's do
             self._g_cap_stream = _engine_stream(("gcap",))
             main_w = ops.precreate_wgrad_stream(torch.cuda.current_stream())
             ops._wgrad_streams.setdefault(self._g_cap_stream.cuda_stream, main_w)
-        counter, cap = self.bn_counter, self._g_cap_stream
-        calls0 = list(counter.calls)
+        cap = self._g_cap_stream
         pool = torch.cuda.graph_pool_handle()
-        gF, gB = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        gg = CapturedGenerator(gF=torch.cuda.CUDAGraph(), static=gs)
         # autograd graphs of earlier (eager) iterations must be gone: an AccumulateGrad node that survives from them belongs to the
         # main stream, and the engine would then pull that stream into the capture (a forked graph -- those replay slowly)
         import gc
         gc.collect()
         torch.cuda.synchronize()
-        with _lib.capture_guard():
-            with torch.cuda.graph(gF, pool=pool, stream=cap):
+        with self.bn_counter.recording() as calls, _lib.capture_guard():      # (`calls` is filled when the block ends)
+            with torch.cuda.graph(gg.gF, pool=pool, stream=cap):
                 fake_imgs, _, mu, logvar = self.netG(gs["z"], st["sent_emb"], gs["words_embs"], gs["mask"], gs["tmi"],
                                                      gs["label_one_hot"], gs["eps"])
+            gg.fake = [t.detach() for t in fake_imgs]
             if self.g_fwd_only:
-                calls = [a - c for a, c in zip(counter.calls, calls0)]
-                counter.calls = calls0
-                torch.cuda.synchronize()
-                return {"gF": gF, "gB": None, "gs": gs, "fake": [t.detach() for t in fake_imgs], "live": (list(fake_imgs), mu, logvar),
-                        "calls": calls}
-            with torch.cuda.graph(gB, pool=pool, stream=cap):
-                self.optG.zero_grad()
-                parts = {"g_loss%d" % i: bg["out"][i][1] for i in range(nD)}
-                parts["w_loss"], parts["s_loss"] = gs["w_loss"], gs["s_loss"]
-                kl_loss = KL_loss(mu, logvar)
-                errG_total = ops.scalar_sum([generator_total(parts, nD), kl_loss.detach()])
-                grads = [bg["out"][i][2] for i in range(nD)]
-                grads[nD - 1] = ops.add(grads[nD - 1], gs["damsm_grad"])
-                with ops.wgrad_overlap():
-                    torch.autograd.backward(list(fake_imgs) + [kl_loss], grads + [None])
-                self._opt_step(self.optG, None)
-                gout = (errG_total.detach(), kl_loss.detach())
-        calls = [a - c for a, c in zip(counter.calls, calls0)]
-        counter.calls = calls0
+                gg.live = (list(fake_imgs), mu, logvar)
+            else:
+                gg.gB = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gg.gB, pool=pool, stream=cap):
+                    self.optG.zero_grad()
+                    parts = {"g_loss%d" % i: br.g_loss for i, br in enumerate(bg["branches"])}
+                    parts["w_loss"], parts["s_loss"] = gs["w_loss"], gs["s_loss"]
+                    kl_loss = KL_loss(mu, logvar)
+                    errG_total = ops.scalar_sum([generator_total(parts, nD), kl_loss.detach()])
+                    grads = [br.g_img for br in bg["branches"]]
+                    grads[nD - 1] = ops.add(grads[nD - 1], gs["damsm_grad"])
+                    with ops.wgrad_overlap():
+                        torch.autograd.backward(list(fake_imgs) + [kl_loss], grads + [None])
+                    self._opt_step(self.optG, None)
+                    gg.errG, gg.kl = errG_total.detach(), kl_loss.detach()
+        gg.calls = calls
         torch.cuda.synchronize()
-        return {"gF": gF, "gB": gB, "gs": gs, "fake": [t.detach() for t in fake_imgs], "gout": gout, "calls": calls}
+        return gg
 
     def _g_graph_for(self, b):
         """the generator graph pair for this batch's text shapes (captured at first use), or None: eager generator"""
         if not self.g_graphs:
             return None
         key = (tuple(b["words_embs"].shape), tuple(b["mask"].shape))
-        table = self._bg.setdefault("G", {})
+        table = self._bg["G"]
         g = table.get(key)
         if g is None:
             if len(table) < self.G_GRAPH_VARIANTS:
@@ -1027,155 +1172,6 @@ class TrainEngine:
                                                    "pad the captions to fewer lengths or raise TrainEngine.G_GRAPH_VARIANTS)",
                                                    key, len(table))
         return g
-
-    def _branch_graph_step(self, b, real_labels, fake_labels, match_labels):
-        """device_step with the discriminator branches replayed as hipGraphs (same streams, same order, same results)."""
-        netG, netsD, nD = self.netG, self.netsD, len(self.netsD)
-        B = b["z"].shape[0]
-        cur = torch.cuda.current_stream()
-        if self._bg is None:
-            # warm-up (allocator, workspaces, packed weight copies) must not train: two eager steps on this batch, undone
-            snap = self._snapshot()
-            calls = list(self.bn_counter.calls)
-            self.branch_graphs = False
-            try:
-                wb = {k: v for k, v in b.items() if k != "inputs_ready"}
-                # the warm-up draws random numbers (CA_NET's eps when the batch carries none): the generators are put back
-                # afterwards, so a run with branch graphs sees the same random stream as one without from step 1 on
-                with torch.random.fork_rng(devices=[b["z"].device]):
-                    for _ in range(2):
-                        self.device_step(dict(wb))
-                    with torch.no_grad():
-                        if "words_embs" not in b:
-                            b["words_embs"], b["sent_emb"], b["mask"] = self.encode_text(b["captions"], b["cap_lens_cpu"])
-                        fk, _, _, _ = netG(b["z"], b["sent_emb"], b["words_embs"], b["mask"], b["tmi"], b["label_one_hot"], b.get("eps"))
-                self._bg = self._bg_capture(b, fk)
-                for o in [self.optG] + self.optDs:
-                    o.repack_on_touch = True
-            finally:
-                self.branch_graphs = True
-            self._restore(snap)
-            self.bn_counter.calls = calls
-            torch.cuda.synchronize()
-        bg, st = self._bg, self._bg["static"]
-        ready = b.get("inputs_ready")
-        text_ev = self._text_first(b, ready) if self.split_d else None
-        # D_i(real) -- split form: the whole real half of D_i's update --: beside the text encoder and the generator's forward
-        # (and the tail of the previous step)
-        for i in range(nD)[::-1]:
-            s = self.side[i]
-            if ready is not None:
-                s.wait_event(ready)
-                if text_ev is not None:
-                    s.wait_event(text_ev)
-            else:
-                s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                st["imgs"][i].copy_(b["imgs"][i])
-                if i == 0:
-                    for k in ("label_one_hot", "tm", "tmi"):
-                        st[k].copy_(b[k])
-                if self.split_d:
-                    st["sent"][i].copy_(b["sent_emb"])
-                bg["gR"][i].replay()
-        if ready is not None:
-            cur.wait_event(ready)
-        self._phase("text+Gfwd")
-        if "words_embs" not in b:
-            b["words_embs"], b["sent_emb"], b["mask"] = self._text_for(b)
-        # (.data: the copy must not move the version counter of a tensor the forward-only generator graph's autograd tape has saved)
-        st["sent_emb"].data.copy_(b["sent_emb"])           # (main stream; the branches wait for it below)
-        gg = self._g_graph_for(b)
-        if gg is not None:
-            gs = gg["gs"]
-            for k in ("z", "words_embs", "mask", "tmi", "label_one_hot"):
-                gs[k].data.copy_(b[k])
-            if b.get("eps") is not None:
-                gs["eps"].data.copy_(b["eps"])
-            else:
-                gs["eps"].data.normal_()                    # model.py:333-338: drawn per forward
-            gg["gF"].replay()
-            fake_imgs, mu, logvar = gg["fake"], None, None
-            if gg["gB"] is None:                          # forward-only graph: the live outputs carry the captured autograd graph
-                fake_imgs, mu, logvar = gg["live"]
-                for j, n in enumerate(gg["calls"]):
-                    self.bn_counter.calls[j] += n
-        else:
-            fake_imgs, _, mu, logvar = netG(b["z"], b["sent_emb"], b["words_embs"], b["mask"], b["tmi"], b["label_one_hot"], b.get("eps"))
-        out, parts = {}, {}
-        self._phase("D heads + Inception")
-
-        def branch(i):
-            s = self.side[i]
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                st["fake"][i].copy_(fake_imgs[i].detach())
-                bg["gU"][i].replay()
-                if bg["gA"][i] is not None:                # data parallel: sum the bucket over the ranks, then Adam and the rest
-                    red = self.reducers.get(id(self.optDs[i]))
-                    if red is not None:
-                        red.reduce_now()
-                    elif not self._debug_no_ar:
-                        allreduce_flat(self.optDs[i].g, None, self.comm, self._bucket_name(self.optDs[i]))
-                    bg["gA"][i].replay()
-            for j, n in enumerate(bg["calls"][i]):
-                self.bn_counter.calls[j] += n
-
-        branch(nD - 1)
-        s = self.side[nD]
-        s.wait_stream(cur)
-        with torch.cuda.stream(s):
-            img = fake_imgs[nD - 1].detach().requires_grad_(True)
-            w_loss, s_loss = generator_damsm_branch(self._encoder(img), img, b["words_embs"], b["sent_emb"], match_labels,
-                                                    b["cap_lens"], b.get("class_ids"), B)
-            damsm_grad, = torch.autograd.grad(ops.scalar_sum([w_loss, s_loss]), img)
-            parts["w_loss"], parts["s_loss"] = w_loss.detach(), s_loss.detach()
-        for i in range(nD - 1)[::-1]:
-            branch(i)
-        self._phase("D tails + G-step D fwd")
-        self._text_in_window()
-        for s in self.side:
-            cur.wait_stream(s)
-        self._phase("G backward")
-        for i in range(nD):
-            errD, g_loss, _ = bg["out"][i]
-            out["errD%d" % i] = errD.clone()
-            parts["g_loss%d" % i] = g_loss.clone()
-        if gg is not None and gg["gB"] is not None:
-            gs = gg["gs"]
-            gs["damsm_grad"].copy_(damsm_grad)
-            gs["w_loss"].copy_(parts["w_loss"])
-            gs["s_loss"].copy_(parts["s_loss"])
-            gg["gB"].replay()
-            for j, n in enumerate(gg["calls"]):
-                self.bn_counter.calls[j] += n
-            self._phase("G adam")
-            self.bn_counter.flush()
-            out.update(errG=gg["gout"][0].clone(), kl=gg["gout"][1].clone(), fake64=fake_imgs[0].clone(),
-                       fake_last=fake_imgs[-1].clone())
-            out.update({k: v.detach() for k, v in parts.items()})
-            self._phase("end")
-            return out
-        self.optG.zero_grad()
-        kl_loss = KL_loss(mu, logvar)
-        errG_total = ops.scalar_sum([generator_total(parts, nD), kl_loss.detach()])          # the logged value
-        grads = [bg["out"][i][2] for i in range(nD)]
-        grads[nD - 1] = ops.add(grads[nD - 1], damsm_grad)       # d errG / d img256 = D256 path + DAMSM path
-        with ops.wgrad_overlap():
-            torch.autograd.backward(list(fake_imgs) + [kl_loss], grads + [None], retain_graph=gg is not None)
-            if gg is not None:
-                # the tape of a replayed forward was recorded on the capture stream and autograd runs its nodes THERE; the gradient
-                # kernels write the parameters' .grad buffers directly (no AccumulateGrad node, hence no end-of-backward stream
-                # synchronisation by the engine): the main stream -- Adam -- has to wait for that stream itself
-                cur.wait_stream(self._g_cap_stream)
-        self._phase("G adam")
-        self._opt_step(self.optG, self._allreduce_async(self.optG))
-        self.bn_counter.flush()
-        keep = (lambda t: t.detach().clone()) if gg is not None else (lambda t: t.detach())     # (a replayed forward rewrites its outputs)
-        out.update(errG=errG_total.detach(), kl=keep(kl_loss), fake64=keep(fake_imgs[0]), fake_last=keep(fake_imgs[-1]))
-        out.update({k: v.detach() for k, v in parts.items()})
-        self._phase("end")
-        return out
 
     # -- text embeddings one step ahead --------------------------------------------------------------------------------
     def prefetch_text(self, captions, cap_lens_cpu):
@@ -1199,7 +1195,7 @@ class TrainEngine:
 
     def _text_in_window(self):
         """called by the step between the generator forward and the join with the side branches"""
-        nxt, self._tx_next = getattr(self, "_tx_next", None), None
+        nxt, self._tx_next = self._tx_next, None
         if nxt is None:
             return
         w, s_, m = self.encode_text(nxt[0], nxt[1])
@@ -1209,7 +1205,7 @@ class TrainEngine:
 
     def _text_for(self, b):
         """the batch's text embeddings: prefetched (see prefetch_text; same stream, so no event) or computed here"""
-        hit, self._tx_ready = getattr(self, "_tx_ready", None), None
+        hit, self._tx_ready = self._tx_ready, None
         if hit is not None and hit[0] is b["captions"]:
             self._text_ev = hit[2]
             return hit[1]

@@ -363,7 +363,7 @@ def test_g_net_eval_mode():
 
 
 @pytest.mark.parametrize("mode", ["eager", "graph", "branch_graphs", "branch_graphs_and_g", "branch_graphs_and_g_fwd",
-                                  "branch_graphs_inputs_ready"])
+                                  "branch_graphs_inputs_ready", "eager_inputs_ready"])
 def test_two_train_steps(mode):
     """the op order of the step (fake images generated once, each D updated
     before generator_loss forwards through it), Adam, EMA, BN running statistics -- eager, as one
@@ -372,7 +372,9 @@ def test_two_train_steps(mode):
     forward / backward + Adam both replayed (MOGAN_G_GRAPHS=1), and -- branch_graphs_inputs_ready --
     the way bench.py and condGANTrainer.train() drive the engine: every batch carries an `inputs_ready` event, so D_i(real) of
     step 1 is replayed on its branch stream while the main stream is still in step 0's generator backward (no host
-    synchronisation between the two steps; the branch results the main stream reads live outside the graphs' pool)."""
+    synchronisation between the two steps; the branch results the main stream reads live outside the graphs' pool);
+    eager_inputs_ready: the same drive with every launch eager (branch_graphs=False): the real halves of step 1 are queued on
+    their branch streams behind the batch's event and their own stream order alone."""
     from mogan_amd.attngan.trainer import TrainEngine
     g = golden("step")
     G, Ds, enc = _build_all()
@@ -380,7 +382,7 @@ def test_two_train_steps(mode):
     assert eng.branch_graphs == mode.startswith("branch_graphs")
     eng.g_graphs = mode in ("branch_graphs_and_g", "branch_graphs_and_g_fwd")
     eng.g_fwd_only = mode == "branch_graphs_and_g_fwd"      # only the generator's forward replayed, its backward eager on the captured tape
-    early = mode == "branch_graphs_inputs_ready"
+    early = mode.endswith("inputs_ready")
     nets = [("G", G)] + [("D%d" % i, D) for i, D in enumerate(Ds)]
     init = {n: {k: probe(v) for k, v in net.state_dict().items()} for n, net in nets}
     bts = [synthetic.to_device(synthetic.make_batch(4, words_num=5, nef=16, seed=100 + step), DEV) for step in range(2)]
@@ -468,6 +470,87 @@ def test_parked_weight_gradients_on_the_generator_tape(monkeypatch):
             off = float(((a[k] - b[k]).abs() > 0.25 * lr).float().mean())
             assert off <= 0.02, "step %d, %s: %.1f %% of the parameters differ by > lr/4 between the eager and the " \
                                 "replayed-forward generator" % (st_, k, 100 * off)
+
+
+def _engine_trajectory(batches, **engine_kw):
+    """A fresh reduced-width engine driven like bench.py drives it -- every batch carries an `inputs_ready` event, no host
+    synchronisation between the steps -- over `batches`; after every step the logs, every parameter and every BatchNorm call
+    counter, cloned on the main stream (which has joined the branch streams at the end of the step).  Returns (engine, steps)."""
+    from mogan_amd.attngan.trainer import TrainEngine
+    G, Ds, enc = _build_all()
+    eng = TrainEngine(None, enc, G, Ds, use_graph=False, **engine_kw)
+    nets = [("G", G)] + [("D%d" % i, D) for i, D in enumerate(Ds)]
+    torch.cuda.synchronize()
+    steps = []
+    for bt in batches:
+        bt = dict(bt)
+        bt["inputs_ready"] = torch.cuda.Event()
+        bt["inputs_ready"].record()
+        logs = eng.step(bt)
+        steps.append(({k: v.clone() for k, v in logs.items()},
+                      {"%s.%s" % (n, k): v.detach().clone() for n, net in nets for k, v in net.named_parameters()},
+                      {"%s.%s" % (n, k): v.clone() for n, net in nets for k, v in net.state_dict().items() if k.endswith("tracked")}))
+    torch.cuda.synchronize()
+    return eng, steps
+
+
+def _same_parameters(got, want, what, lr=2e-4, allowed=0.02):
+    """the criterion of test_parked_weight_gradients_on_the_generator_tape, for every parameter tensor of the four networks"""
+    worst = ("", 0.0)
+    for k in want:
+        off = float(((got[k] - want[k]).abs() > 0.25 * lr).float().mean())
+        worst = max(worst, (k, off), key=lambda t: t[1])
+    print("%s: worst fraction of elements off by > lr/4: %.4f (%s)" % (what, worst[1], worst[0]))
+    assert worst[1] <= allowed, "%s, %s: %.1f %% of the parameters differ by > lr/4" % (what, worst[0], 100 * worst[1])
+
+
+def test_two_halves_discriminator_loss_through_the_engine():
+    """losses.D_SPLIT through TrainEngine (the real-image half of every discriminator update evaluated and back-propagated beside the
+    generator's forward), eager multi-stream and with the branches replayed, against the eager engine with the one-piece loss on the
+    same weights and batches, all driven by `inputs_ready` without a host synchronisation between the two steps.  Bounds: errD_i
+    of step 0 to 2e-6 relative (test_discriminator_loss_in_two_halves: the same sums in another order); after each step at most
+    2 % of any parameter tensor's elements off by more than lr/4 (test_parked_weight_gradients_on_the_generator_tape)."""
+    from mogan_amd.attngan.miscc import losses as L
+    bts = [synthetic.to_device(synthetic.make_batch(4, words_num=5, nef=16, seed=100 + s_), DEV) for s_ in range(2)]
+    _, ref = _engine_trajectory(bts, branch_graphs=False)
+    L.D_SPLIT = True
+    try:
+        for bgr in (False, True):
+            eng, got = _engine_trajectory(bts, branch_graphs=bgr)
+            assert eng.split_d and eng.branch_graphs == bgr
+            for i in range(3):
+                a, b = float(got[0][0]["errD%d" % i]), float(ref[0][0]["errD%d" % i])
+                print("branch_graphs=%s errD%d: %.9g vs %.9g, rel %.3e" % (bgr, i, a, b, abs(a - b) / abs(b)))
+                assert abs(a - b) <= 2e-6 * abs(b), (bgr, i, a, b)
+            for st_ in range(2):
+                _same_parameters(got[st_][1], ref[st_][1], "split, branch_graphs=%s, step %d" % (bgr, st_))
+    finally:
+        L.D_SPLIT = False
+
+
+def test_ragged_last_batch_behind_captured_branches():
+    """Batches of 4, 4, 3, 4 samples through an engine with captured branches: the third runs eagerly (the graphs are for B = 4),
+    the fourth replays the one captured set again; against an all-eager engine over the same batches, after every step: parameters
+    (the criterion of test_parked_weight_gradients_on_the_generator_tape) and every num_batches_tracked -- a replay stands for the
+    BatchNorm calls recorded at its capture, an eager step counts its own."""
+    sizes = (4, 4, 3, 4)
+    bts = [synthetic.to_device(synthetic.make_batch(n, words_num=5, nef=16, seed=200 + s_), DEV) for s_, n in enumerate(sizes)]
+    _, ref = _engine_trajectory(bts, branch_graphs=False)
+    captures = []
+    from mogan_amd.attngan.trainer import TrainEngine
+    capture = TrainEngine._bg_capture
+    try:
+        TrainEngine._bg_capture = lambda self, *a, **k: captures.append(1) or capture(self, *a, **k)
+        eng, got = _engine_trajectory(bts, branch_graphs=True)
+    finally:
+        TrainEngine._bg_capture = capture
+    assert eng.branch_graphs and len(captures) == 1                   # one set of branch graphs, for B = 4
+    assert len(eng._bg.get("G", {})) == 1                             # and one generator forward graph
+    for st_ in range(len(sizes)):
+        _same_parameters(got[st_][1], ref[st_][1], "ragged, step %d (B = %d)" % (st_, sizes[st_]))
+        for k, v in ref[st_][2].items():
+            assert int(got[st_][2][k]) == int(v), "step %d, %s: %d calls counted, %d by the eager engine" % (
+                st_, k, int(got[st_][2][k]), int(v))
 
 
 @pytest.mark.parametrize("B", [4, 20])
