@@ -418,7 +418,8 @@ int mogan_scale(const float* a, float alpha, float* y, long long n, hipStream_t 
 
 /* softmax over L of x viewed as (outer, L, inner), y = softmax(scale*x) restricted to the first
  * lens[o*inner+i] entries (lens nullable = all L); masked entries get 0.  bwd: dx = scale*y*(dy - sum(y*dy)).
- * GlobalAttention.py:50,58 (func_attention, DAMSM). */
+ * GlobalAttention.py:50,58 (func_attention, DAMSM).  lens is clamped to [0, L]; a column with no entry left is all zeros.
+ * MOGAN_ERR_SHAPE before any HIP call: outer, L or inner <= 0, a NULL x / y (fwd), y / dy / dx (bwd). */
 int mogan_softmax_fwd(const float* x, float* y, const int32_t* lens, long long outer, int L, long long inner,
                       float scale, hipStream_t stream);
 int mogan_softmax_bwd(const float* y, const float* dy, float* dx, const int32_t* lens, long long outer, int L,
@@ -427,7 +428,10 @@ int mogan_softmax_bwd(const float* y, const float* dy, float* dx, const int32_t*
 /* ---------------------------------------------------------------- spatial transformer (object pathway)
  * y[b,c] = grid_sample(x[b,c], affine_grid(theta[b])) bilinear, zero padding (model.py:17-21).
  * align_corners: 0 = torch>=1.3 default, 1 = torch 0.4.1 semantics.
- * bwd scatters with fp32 atomics into dx, which the callee zero-fills first. */
+ * bwd gathers: one thread per source pixel writes dx once, with no atomics and no zero-fill (see "Determinism" below); every
+ * element of dx is written, the ones no output pixel reaches with 0.
+ * MOGAN_ERR_SHAPE before any HIP call: a NULL x / dy, theta or y / dx, a dimension <= 0, B > 65535, Hin * Win or Hout * Wout
+ * beyond 2^31 - 256 (the _ex forms also: xB <= 0, B % xB, theta_G < 0, B % theta_G; the gather: C > 8 * 65535). */
 int mogan_stn_fwd(const float* x, const float* theta, float* y, int B, int C, int Hin, int Win, int Hout, int Wout,
                   int align_corners, hipStream_t stream);
 int mogan_stn_bwd(const float* dy, const float* theta, float* dx, int B, int C, int Hin, int Win, int Hout,
@@ -442,7 +446,8 @@ int mogan_stn_bwd(const float* dy, const float* theta, float* dx, int B, int C, 
  * Determinism: mogan_stn_bwd / _ex gather rather than scatter: every source pixel sums the contributions of the output
  * pixels whose taps land on it, samples in batch order and output pixels in row-major order, with no atomics, so dx is the
  * same bit for bit from run to run (the shared-source forms add the objects in object order, as the reference does).
- * tests/test_kernels_gpu.py::test_stn_shared_source_gradient_is_order_independent_to_rounding pins that. */
+ * tests/test_kernels_gpu.py::test_stn_shared_source_gradient_is_order_independent_to_rounding pins that, and
+ * tests/test_pathway_entry_points_gpu.py repeats every backward call of its table into re-poisoned memory and compares the bits. */
 int mogan_stn_fwd_ex(const float* x, const float* theta, float* y, int B, int C, int Hin, int Win, int Hout, int Wout,
                      int align_corners, int xB, int x_plane, int theta_G, hipStream_t stream);
 int mogan_stn_bwd_ex(const float* dy, const float* theta, float* dx, int B, int C, int Hin, int Win, int Hout, int Wout,
@@ -457,20 +462,28 @@ int mogan_stn_bwd_ex(const float* dy, const float* theta, float* dx, int B, int 
  *   (N/G, C, HW) tensor repeated for G objects:  rows = N / G, sb = C HW, sg = 0
  *   label[:, g] of a (B, G, C) tensor, batch n = g B + b (object-major): rows = B, sb = G C, sg = C  (x HW when bcast = 0)
  * mogan_concat_bwd: dsrc[i] (NULL = not wanted), in the source's own layout, = the sum of ddst over everything that read it
- * (its channel slice; summed over the plane when bcast; summed over the repeats when rows < N and sg = 0).  nsrc <= MOGAN_CAT_MAX. */
+ * (its channel slice; summed over the plane when bcast; summed over the repeats when rows < N and sg = 0).  nsrc <= MOGAN_CAT_MAX.
+ * MOGAN_ERR_SHAPE before any HIP call: a NULL table, dst / ddst or src[i] (dsrc[i] alone is nullable), nsrc outside
+ * 1..MOGAN_CAT_MAX, N or HW <= 0, C[i] or rows[i] <= 0, N % rows[i], and with sg[i] > 0 an sb[i] that is no positive multiple of
+ * sg[i] or holds fewer than N / rows[i] objects (sb[i] / sg[i]); in the backward also a wanted dsrc[i] with sg[i] > 0 whose
+ * tensor holds MORE objects than the batch reads (it is written whole, one row per batch index: N / rows[i] == sb[i] / sg[i]).
+ * Every dsrc[i] NULL: returns 0 and launches nothing. */
 #define MOGAN_CAT_MAX 4
 int mogan_concat_fwd(const void* const* src, const int* C, const int* rows, const long long* sb, const long long* sg,
                      const int* bcast, int nsrc, float* dst, int N, int HW, hipStream_t stream);
 int mogan_concat_bwd(const float* ddst, void* const* dsrc, const int* C, const int* rows, const long long* sb,
                      const long long* sg, const int* bcast, int nsrc, int N, int HW, hipStream_t stream);
-/* bbox (N,4)=(x,y,w,h) -> theta (N,2,3), theta_inv (N,2,3)   (miscc/utils.py:16-49) */
+/* bbox (N,4)=(x,y,w,h) -> theta (N,2,3), theta_inv (N,2,3)   (miscc/utils.py:16-49, its operation order, no contraction).
+ * MOGAN_ERR_SHAPE before any HIP call: N <= 0, a NULL pointer. */
 int mogan_bbox_to_theta(const float* bbox, float* theta, float* theta_inv, int N, hipStream_t stream);
 
 /* ---------------------------------------------------------------- word attention over image regions
  * GlobalAttentionGeneral.forward core (GlobalAttention.py:96-121) after conv_context:
  * h (B,idf,Q), src (B,idf,T), mask (B,T) uint8 nullable -> wc (B,idf,Q), attn (B,T,Q).
  * mask_mode 0 = reference indexing (row b*Q+q is masked with mask[(b*Q+q) mod B]),
- *           1 = mask[b].   Limits: idf <= 128, T <= 32. */
+ *           1 = mask[b].   Limits: idf <= 128, T <= 32.
+ * MOGAN_ERR_SHAPE before any HIP call (fwd and bwd): a dimension <= 0, idf > 128, T > 32, B > 65535, a NULL pointer other than
+ * mask / dattn. */
 int mogan_attn_fwd(const float* h, const float* src, const uint8_t* mask, float* wc, float* attn, int B, int idf,
                    int Q, int T, int mask_mode, hipStream_t stream);
 /* -> dh (B,idf,Q) and dscore (B,T,Q) (gradient w.r.t. the pre-softmax scores).  dattn nullable.

@@ -573,14 +573,17 @@ __global__ __launch_bounds__(256) void concat_bwd_kernel(CatGradP G, const float
 }
 
 static int cat_params(CatP& P, const void* const* src, const int* C, const int* rows, const long long* sb, const long long* sg,
-                      const int* bcast, int nsrc, int N, int HW) {
+                      const int* bcast, int nsrc, int N, int HW, bool nullable) {
+    if (!src || !C || !rows || !sb || !sg || !bcast) return MOGAN_ERR_SHAPE;
     if (nsrc <= 0 || nsrc > MOGAN_CAT_MAX || N <= 0 || HW <= 0) return MOGAN_ERR_SHAPE;
     P.nsrc = nsrc; P.N = N; P.HW = HW;
     int c0 = 0;
     for (int i = 0; i < MOGAN_CAT_MAX; ++i) {
         CatSrcP& S = P.s[i];
         if (i < nsrc) {
-            if (C[i] <= 0 || rows[i] <= 0 || N % rows[i] != 0) return MOGAN_ERR_SHAPE;
+            if (C[i] <= 0 || rows[i] <= 0 || N % rows[i] != 0 || (!nullable && !src[i])) return MOGAN_ERR_SHAPE;
+            // the per-object slice of a (rows, G, C) tensor: sb / sg objects per row, of which N / rows are read
+            if (sg[i] > 0 && (sb[i] <= 0 || sb[i] % sg[i] != 0 || N / rows[i] > sb[i] / sg[i])) return MOGAN_ERR_SHAPE;
             S.p = (const float*)src[i]; S.C = C[i]; S.rows = rows[i]; S.sb = sb[i]; S.sg = sg[i]; S.bcast = bcast[i] ? 1 : 0; S.c0 = c0;
             c0 += C[i];
         } else {
@@ -674,14 +677,14 @@ int mogan_down2_sum(const float* du, float* dx, int planes, int H, int W, hipStr
 
 int mogan_softmax_fwd(const float* x, float* y, const int32_t* lens, long long outer, int L, long long inner,
                       float scale, hipStream_t stream) {
-    if (outer <= 0 || L <= 0 || inner <= 0) return MOGAN_ERR_SHAPE;
+    if (outer <= 0 || L <= 0 || inner <= 0 || !x || !y) return MOGAN_ERR_SHAPE;                 // (lens is nullable)
     const long long cols = outer * inner;
     hipLaunchKernelGGL((softmax_kernel<false>), dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, stream, x, nullptr, y, lens, cols, L, inner, scale);
     return ok_launch();
 }
 int mogan_softmax_bwd(const float* y, const float* dy, float* dx, const int32_t* lens, long long outer, int L,
                       long long inner, float scale, hipStream_t stream) {
-    if (outer <= 0 || L <= 0 || inner <= 0) return MOGAN_ERR_SHAPE;
+    if (outer <= 0 || L <= 0 || inner <= 0 || !y || !dy || !dx) return MOGAN_ERR_SHAPE;
     const long long cols = outer * inner;
     hipLaunchKernelGGL((softmax_kernel<true>), dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, stream, y, dy, dx, lens, cols, L, inner, scale);
     return ok_launch();
@@ -743,7 +746,8 @@ int mogan_relu_bwd(const float* z, const float* dz, float* dx, long long n, int 
 int mogan_concat_fwd(const void* const* src, const int* C, const int* rows, const long long* sb, const long long* sg,
                      const int* bcast, int nsrc, float* dst, int N, int HW, hipStream_t stream) {
     CatP P;
-    const int rc = cat_params(P, src, C, rows, sb, sg, bcast, nsrc, N, HW);
+    if (!dst) return MOGAN_ERR_SHAPE;
+    const int rc = cat_params(P, src, C, rows, sb, sg, bcast, nsrc, N, HW, false);
     if (rc) return rc;
     bool v4 = (HW % 4) == 0 && (((uintptr_t)dst) & 15) == 0;
     for (int i = 0; i < nsrc && v4; ++i)
@@ -757,8 +761,13 @@ int mogan_concat_fwd(const void* const* src, const int* C, const int* rows, cons
 int mogan_concat_bwd(const float* ddst, void* const* dsrc, const int* C, const int* rows, const long long* sb, const long long* sg,
                      const int* bcast, int nsrc, int N, int HW, hipStream_t stream) {
     CatGradP G;
-    const int rc = cat_params(G.c, (const void* const*)dsrc, C, rows, sb, sg, bcast, nsrc, N, HW);
+    if (!ddst) return MOGAN_ERR_SHAPE;
+    const int rc = cat_params(G.c, (const void* const*)dsrc, C, rows, sb, sg, bcast, nsrc, N, HW, true);   // (dsrc[i] is nullable)
     if (rc) return rc;
+    // a per-object gradient is written as the whole (rows, sb / sg, C) tensor, one storage row per batch index: with fewer
+    // batch groups than objects the rows would not match (and ddst would be read past batch N)
+    for (int i = 0; i < nsrc; ++i)
+        if (dsrc[i] && sg[i] > 0 && N / rows[i] != sb[i] / sg[i]) return MOGAN_ERR_SHAPE;
     long long ne = 0, nr = 0;
     for (int i = 0; i <= MOGAN_CAT_MAX; ++i) { G.ebeg[i] = 0; G.rbeg[i] = 0; }
     for (int i = 0; i < MOGAN_CAT_MAX; ++i) {

@@ -17,6 +17,17 @@ namespace {
 
 static inline int ok_launch() { return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH; }
 
+// the kernels index a plane with ints and the grids round it up to blocks of 256: Hin * Win and Hout * Wout stay 256 below 2^31
+static inline bool plane_fits(int H, int W) { return (long long)H * W <= 0x7fffffffLL - 255; }
+
+// channel chunks per sample of the forward, so that about 1024 blocks run (pb * B may pass an int: counted in 64 bits)
+static inline int stn_csplit(int pb, int B, int C) {
+    const long long blocks = (long long)pb * B;
+    long long csplit = (1024 + blocks - 1) / blocks;
+    if (csplit > C) csplit = C;
+    return csplit < 1 ? 1 : (int)csplit;
+}
+
 struct Taps { int x0, y0; float wx1, wy1; bool vx0, vx1, vy0, vy1; };
 
 __device__ __forceinline__ Taps stn_taps(const float* __restrict__ th, int oy, int ox, int Hin, int Win, int Hout,
@@ -348,9 +359,11 @@ extern "C" {
 
 int mogan_stn_fwd(const float* x, const float* theta, float* y, int B, int C, int Hin, int Win, int Hout, int Wout,
                   int align_corners, hipStream_t stream) {
+    if (!x || !theta || !y) return MOGAN_ERR_SHAPE;
     if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || B > 65535) return MOGAN_ERR_SHAPE;
+    if (!plane_fits(Hin, Win) || !plane_fits(Hout, Wout)) return MOGAN_ERR_SHAPE;
     const int pb = (Hout * Wout + 255) / 256;
-    int csplit = (1024 + pb * B - 1) / (pb * B); if (csplit > C) csplit = C; if (csplit < 1) csplit = 1;
+    int csplit = stn_csplit(pb, B, C);
     const int cchunk = (C + csplit - 1) / csplit; csplit = (C + cchunk - 1) / cchunk;
     hipLaunchKernelGGL(stn_fwd_kernel, dim3(pb, csplit, B), dim3(256), 0, stream, x, theta, y, C, Hin, Win, Hout, Wout,
                        align_corners, cchunk);
@@ -367,8 +380,9 @@ int mogan_stn_fwd_ex(const float* x, const float* theta, float* y, int B, int C,
     if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || B > 65535 || xB <= 0 || B % xB != 0 ||
         theta_G < 0 || (theta_G > 0 && B % theta_G != 0))
         return MOGAN_ERR_SHAPE;
+    if (!x || !theta || !y || !plane_fits(Hin, Win) || !plane_fits(Hout, Wout)) return MOGAN_ERR_SHAPE;
     const int pb = (Hout * Wout + 255) / 256;
-    int csplit = (1024 + pb * B - 1) / (pb * B); if (csplit > C) csplit = C; if (csplit < 1) csplit = 1;
+    int csplit = stn_csplit(pb, B, C);
     const int cchunk = (C + csplit - 1) / csplit; csplit = (C + cchunk - 1) / cchunk;
     if (x_plane) hipLaunchKernelGGL((stn_fwd_ex_kernel<true>), dim3(pb, csplit, B), dim3(256), 0, stream, x, theta, y, C, Hin, Win,
                                     Hout, Wout, align_corners, cchunk, xB, theta_G);
@@ -382,6 +396,7 @@ int mogan_stn_bwd_ex(const float* dy, const float* theta, float* dx, int B, int 
     if (B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || B > 65535 || xB <= 0 || B % xB != 0 ||
         theta_G < 0 || (theta_G > 0 && B % theta_G != 0))
         return MOGAN_ERR_SHAPE;
+    if (!dy || !theta || !dx || !plane_fits(Hin, Win) || !plane_fits(Hout, Wout)) return MOGAN_ERR_SHAPE;
     if (x_plane) {
         hipLaunchKernelGGL(stn_bwd_plane_kernel, dim3(C, xB), dim3(256), 0, stream, dy, theta, dx, B, C, Hin, Win, Hout, Wout,
                            align_corners, xB, theta_G);
@@ -395,7 +410,7 @@ int mogan_stn_bwd_ex(const float* dy, const float* theta, float* dx, int B, int 
 }
 
 int mogan_bbox_to_theta(const float* bbox, float* theta, float* theta_inv, int N, hipStream_t stream) {
-    if (N <= 0) return MOGAN_ERR_SHAPE;
+    if (N <= 0 || !bbox || !theta || !theta_inv) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(bbox_to_theta_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, bbox, theta, theta_inv, N);
     return ok_launch();
 }
@@ -403,6 +418,7 @@ int mogan_bbox_to_theta(const float* bbox, float* theta, float* theta_inv, int N
 int mogan_attn_fwd(const float* h, const float* src, const uint8_t* mask, float* wc, float* attn, int B, int idf,
                    int Q, int T, int mask_mode, hipStream_t stream) {
     if (B <= 0 || idf <= 0 || idf > 128 || Q <= 0 || T <= 0 || T > 32 || B > 65535) return MOGAN_ERR_SHAPE;
+    if (!h || !src || !wc || !attn) return MOGAN_ERR_SHAPE;                  // (mask is nullable)
     dim3 grid((Q + 255) / 256, B);
     const size_t sh = (size_t)idf * (T <= 8 ? 8 : T <= 16 ? 16 : 32) * sizeof(float);
     if (T <= 8) hipLaunchKernelGGL((attn_fwd_kernel<8>), grid, dim3(256), sh, stream, h, src, mask, wc, attn, B, idf, Q, T, mask_mode);
@@ -414,6 +430,7 @@ int mogan_attn_fwd(const float* h, const float* src, const uint8_t* mask, float*
 int mogan_attn_bwd(const float* src, const float* attn, const float* dwc, const float* dattn, float* dh,
                    float* dscore, int B, int idf, int Q, int T, hipStream_t stream) {
     if (B <= 0 || idf <= 0 || idf > 128 || Q <= 0 || T <= 0 || T > 32 || B > 65535) return MOGAN_ERR_SHAPE;
+    if (!src || !attn || !dwc || !dh || !dscore) return MOGAN_ERR_SHAPE;     // (dattn is nullable)
     dim3 grid((Q + 255) / 256, B);
     const size_t sh = (size_t)idf * (T <= 8 ? 8 : T <= 16 ? 16 : 32) * sizeof(float);
     if (T <= 8) hipLaunchKernelGGL((attn_bwd_kernel<8>), grid, dim3(256), sh, stream, src, attn, dwc, dattn, dh, dscore, idf, Q, T);
