@@ -702,6 +702,22 @@ int mogan_damsm_sent_bwd_text(const float* cnn, const float* rnn, const float* d
 int mogan_retrieval_rank(const float* code, const float* pos, const float* bank, const int32_t* idx, int Q, int Rn, int C,
                          long long N, float eps, float* score, int32_t* rank, hipStream_t stream);
 
+/* fp64 moments of a set of feature codes: what the Frechet distance is computed from (the reference has no code for it --
+ * DESIGN.md section 9d; csrc/mogan_stats.hip).  x is fp32 (N, D), dense, widened exactly; mean (D) and cov (D, D) are fp64 -- the
+ * only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from workgroup to workgroup: every sum over n runs in
+ * one fixed order, so the same inputs give the same bits on every call.
+ *   mean[j]   = (sum_n (double)x[n][j]) / N
+ *   cov[i][j] = (sum_n (x[n][i] - mean[i]) (x[n][j] - mean[j])) / (N - 1)       (numpy.cov(x, rowvar=False))
+ * mogan_cov_f64 centres in fp64 with the caller's mean (mogan_col_mean_f64's, for the covariance), forms products and sums on
+ * v_mfma_f64_16x16x4_f64 for the 64 x 64 tiles on and above the diagonal, ends with a true division by N - 1 and writes every
+ * element and its mirror image from one register: cov[i][j] and cov[j][i] have the same bits.  Rows past N and columns past D enter
+ * the last tiles as zeros and are never stored.
+ * Limits of the index arithmetic: N <= 2^31 - 1, D <= 65536 (x is indexed in 64 bits; the covariance grid holds
+ * ceil(D / 64) (ceil(D / 64) + 1) / 2 <= 524 800 blocks).
+ * MOGAN_ERR_SHAPE before any HIP call: a NULL x / mean / cov, D < 1, D > 65536, N > 2^31 - 1, N < 1 (mean) or N < 2 (cov). */
+int mogan_col_mean_f64(const float* x, long long N, int D, double* mean, hipStream_t stream);
+int mogan_cov_f64(const float* x, const double* mean, long long N, int D, double* cov, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,7 +51,17 @@ def parse_args(argv=None):
                              'split (condGANTrainer.r_precision) -> <NET_G minus .pth>/<split>/r_precision.json')
     parser.add_argument('--real', action='store_true',
                         help='with --r_precision: score the real images instead of generated ones (the ceiling of the encoder pair)')
-    return parser.parse_args(argv)
+    parser.add_argument('--fid', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): Frechet distance between the Inception pool codes of the real images and of '
+                             'TRAIN.NET_G\'s images under the trunk of TRAIN.NET_E\'s image encoder (condGANTrainer.fid) -> '
+                             '<NET_G minus .pth>/<split>/fid.json; not together with --sampling or --r_precision')
+    parser.add_argument('--fid_stats', type=str, default=None, metavar='PATH',
+                        help='with --fid: the real images\' statistics as an .npz -- loaded when it exists and was taken under the same '
+                             'trunk, computed and saved there otherwise')
+    args = parser.parse_args(argv)
+    if args.fid and (args.sampling or args.r_precision):
+        parser.error('--fid cannot be combined with --sampling or --r_precision')
+    return args
 
 
 def main(argv=None):
@@ -102,7 +112,7 @@ def main(argv=None):
         output_dir = args.resume
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
-    with_bbox = evaluate and not (args.sampling or args.r_precision)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -125,6 +135,8 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
+    elif args.fid:
+        algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats)
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:

@@ -217,13 +217,13 @@ class CNN_ENCODER(nn.Module):
         they then run under autograd on the trunk's outputs)"""
         return inception.FAST_TRUNK and not self.training and not any(p.requires_grad for p in self.trunk_parameters())
 
-    def forward(self, x):
+    def _trunk_walk(self, x):
+        """the one copy of the trunk walk: images -> (the 17 x 17 x 768 map, the pooled (B, 2048) vector)"""
         x = ops.bilinear_resize(x, 299, 299)
         if self._frozen():
             # the train step's case (trainer.py:62-66): explicit forward/backward over the folded, grouped trunk
             features, x = inception.frozen_trunk(self, x)
-            x = ops.avg_pool2d(x, 8).view(x.size(0), -1)
-            return self.emb_features(features), self.emb_cnn_code(x)
+            return features, ops.avg_pool2d(x, 8).view(x.size(0), -1)
         x = self.Conv2d_2b_3x3(self.Conv2d_2a_3x3(self.Conv2d_1a_3x3(x)))
         x = ops.max_pool2d(x, 3, 2)
         x = self.Conv2d_4a_3x3(self.Conv2d_3b_1x1(x))
@@ -233,8 +233,16 @@ class CNN_ENCODER(nn.Module):
         features = x                                                   # 17 x 17 x 768
         for name in ("Mixed_7a", "Mixed_7b", "Mixed_7c"):
             x = getattr(self, name)(x)
-        x = ops.avg_pool2d(x, 8).view(x.size(0), -1)                   # 2048
-        return self.emb_features(features), self.emb_cnn_code(x)
+        return features, ops.avg_pool2d(x, 8).view(x.size(0), -1)      # 2048
+
+    def pool_code(self, x):
+        """the pooled (B, 2048) vector `forward` hands to emb_cnn_code -- Inception-v3's pool3 feature, what the Frechet distance of
+        DESIGN.md section 9d is defined on -- on the frozen fast path when _frozen() holds, on the module path otherwise"""
+        return self._trunk_walk(x)[1]
+
+    def forward(self, x):
+        features, code = self._trunk_walk(x)
+        return self.emb_features(features), self.emb_cnn_code(code)
 
 
 # --------------------------------------------------------------------------- generator

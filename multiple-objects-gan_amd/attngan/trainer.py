@@ -1638,6 +1638,90 @@ class condGANTrainer(object):
                          "rank": rank, "bank": bank.bank.cpu()}
         return out
 
+    def fid(self, split_dir, num_samples=30000, seed=100, stats_path=None, return_codes=False):
+        """Frechet distance between real and generated images of the checkpoint TRAIN.NET_G in the Inception pool codes of
+        TRAIN.NET_E's image encoder: in ONE pass over the data loader the real 256x256 image and one generated
+        256x256 image per caption (EMA generator, eval mode, noise from the seeded device generator exactly as r_precision draws it)
+        go through CNN_ENCODER.pool_code; the codes stay on the device in two preallocated (num_samples, 2048) fp32 buffers, their
+        fp64 mean and covariance come from hip/ops.feature_moments after the loop and the distance from fid.frechet_distance on
+        the host.  With `stats_path` the real side is loaded from that file when it exists and was taken under the same trunk
+        (the real images then skip the trunk), and computed and saved there otherwise.  With a trunk that holds torchvision's
+        ImageNet weights the figure is FID under torchvision's Inception-v3; with a random-init trunk it is a Frechet distance in
+        random convolutional features, comparable between checkpoints under the same trunk only.
+        Writes <NET_G minus .pth>/<split>/fid.json and returns its content; with return_codes also a dict of the two code matrices
+        on the host, "real" (None where the real side was loaded) and "fake"."""
+        import json
+        from .datasets import prepare_data
+        from .fid import FeatureStats, frechet_distance, trunk_digest
+        if cfg.TRAIN.NET_G == '':
+            print('Error: the path for model NET_G is not found!')
+            return None
+        if split_dir == 'test':
+            split_dir = 'valid'
+        torch.manual_seed(seed)
+        netG, text_encoder = self._load_eval_models()
+        image_encoder = self._load_image_encoder()
+        save_dir = '%s/%s' % (cfg.TRAIN.NET_G[:cfg.TRAIN.NET_G.rfind('.pth')], split_dir)
+        mkdir_p(save_dir)
+        D = int(image_encoder.emb_cnn_code.weight.shape[1])                 # 2048: the pooled code's width
+        digest = trunk_digest(image_encoder)
+        real_stats = None
+        if stats_path is not None and os.path.isfile(stats_path):
+            real_stats = FeatureStats.load(stats_path, digest, D)           # ValueError for another trunk's file
+            print('Load real-image statistics from: %s (%d images)' % (stats_path, real_stats.n))
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(seed)
+        rows = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        fake_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device)
+        real_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device) if real_stats is None else None
+        n = 0
+        for data in self.data_loader:
+            if n >= rows:
+                break
+            imgs, captions, cap_lens, class_ids, keys, (tm, tmi), label_one_hot = prepare_data(data, self.device)
+            B = captions.shape[0]
+            take = min(B, rows - n)
+            with torch.no_grad():
+                words_embs, sent_emb = text_encoder(captions, cap_lens.cpu(), text_encoder.init_hidden(B))
+                mask = (captions == 0)
+                if mask.size(1) > words_embs.size(2):
+                    mask = mask[:, :words_embs.size(2)]
+                noise = torch.randn(B, cfg.GAN.Z_DIM, device=self.device, generator=gen)
+                eps = torch.randn(B, cfg.GAN.CONDITION_DIM, device=self.device, generator=gen)
+                fake_imgs, _, _, _ = netG(noise, sent_emb.contiguous(), words_embs.contiguous(), mask, tmi, label_one_hot, eps=eps)
+                fake_codes[n:n + take] = image_encoder.pool_code(fake_imgs[-1])[:take]
+                if real_codes is not None:
+                    real_codes[n:n + take] = image_encoder.pool_code(imgs[-1])[:take]
+            n += take
+        if n < 2:
+            raise ValueError("fid: the data loader gave %d images; a covariance needs two at least" % n)
+        fake_stats = FeatureStats(*[t.cpu() for t in ops.feature_moments(fake_codes[:n])], n, digest)
+        if real_stats is None:
+            real_stats = FeatureStats(*[t.cpu() for t in ops.feature_moments(real_codes[:n])], n, digest)
+            if stats_path is not None:
+                real_stats.save(stats_path)
+                print('Save real-image statistics to: %s' % stats_path)
+        dist, terms = frechet_distance(real_stats.mean, real_stats.cov, fake_stats.mean, fake_stats.cov)
+        few = min(real_stats.n, fake_stats.n)
+        note = ("Frechet distance of Inception pool codes under the trunk of NET_E's image encoder: FID under torchvision's "
+                "Inception-v3 if that trunk holds ImageNet weights (published figures mostly use the TF-ported network), a distance "
+                "in random convolutional features -- comparable between checkpoints under this trunk only -- if it is random-init.")
+        if few < D:
+            note += (" n = %d < %d features: the covariances are rank-deficient, so the figure is biased and only comparable "
+                     "at equal n." % (few, D))
+            print("FID: %d images for %d features -- the covariances are rank-deficient, the figure is biased and only comparable "
+                  "at equal n (the JSON records it)" % (few, D))
+        out = {"fid": dist, "n_real": int(real_stats.n), "n_fake": int(fake_stats.n), "seed": int(seed), "NET_G": cfg.TRAIN.NET_G,
+               "NET_E": cfg.TRAIN.NET_E, "trunk_digest": digest, "note": note}
+        out.update(terms)
+        with open('%s/fid.json' % save_dir, 'w') as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+        print("FID (%d real, %d generated images): %.4f = |dmu|^2 %.4f + Tr S_real %.4f + Tr S_fake %.4f - 2 x %.4f -> %s/fid.json"
+              % (out["n_real"], out["n_fake"], dist, terms["mean_sq"], terms["tr_s1"], terms["tr_s2"], terms["tr_sqrt"], save_dir))
+        if return_codes:
+            return out, {"real": None if real_codes is None else real_codes[:n].cpu(), "fake": fake_codes[:n].cpu()}
+        return out
+
     def sample(self, split_dir, num_samples=25, draw_bbox=False):
         """trainer.py:474-579 (what main.py:158 runs for B_VALIDATION): for the first `num_samples` batches of an
         eval-mode loader take the FIRST sample of the sorted batch, generate nine 256x256 images for its caption /

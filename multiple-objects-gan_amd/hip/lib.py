@@ -141,6 +141,8 @@ SIGNATURES = {
     "mogan_gru_encoder_train_fwd": [P] * 9 + [F] + [P] * 6 + [I] * 6 + [P],
     "mogan_gru_encoder_bwd": [P] * 11 + [I] * 3 + [P],
     "mogan_retrieval_rank": [P, P, P, P, I, I, I, L, F, P, P, P],
+    "mogan_col_mean_f64": [P, L, I, P, P],
+    "mogan_cov_f64": [P, P, L, I, P, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }

@@ -1744,6 +1744,28 @@ def retrieval_rank(code, pos, bank, idx, eps=1e-8, want_scores=False):
     return (rank, score) if want_scores else rank
 
 
+def feature_moments(codes):
+    """fp64 mean (D,) and covariance (D, D) -- numpy.cov(rowvar=False), divisor N - 1 -- of fp32 codes (N, D) on the device, in two
+    launches (mogan_col_mean_f64, mogan_cov_f64: fp64 MFMA, fixed summation order, cov bitwise symmetric).  No gradient.  Nothing is
+    converted or copied for the caller: a wrong dtype or rank, N < 2 or a non-contiguous input is a ValueError."""
+    if not torch.is_tensor(codes) or codes.dtype != torch.float32:
+        raise ValueError("feature_moments: fp32 codes expected, got %s" % (getattr(codes, "dtype", type(codes)),))
+    if codes.dim() != 2:
+        raise ValueError("feature_moments: codes (N, D) expected, got %s" % (tuple(codes.shape),))
+    N, D = codes.shape
+    if N < 2 or D < 1:
+        raise ValueError("feature_moments: at least 2 codes of at least 1 feature expected, got %s" % (tuple(codes.shape),))
+    if not codes.is_contiguous():
+        raise ValueError("feature_moments: contiguous codes expected (strides %s)" % (tuple(codes.stride()),))
+    codes = codes.detach()
+    x = ptr(codes)
+    mean = torch.empty((D,), dtype=torch.float64, device=codes.device)
+    cov = torch.empty((D, D), dtype=torch.float64, device=codes.device)
+    call("mogan_col_mean_f64", x, N, D, ptr(mean), stream_ptr())
+    call("mogan_cov_f64", x, ptr(mean), N, D, ptr(cov), stream_ptr())
+    return mean, cov
+
+
 class ScalarSumFn(torch.autograd.Function):
     """sum_k w_k * x_k over up to 8 zero-dim device scalars in ONE launch (forward) / one launch (backward): the loss sums
     of miscc/losses.py:169-174,203,221 and trainer.py:330 otherwise cost a chain of 0-dim aten kernels each way."""
