@@ -703,9 +703,9 @@ int mogan_retrieval_rank(const float* code, const float* pos, const float* bank,
                          long long N, float eps, float* score, int32_t* rank, hipStream_t stream);
 
 /* fp64 moments of a set of feature codes: what the Frechet distance is computed from (the reference has no code for it --
- * DESIGN.md section 9d; csrc/mogan_stats.hip).  x is fp32 (N, D), dense, widened exactly; mean (D) and cov (D, D) are fp64 -- the
- * only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from workgroup to workgroup: every sum over n runs in
- * one fixed order, so the same inputs give the same bits on every call.
+ * DESIGN.md section 9d; csrc/mogan_stats.hip).  x is fp32 (N, D), dense, widened exactly; mean (D) and cov (D, D) are fp64 -- with
+ * the sums of mogan_poly3_mmd_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
+ * workgroup to workgroup: every sum over n runs in one fixed order, so the same inputs give the same bits on every call.
  *   mean[j]   = (sum_n (double)x[n][j]) / N
  *   cov[i][j] = (sum_n (x[n][i] - mean[i]) (x[n][j] - mean[j])) / (N - 1)       (numpy.cov(x, rowvar=False))
  * mogan_cov_f64 centres in fp64 with the caller's mean (mogan_col_mean_f64's, for the covariance), forms products and sums on
@@ -717,6 +717,26 @@ int mogan_retrieval_rank(const float* code, const float* pos, const float* bank,
  * MOGAN_ERR_SHAPE before any HIP call: a NULL x / mean / cov, D < 1, D > 65536, N > 2^31 - 1, N < 1 (mean) or N < 2 (cov). */
 int mogan_col_mean_f64(const float* x, long long N, int D, double* mean, hipStream_t stream);
 int mogan_cov_f64(const float* x, const double* mean, long long N, int D, double* cov, hipStream_t stream);
+
+/* The sums of the kernel Inception distance (csrc/mogan_mmd.hip; the reference has no code for it): for S
+ * subset pairs of s rows of x (Nx, D) and s rows of y (Ny, D), fp32, dense, widened exactly, gathered through the int32 tables
+ * ix (S, s) and iy (S, s), under k(a, b) = (gamma <a, b> + coef0)^3:
+ *   sums[k][0] = sum_{i != j} k(x_ix[k][i], x_ix[k][j])       ordered pairs, i != j by POSITION in the subset
+ *   sums[k][1] = sum_{i != j} k(y_iy[k][i], y_iy[k][j])
+ *   sums[k][2] = sum_{i, j}   k(x_ix[k][i], y_iy[k][j])
+ * sums (S, 3) is fp64.  Products and sums over the features run on v_mfma_f64_16x16x4_f64 in index order, one 64 x 64 tile of one
+ * subset's kernel matrix per workgroup (for xx / yy only the tiles on and above the diagonal, doubled; a diagonal tile keeps
+ * i < j); t = acc * gamma + coef0, value (t * t) * t, no pow, no contraction.  No kernel matrix is ever written: a workgroup
+ * reduces its tile in a fixed order to ONE double in ws[subset][tile] and a second launch of the same call adds a subset's tile
+ * partials in tile order.  No atomics: the same inputs give the same bits on every call, and a subset's sums do not depend on
+ * which other subsets share the call.  Index entries outside [0, N) are clamped to [0, N - 1] (as mogan_retrieval_rank does).
+ * The workspace is required: mogan_poly3_mmd_ws_bytes(S, s) = S * (2 T^2 + T) * 8 bytes, T = ceil(s / 64), 8-byte aligned (0 for an
+ * S or s the call rejects); MOGAN_ERR_WS where ws is NULL, misaligned or shorter, nothing launched.
+ * MOGAN_ERR_SHAPE before any HIP call (and before the workspace is looked at): a NULL x / y / ix / iy / sums, S < 1, S > 65535 (the
+ * grid), s < 2, s > 2^20, D < 1, D > 65536, Nx or Ny < 1 or > 2^31 - 1, a non-finite gamma or coef0. */
+size_t mogan_poly3_mmd_ws_bytes(int S, int s);
+int mogan_poly3_mmd_f64(const float* x, long long Nx, const float* y, long long Ny, int D, const int32_t* ix, const int32_t* iy,
+                        int S, int s, double gamma, double coef0, double* sums, void* ws, size_t ws_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -58,9 +58,18 @@ def parse_args(argv=None):
     parser.add_argument('--fid_stats', type=str, default=None, metavar='PATH',
                         help='with --fid: the real images\' statistics as an .npz -- loaded when it exists and was taken under the same '
                              'trunk, computed and saved there otherwise')
+    parser.add_argument('--kid', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): kernel Inception distance between the same pool codes (condGANTrainer.kid: '
+                             'unbiased, no dependence on the number of images) -> <NET_G minus .pth>/<split>/kid.json; with --fid both '
+                             'scores come from one pass; not together with --sampling or --r_precision')
+    parser.add_argument('--kid_subsets', type=int, default=100, metavar='N', help='with --kid: number of random subset pairs')
+    parser.add_argument('--kid_subset_size', type=int, default=1000, metavar='N',
+                        help='with --kid: codes per subset (lowered to the number of images where there are fewer)')
     args = parser.parse_args(argv)
     if args.fid and (args.sampling or args.r_precision):
         parser.error('--fid cannot be combined with --sampling or --r_precision')
+    if args.kid and (args.sampling or args.r_precision):
+        parser.error('--kid cannot be combined with --sampling or --r_precision')
     return args
 
 
@@ -112,7 +121,7 @@ def main(argv=None):
         output_dir = args.resume
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
-    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -135,8 +144,15 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
+    elif args.fid and args.kid:
+        codes = algo.pool_codes(split_dir, seed=args.manualSeed)                    # one pass over the loader and the trunk for both
+        if codes is not None:
+            algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats, codes=codes)
+            algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size, codes=codes)
     elif args.fid:
         algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats)
+    elif args.kid:
+        algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size)
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:

@@ -1638,42 +1638,32 @@ class condGANTrainer(object):
                          "rank": rank, "bank": bank.bank.cpu()}
         return out
 
-    def fid(self, split_dir, num_samples=30000, seed=100, stats_path=None, return_codes=False):
-        """Frechet distance between real and generated images of the checkpoint TRAIN.NET_G in the Inception pool codes of
-        TRAIN.NET_E's image encoder: in ONE pass over the data loader the real 256x256 image and one generated
-        256x256 image per caption (EMA generator, eval mode, noise from the seeded device generator exactly as r_precision draws it)
-        go through CNN_ENCODER.pool_code; the codes stay on the device in two preallocated (num_samples, 2048) fp32 buffers, their
-        fp64 mean and covariance come from hip/ops.feature_moments after the loop and the distance from fid.frechet_distance on
-        the host.  With `stats_path` the real side is loaded from that file when it exists and was taken under the same trunk
-        (the real images then skip the trunk), and computed and saved there otherwise.  With a trunk that holds torchvision's
-        ImageNet weights the figure is FID under torchvision's Inception-v3; with a random-init trunk it is a Frechet distance in
-        random convolutional features, comparable between checkpoints under the same trunk only.
-        Writes <NET_G minus .pth>/<split>/fid.json and returns its content; with return_codes also a dict of the two code matrices
-        on the host, "real" (None where the real side was loaded) and "fake"."""
-        import json
+    def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True):
+        """The one pass over the data loader that fid() and kid() share: the real 256x256 image and one generated 256x256 image per
+        caption (EMA generator, eval mode, noise from the seeded device generator exactly as r_precision draws it) go through
+        CNN_ENCODER.pool_code; the codes stay on the device in two preallocated (num_samples, 2048) fp32 buffers.  `want_real`
+        False leaves the real images out of the trunk; it may also be a callable (trunk digest, code width) -> bool, asked once the
+        image encoder is loaded and before the pass (fid() decides there whether a statistics file replaces the real side).
+        `split_dir` names the split the data loader was built for; the pass itself reads the loader only.
+        Returns a dict: "real" (None where not wanted) and "fake", the device buffers, of which the first "n" rows are filled;
+        "trunk_digest"; the "seed" the pass ran under.  None, with fid()'s message, where TRAIN.NET_G is empty."""
         from .datasets import prepare_data
-        from .fid import FeatureStats, frechet_distance, trunk_digest
+        from .fid import trunk_digest
         if cfg.TRAIN.NET_G == '':
             print('Error: the path for model NET_G is not found!')
             return None
-        if split_dir == 'test':
-            split_dir = 'valid'
         torch.manual_seed(seed)
         netG, text_encoder = self._load_eval_models()
         image_encoder = self._load_image_encoder()
-        save_dir = '%s/%s' % (cfg.TRAIN.NET_G[:cfg.TRAIN.NET_G.rfind('.pth')], split_dir)
-        mkdir_p(save_dir)
         D = int(image_encoder.emb_cnn_code.weight.shape[1])                 # 2048: the pooled code's width
         digest = trunk_digest(image_encoder)
-        real_stats = None
-        if stats_path is not None and os.path.isfile(stats_path):
-            real_stats = FeatureStats.load(stats_path, digest, D)           # ValueError for another trunk's file
-            print('Load real-image statistics from: %s (%d images)' % (stats_path, real_stats.n))
+        if callable(want_real):
+            want_real = want_real(digest, D)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
         rows = max(1, min(int(num_samples), len(self.data_loader.dataset)))
         fake_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device)
-        real_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device) if real_stats is None else None
+        real_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device) if want_real else None
         n = 0
         for data in self.data_loader:
             if n >= rows:
@@ -1693,6 +1683,57 @@ class condGANTrainer(object):
                 if real_codes is not None:
                     real_codes[n:n + take] = image_encoder.pool_code(imgs[-1])[:take]
             n += take
+        return {"real": real_codes, "fake": fake_codes, "n": n, "trunk_digest": digest, "seed": int(seed)}
+
+    @staticmethod
+    def _eval_save_dir(split_dir):
+        """<NET_G minus .pth>/<split> of the evaluation scores ('test' reads the 'valid' split), created"""
+        if split_dir == 'test':
+            split_dir = 'valid'
+        save_dir = '%s/%s' % (cfg.TRAIN.NET_G[:cfg.TRAIN.NET_G.rfind('.pth')], split_dir)
+        mkdir_p(save_dir)
+        return save_dir
+
+    @staticmethod
+    def _check_handed_codes(who, codes, seed):
+        if int(codes["seed"]) != int(seed):
+            raise ValueError("%s: the codes were taken under seed %d, not %d" % (who, codes["seed"], seed))
+
+    def fid(self, split_dir, num_samples=30000, seed=100, stats_path=None, return_codes=False, codes=None):
+        """Frechet distance between real and generated images of the checkpoint TRAIN.NET_G in the Inception pool codes of
+        TRAIN.NET_E's image encoder: the codes of ONE pass over the data loader (pool_codes; or the `codes`
+        a caller hands over from a pass of its own, which kid() can share) stay on the device, their
+        fp64 mean and covariance come from hip/ops.feature_moments after the loop and the distance from fid.frechet_distance on
+        the host.  With `stats_path` the real side is loaded from that file when it exists and was taken under the same trunk
+        (the real images then skip the trunk), and computed and saved there otherwise.  With a trunk that holds torchvision's
+        ImageNet weights the figure is FID under torchvision's Inception-v3; with a random-init trunk it is a Frechet distance in
+        random convolutional features, comparable between checkpoints under the same trunk only.
+        Writes <NET_G minus .pth>/<split>/fid.json and returns its content; with return_codes also a dict of the two code matrices
+        on the host, "real" (None where the real side was loaded) and "fake"."""
+        import json
+        from .fid import FeatureStats, frechet_distance
+        if cfg.TRAIN.NET_G == '':
+            print('Error: the path for model NET_G is not found!')
+            return None
+        loaded = []
+
+        def want_real(digest, D):
+            if stats_path is not None and os.path.isfile(stats_path):
+                loaded.append(FeatureStats.load(stats_path, digest, D))     # ValueError for another trunk's file
+                print('Load real-image statistics from: %s (%d images)' % (stats_path, loaded[0].n))
+            return not loaded
+        if codes is None:
+            codes = self.pool_codes(split_dir, num_samples, seed, want_real)
+        else:
+            self._check_handed_codes("fid", codes, seed)
+            want_real(codes["trunk_digest"], int(codes["fake"].shape[1]))
+        save_dir = self._eval_save_dir(split_dir)
+        real_stats = loaded[0] if loaded else None
+        real_codes = codes["real"] if real_stats is None else None
+        fake_codes, n, digest = codes["fake"], codes["n"], codes["trunk_digest"]
+        D = int(fake_codes.shape[1])
+        if real_stats is None and real_codes is None:
+            raise ValueError("fid: the codes handed over hold no real side and there is no statistics file")
         if n < 2:
             raise ValueError("fid: the data loader gave %d images; a covariance needs two at least" % n)
         fake_stats = FeatureStats(*[t.cpu() for t in ops.feature_moments(fake_codes[:n])], n, digest)
@@ -1720,6 +1761,54 @@ class condGANTrainer(object):
               % (out["n_real"], out["n_fake"], dist, terms["mean_sq"], terms["tr_s1"], terms["tr_s2"], terms["tr_sqrt"], save_dir))
         if return_codes:
             return out, {"real": None if real_codes is None else real_codes[:n].cpu(), "fake": fake_codes[:n].cpu()}
+        return out
+
+    def kid(self, split_dir, num_samples=30000, seed=100, subsets=100, subset_size=1000, codes=None, return_codes=False):
+        """Kernel Inception distance between real and generated images of the checkpoint TRAIN.NET_G in the Inception pool codes
+        of TRAIN.NET_E's image encoder: the unbiased estimate of the squared maximum mean discrepancy under
+        k(a, b) = (<a, b> / D + 1)^3, averaged over `subsets` random subset pairs of `subset_size` codes each (kid.draw_subsets
+        under `seed`; the size is lowered to the number of images where there are fewer).  The codes are those of fid() -- ONE
+        pass over the data loader (pool_codes), or the `codes` a caller hands over from a pass of its own -- and stay on the device;
+        the three sums per subset pair come from hip/ops.poly_mmd_sums in one call, the figure from kid.kid_from_sums on the host.
+        Unlike the Frechet distance the estimator has no bias that depends on n; it may be negative.  The real images always go
+        through the trunk.  Writes <NET_G minus .pth>/<split>/kid.json and returns its content; with return_codes also a dict of
+        the two code matrices on the host, "real" and "fake"."""
+        import json
+        from . import kid as KID
+        if cfg.TRAIN.NET_G == '':
+            print('Error: the path for model NET_G is not found!')
+            return None
+        if codes is None:
+            codes = self.pool_codes(split_dir, num_samples, seed, True)
+        else:
+            self._check_handed_codes("kid", codes, seed)
+        if codes["real"] is None:
+            raise ValueError("kid: the codes handed over hold no real side")
+        save_dir = self._eval_save_dir(split_dir)
+        n, digest = codes["n"], codes["trunk_digest"]
+        real_codes, fake_codes = codes["real"][:n], codes["fake"][:n]
+        D = int(fake_codes.shape[1])
+        s = KID.subset_size(n, n, subset_size)
+        ix, iy = KID.draw_subsets(n, n, subsets, s, seed)
+        gamma = 1.0 / D
+        sums = ops.poly_mmd_sums(real_codes, fake_codes, ix, iy, gamma=gamma, coef0=KID.COEF0).cpu().numpy()   # the one read-back
+        mean, std, _ = KID.kid_from_sums(sums, s)
+        note = ("Kernel Inception distance (unbiased MMD^2 under the cubic polynomial kernel, mean over subset pairs) of Inception "
+                "pool codes under the trunk of NET_E's image encoder: KID under torchvision's "
+                "Inception-v3 if that trunk holds ImageNet weights (published figures mostly use the TF-ported network), a distance "
+                "in random convolutional features -- comparable between checkpoints under this trunk only -- if it is random-init.")
+        if s < int(subset_size):
+            note += (" subset_size lowered from %d to %d: there are only %d images per side." % (subset_size, s, n))
+            print("KID: %d images per side -- subsets of %d codes instead of %d (the JSON records it)" % (n, s, subset_size))
+        out = {"kid": mean, "kid_std": std, "subsets": int(subsets), "subset_size": int(s), "n_real": int(n), "n_fake": int(n),
+               "seed": int(seed), "gamma": gamma, "coef0": float(KID.COEF0), "degree": int(KID.DEGREE), "NET_G": cfg.TRAIN.NET_G,
+               "NET_E": cfg.TRAIN.NET_E, "trunk_digest": digest, "note": note}
+        with open('%s/kid.json' % save_dir, 'w') as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+        print("KID (%d real, %d generated images; %d subset pairs of %d): %.6f +- %.6f -> %s/kid.json"
+              % (n, n, out["subsets"], s, mean, std, save_dir))
+        if return_codes:
+            return out, {"real": real_codes.cpu(), "fake": fake_codes.cpu()}
         return out
 
     def sample(self, split_dir, num_samples=25, draw_bbox=False):

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("MOGAN_LIB") or os.path.join(_HERE, "libmogan_hip.so")   # MOGAN_LIB: tools/lab variants
 
-P, I, F, L, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_size_t
+P, I, F, L, Z, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_double
 
 # name -> argtypes (all return int unless listed in _RESTYPE); mirrors include/mogan_hip.h
 SIGNATURES = {
@@ -143,6 +143,8 @@ SIGNATURES = {
     "mogan_retrieval_rank": [P, P, P, P, I, I, I, L, F, P, P, P],
     "mogan_col_mean_f64": [P, L, I, P, P],
     "mogan_cov_f64": [P, P, L, I, P, P],
+    "mogan_poly3_mmd_ws_bytes": [I, I],
+    "mogan_poly3_mmd_f64": [P, L, P, L, I, P, P, I, I, D, D, P, P, Z, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }
@@ -171,7 +173,7 @@ class TailArgs(ctypes.Structure):               # MoganTailArgs
 
 
 _RESTYPE = {"mogan_bn_ws_bytes": Z, "mogan_upconv3x3_ws_bytes": Z, "mogan_pk_weight_bytes": Z, "mogan_pk_panel_bytes": Z,
-            "mogan_wino_prep_bytes": Z, "mogan_conv_prep_bytes": Z}
+            "mogan_wino_prep_bytes": Z, "mogan_conv_prep_bytes": Z, "mogan_poly3_mmd_ws_bytes": Z}
 _ERRORS = {-1: "MOGAN_ERR_SHAPE", -2: "MOGAN_ERR_LAUNCH", -3: "MOGAN_ERR_WS"}
 
 _lib = None

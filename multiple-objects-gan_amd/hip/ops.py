@@ -1766,6 +1766,63 @@ def feature_moments(codes):
     return mean, cov
 
 
+def poly_mmd_sums(x, y, ix, iy, gamma=None, coef0=1.0):
+    """The three sums per subset pair that the kernel Inception distance is formed from (mogan_poly3_mmd_f64: fp64 MFMA, fixed
+    summation order, no kernel matrix written): for fp32 codes x (Nx, D), y (Ny, D) and int32 tables ix, iy (S, s), under
+    k(a, b) = (gamma <a, b> + coef0)^3 with gamma = 1 / D by default, sums (S, 3) fp64 on the device =
+    [sum_{i != j} k(x_ix[k,i], x_ix[k,j]), sum_{i != j} k(y_iy[k,i], y_iy[k,j]), sum_{i,j} k(x_ix[k,i], y_iy[k,j])].
+    No gradient.  Nothing is converted or copied for the caller: a wrong dtype or rank, a non-contiguous input, codes on different
+    devices or of different widths are a ValueError.  ix, iy: int32 device tensors (entries outside [0, N) are clamped by the
+    kernel), or host arrays (numpy), which are checked against [0, N) here -- IndexError -- and uploaded."""
+    import numpy as np
+    for name, t in (("x", x), ("y", y)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError("poly_mmd_sums: fp32 codes expected, %s is %s" % (name, getattr(t, "dtype", type(t))))
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("poly_mmd_sums: codes (N, D) expected, %s is %s" % (name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("poly_mmd_sums: contiguous codes expected (%s has strides %s)" % (name, tuple(t.stride())))
+    if x.shape[1] != y.shape[1]:
+        raise ValueError("poly_mmd_sums: x and y differ in width: %s, %s" % (tuple(x.shape), tuple(y.shape)))
+    if x.device != y.device:
+        raise ValueError("poly_mmd_sums: x and y must be on one device (%s, %s)" % (x.device, y.device))
+    x, y = x.detach(), y.detach()
+    D = x.shape[1]
+    tables = []
+    for name, idx, N in (("ix", ix, x.shape[0]), ("iy", iy, y.shape[0])):
+        if isinstance(idx, np.ndarray):
+            if idx.ndim != 2 or not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError("poly_mmd_sums: %s must be an integer (S, s) table, got %s %s" % (name, idx.dtype, idx.shape))
+            if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= N):
+                raise IndexError("poly_mmd_sums: %s holds rows outside [0, %d): min %d, max %d" % (name, N, idx.min(), idx.max()))
+            ptr(x)                                           # (a host tensor raises here, before anything is uploaded)
+            idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(x.device)
+        if not torch.is_tensor(idx) or idx.dtype != torch.int32 or idx.dim() != 2:
+            raise ValueError("poly_mmd_sums: %s must be int32 (S, s), got %s %s"
+                             % (name, getattr(idx, "dtype", type(idx)), tuple(getattr(idx, "shape", ()))))
+        if idx.device != x.device:
+            raise ValueError("poly_mmd_sums: %s must be on the codes' device (%s, %s)" % (name, idx.device, x.device))
+        tables.append(idx if idx.is_contiguous() else idx.contiguous())
+    ix, iy = tables
+    if ix.shape != iy.shape or ix.shape[0] < 1 or ix.shape[1] < 2:
+        raise ValueError("poly_mmd_sums: ix and iy must share one shape (S >= 1, s >= 2), got %s, %s" % (tuple(ix.shape), tuple(iy.shape)))
+    S, s = ix.shape
+    gamma = 1.0 / D if gamma is None else float(gamma)
+    px, py = ptr(x), ptr(y)
+    need = int(lib.load().mogan_poly3_mmd_ws_bytes(S, s))
+    ws, ws_bytes = workspace(x.device)
+    own = None
+    if ws_bytes < need:                                       # larger than the shared scratch: a tensor of its own
+        own = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+        ws, ws_bytes = own.data_ptr(), own.numel()
+    sums = torch.empty((S, 3), dtype=torch.float64, device=x.device)
+    call("mogan_poly3_mmd_f64", px, x.shape[0], py, y.shape[0], D, ptr(ix), ptr(iy), S, s, gamma, float(coef0), ptr(sums), ws,
+         ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(x.device))
+    return sums
+
+
 class ScalarSumFn(torch.autograd.Function):
     """sum_k w_k * x_k over up to 8 zero-dim device scalars in ONE launch (forward) / one launch (backward): the loss sums
     of miscc/losses.py:169-174,203,221 and trainer.py:330 otherwise cost a chain of 0-dim aten kernels each way."""
