@@ -117,7 +117,12 @@ int mogan_conv2d_fwd(const float* x, const float* w, float* y, int B, int Cin, i
 /* The discriminators' logits head in one launch each way: p (B,Cout) = sigmoid(<x[b], w[co]> + bias[co]) over K = Cin*KH*KW --
  * nn.Conv2d(8 ndf, 1, kernel_size=4, stride=4) (with bias) on a 4x4 map followed by nn.Sigmoid (model.py:626-627, 640-641);
  * x (B,K) and w (Cout,K) dense, K % 4 == 0, Cout <= 4.  Backward from dp and p: dx (B,K) (NULL = not wanted), dw (Cout,K) and
- * db (Cout) written or accumulated (NULL = not wanted; the images are summed in order). */
+ * db (Cout) written or accumulated (NULL = not wanted; the images are summed in order).
+ * MOGAN_ERR_SHAPE before any HIP call: B or K <= 0, Cout outside 1..4, a NULL x / w / p (fwd; bias alone is nullable: no bias) or
+ * dp / p / x / w (bwd; dx / dw / db are nullable); in the forward also K % 4 != 0 and an x or w that is not 16-byte aligned; in the
+ * backward B K >= 2^31.  dx, dw and db all NULL: returns 0 and launches nothing.
+ * tests/test_loss_entry_points_gpu.py holds both entries per element against fp64 (tests/loss_cases.py), under the memory contract
+ * of tests/memguard.py; tests/test_loss_rejections_cpu.py holds the rejections. */
 int mogan_logits_head_fwd(const float* x, const float* w, const float* bias, float* p, int B, int K, int Cout,
                           hipStream_t stream);
 int mogan_logits_head_bwd(const float* dp, const float* p, const float* x, const float* w, float* dx, float* dw, float* db,
@@ -492,6 +497,9 @@ int mogan_attn_bwd(const float* src, const float* attn, const float* dwc, const 
                    float* dscore, int B, int idf, int Q, int T, hipStream_t stream);
 
 /* ---------------------------------------------------------------- losses
+ * Every entry of this section, the matching losses and the optimizer below: MOGAN_ERR_SHAPE before any HIP call for n <= 0 and
+ * for a NULL pointer (none of the pointers of the BCE / KL / reparametrisation entries is nullable).  Per element against fp64,
+ * in guard-banded memory: tests/test_loss_entry_points_gpu.py; the rejections: tests/test_loss_rejections_cpu.py.
  * BCE (mean) of probabilities p[n] against a constant target (nn.BCELoss with torch's log clamp at -100;
  * miscc/losses.py:158-168,198-201): loss[0] (+)= weight * mean(...); bwd: dp = gout[0]*weight/n * d/dp */
 int mogan_bce_fwd(const float* p, float target, float weight, float* loss, int n, int accumulate,
@@ -522,10 +530,19 @@ int mogan_reparam_bwd(const float* logvar, const float* eps, const float* dc, fl
  *   fwd -> sim (B,Bc) = gamma3 * log sum_t exp(gamma2 * cos(word_{i,t}, context_{b,i,t})), and for the backward pass
  *          a1 (B,Bc,S,T) softmax over the words, a2 (B,Bc,T,S) softmax over the regions (= the attention maps of
  *          losses.py:87-91), wc (B,C,Bc,T) weighted contexts, wt (C,Bc,T) the word embeddings in GEMM layout
- *          (nullable).  Limits: T <= 32, (C*T + T*(S+1) + 896) * 4 bytes of LDS <= 64 KB.
+ *          (nullable: not wanted); exactly zero behind each caption's end.
+ *          Limits: T <= 32, (C*T + T*(S+1) + 1088) * 4 bytes of LDS <= 64 KB (1088 = 960 + 128 floats of reduction scratch:
+ *          what the backward needs, and the forward is held to the same figure so that every forward has its backward but for
+ *          the backward's own limit on S).  No limit on S besides: the forward's loops take any S.
+ *          cap_lens[i] is clamped to [0, T]; only the valid words words[i, :, t < cap_lens[i]] enter a result (the slots behind
+ *          them may hold anything, NaN included), and a1, a2, wc, wt (and dwc, dscore_t) are exactly zero at t >= cap_lens[i].
+ *          A caption of length 0 has sim[b,i] = gamma3 * log(0) = -inf (for gamma3 > 0) and zeros in all its other slots.
  *   bwd: dsim (B,Bc) -> dwc (B,C,Bc,T), dscore_t (B,Bc,T,S); the region-feature gradient is then two mogan_bmm calls:
  *          dctx[b] (C,S) = dwc[b] (C, Bc*T) . a2[b] (Bc*T, S)  +  wt (C, Bc*T) . dscore_t[b] (Bc*T, S).
- *        (the image side; the text side is mogan_damsm_words_bwd_text, further down).  S <= 640. */
+ *        (the image side; the text side is mogan_damsm_words_bwd_text, further down).  The backward alone has S <= 640
+ *        (at most two regions per thread).
+ * MOGAN_ERR_SHAPE before any HIP call (fwd and bwd): a dimension <= 0, T > 32, B > 65535, more LDS than 64 KB by the formula
+ * above, a NULL pointer other than wt; in the backward also S > 640. */
 int mogan_damsm_words_fwd(const float* ctx, const float* words, const int32_t* cap_lens, int B, int Bc, int C, int S, int T,
                           float gamma1, float gamma2, float gamma3, float* sim, float* a1, float* a2, float* wc, float* wt,
                           hipStream_t stream);
@@ -535,19 +552,25 @@ int mogan_damsm_words_bwd(const float* ctx, const float* words, const int32_t* c
 /* The two cross-entropies over a square similarity matrix sim (R,R) (losses.py:45-58,116-130): rows against labels
  * (image -> caption) and columns against labels (caption -> image), entries with mask[r,q] != 0 (same class, nullable)
  * set to -inf first.  fwd -> prow, pcol (R,R) softmax probabilities, nll (2R) scratch, out2 = {loss0, loss1} (means).
- * bwd: g0, g1 (device scalars, gradients of loss0 / loss1; nullable = 0) -> dsim (R,R). */
+ * bwd: g0, g1 (device scalars, gradients of loss0 / loss1; nullable = 0) -> dsim (R,R).
+ * labels[r] is clamped to [0, R - 1] on the device, in both directions (like the token ids and the idx of
+ * mogan_retrieval_rank).  A masked entry of sim is not read into any result.
+ * MOGAN_ERR_SHAPE before any HIP call: R or Q <= 0, R != Q, a NULL pointer other than mask / g0 / g1. */
 int mogan_damsm_ce_fwd(const float* sim, const int64_t* labels, const uint8_t* mask, int R, int Q, float* prow,
                        float* pcol, float* nll, float* out2, hipStream_t stream);
 int mogan_damsm_ce_bwd(const float* prow, const float* pcol, const int64_t* labels, const float* g0, const float* g1, int R,
                        int Q, float* dsim, hipStream_t stream);
-/* sent_loss similarity (losses.py:36-44): sim[b,i] = gamma3 * <cnn_b, rnn_i> / max(|cnn_b| |rnn_i|, eps); bwd -> dcnn */
+/* sent_loss similarity (losses.py:36-44): sim[b,i] = gamma3 * <cnn_b, rnn_i> / max(|cnn_b| |rnn_i|, eps); bwd -> dcnn
+ * (where |cnn_b| |rnn_i| < eps: the gradient of the clamped quotient, dsim gamma3 rnn_i / eps).
+ * MOGAN_ERR_SHAPE before any HIP call: B, Bc or C <= 0, a NULL pointer; in the backward also Bc > 8192 (LDS). */
 int mogan_damsm_sent_fwd(const float* cnn, const float* rnn, int B, int Bc, int C, float gamma3, float eps, float* sim,
                          hipStream_t stream);
 int mogan_damsm_sent_bwd(const float* cnn, const float* rnn, const float* dsim, int B, int Bc, int C, float gamma3,
                          float eps, float* dcnn, hipStream_t stream);
 /* out[0] = sum_k weights[k] * in[k][0] for n <= 8 device scalars (the loss sums of losses.py:169-174,203,221 and
  * trainer.py:330 in one launch); scalar_scale is its gradient: out[k][0] = weights[k] * g[0].  `in` / `out` / `weights`
- * are HOST arrays (read during the call). */
+ * are HOST arrays (read during the call).
+ * MOGAN_ERR_SHAPE before any HIP call: n outside 1..8, a NULL in / out / weights / g, a NULL in[k] or out[k] for k < n. */
 int mogan_scalar_sum(const float* const* in, const float* weights, int n, float* out, hipStream_t stream);
 int mogan_scalar_scale(const float* g, const float* weights, int n, float* const* out, hipStream_t stream);
 
@@ -601,7 +624,9 @@ int mogan_feed_resample(const uint8_t* in, uint8_t* tmp, float* out, const int32
  * replaces `step`: the count lives in dev_state[0] and is incremented on the device, so the call can be
  * captured in a hipGraph and replayed.  eps_mode 0: denom = sqrt(v)/sqrt(1-b2^t) + eps (torch>=1.x);
  * 1: denom = sqrt(v) + eps with step size lr*sqrt(1-b2^t)/(1-b1^t) (torch 0.4.1).  grad_scale multiplies g
- * first (1/world_size after an RCCL sum all-reduce). */
+ * first (1/world_size after an RCCL sum all-reduce).  n need not be a multiple of 4: nothing behind element n - 1 is touched.
+ * MOGAN_ERR_SHAPE before any HIP call -- so a rejected call leaves dev_state[0] where it was --: n <= 0, step < 1 without
+ * dev_state, a NULL p / g / m / v, a p / g / m / v / ema that is not 16-byte aligned (ema and dev_state are nullable). */
 int mogan_adam_step(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr, float beta1,
                     float beta2, float eps, int step, float* dev_state, int eps_mode, float grad_scale,
                     float ema_decay, hipStream_t stream);

@@ -346,6 +346,10 @@ __global__ __launch_bounds__(NT) void damsm_words_bwd_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------- cross-entropies
+// a label indexes the softmax axis of n entries: clamped to [0, n - 1] like every other device-side index of this ABI
+__device__ __forceinline__ int clamp_label(int64_t lab, int n) {
+    return (int)(lab < 0 ? 0 : (lab > (int64_t)(n - 1) ? (int64_t)(n - 1) : lab));
+}
 // sim (R x Q).  Block r < R: softmax over the row (image -> caption), CE against labels[r]; block R + q: softmax over
 // column q (caption -> image), CE against labels[q].  Writes the probabilities and per-row / per-column NLL terms.
 __global__ __launch_bounds__(NT2) void damsm_ce_fwd_kernel(const float* __restrict__ sim, const int64_t* __restrict__ labels,
@@ -382,7 +386,7 @@ __global__ __launch_bounds__(NT2) void damsm_ce_fwd_kernel(const float* __restri
         pout[(size_t)br * Q + bq] = __expf(at(k) - m) / z;
     }
     if (tid == 0) {
-        const int lab = (int)labels[r];
+        const int lab = clamp_label(labels[r], n);
         nll[blk] = -(at(lab) - m - lz);
     }
 }
@@ -412,8 +416,8 @@ __global__ __launch_bounds__(NT2) void damsm_ce_bwd_kernel(const float* __restri
     const int idx = blockIdx.x * NT2 + threadIdx.x;
     if (idx >= R * Q) return;
     const int r = idx / Q, q = idx - r * Q;
-    const float a = g0 ? g0[0] * (prow[idx] - ((int)labels[r] == q ? 1.f : 0.f)) / (float)R : 0.f;
-    const float b = g1 ? g1[0] * (pcol[idx] - ((int)labels[q] == r ? 1.f : 0.f)) / (float)Q : 0.f;
+    const float a = g0 ? g0[0] * (prow[idx] - (clamp_label(labels[r], Q) == q ? 1.f : 0.f)) / (float)R : 0.f;
+    const float b = g1 ? g1[0] * (pcol[idx] - (clamp_label(labels[q], R) == r ? 1.f : 0.f)) / (float)Q : 0.f;
     dsim[idx] = a + b;
 }
 
@@ -643,6 +647,8 @@ extern "C" {
 int mogan_damsm_words_fwd(const float* ctx, const float* words, const int32_t* cap_lens, int B, int Bc, int C, int S, int T,
                           float gamma1, float gamma2, float gamma3, float* sim, float* a1, float* a2, float* wc, float* wt,
                           hipStream_t stream) {
+    if (!ctx || !words || !cap_lens || !sim || !a1 || !a2 || !wc) return MOGAN_ERR_SHAPE;      // (wt is nullable: not wanted)
+    // (no limit on S but the LDS bound: the kernel's loops over the regions take any S; S <= 640 is the backward's limit)
     if (B <= 0 || Bc <= 0 || C <= 0 || S <= 0 || T <= 0 || T > TMAX || B > 65535) return MOGAN_ERR_SHAPE;
     const size_t lds = words_lds_bytes(C, S, T);
     if (lds > 64 * 1024) return MOGAN_ERR_SHAPE;
@@ -657,6 +663,7 @@ int mogan_damsm_words_fwd(const float* ctx, const float* words, const int32_t* c
 int mogan_damsm_words_bwd(const float* ctx, const float* words, const int32_t* cap_lens, const float* a1, const float* a2,
                           const float* wc, const float* dsim, int B, int Bc, int C, int S, int T, float gamma1,
                           float gamma2, float gamma3, float* dwc, float* dscore_t, hipStream_t stream) {
+    if (!ctx || !words || !cap_lens || !a1 || !a2 || !wc || !dsim || !dwc || !dscore_t) return MOGAN_ERR_SHAPE;
     if (B <= 0 || Bc <= 0 || C <= 0 || S <= 0 || T <= 0 || T > TMAX || B > 65535 || S > 2 * NT) return MOGAN_ERR_SHAPE;
     const size_t lds = words_lds_bytes(C, S, T);
     if (lds > 64 * 1024) return MOGAN_ERR_SHAPE;
@@ -670,6 +677,7 @@ int mogan_damsm_words_bwd(const float* ctx, const float* words, const int32_t* c
 
 int mogan_damsm_ce_fwd(const float* sim, const int64_t* labels, const uint8_t* mask, int R, int Q, float* prow,
                        float* pcol, float* nll, float* out2, hipStream_t stream) {
+    if (!sim || !labels || !prow || !pcol || !nll || !out2) return MOGAN_ERR_SHAPE;             // (mask is nullable: no mask)
     if (R <= 0 || Q <= 0 || R != Q) return MOGAN_ERR_SHAPE;      // labels index both axes (losses.py:128-130)
     hipLaunchKernelGGL(damsm_ce_fwd_kernel, dim3(R + Q), dim3(NT2), 0, stream, sim, labels, mask, R, Q, prow, pcol, nll);
     hipLaunchKernelGGL(damsm_ce_finish_kernel, dim3(1), dim3(NT2), 0, stream, (const float*)nll, R, Q, out2);
@@ -678,6 +686,7 @@ int mogan_damsm_ce_fwd(const float* sim, const int64_t* labels, const uint8_t* m
 
 int mogan_damsm_ce_bwd(const float* prow, const float* pcol, const int64_t* labels, const float* g0, const float* g1, int R,
                        int Q, float* dsim, hipStream_t stream) {
+    if (!prow || !pcol || !labels || !dsim) return MOGAN_ERR_SHAPE;                             // (g0, g1 are nullable: zero)
     if (R <= 0 || Q <= 0 || R != Q) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(damsm_ce_bwd_kernel, dim3((R * Q + NT2 - 1) / NT2), dim3(NT2), 0, stream, prow, pcol, labels, g0, g1,
                        R, Q, dsim);
@@ -686,6 +695,7 @@ int mogan_damsm_ce_bwd(const float* prow, const float* pcol, const int64_t* labe
 
 int mogan_damsm_sent_fwd(const float* cnn, const float* rnn, int B, int Bc, int C, float gamma3, float eps, float* sim,
                          hipStream_t stream) {
+    if (!cnn || !rnn || !sim) return MOGAN_ERR_SHAPE;
     if (B <= 0 || Bc <= 0 || C <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(damsm_sent_fwd_kernel, dim3(B), dim3(NT2), 0, stream, cnn, rnn, Bc, C, gamma3, eps, sim);
     return ok_launch();
@@ -693,6 +703,7 @@ int mogan_damsm_sent_fwd(const float* cnn, const float* rnn, int B, int Bc, int 
 
 int mogan_damsm_sent_bwd(const float* cnn, const float* rnn, const float* dsim, int B, int Bc, int C, float gamma3,
                          float eps, float* dcnn, hipStream_t stream) {
+    if (!cnn || !rnn || !dsim || !dcnn) return MOGAN_ERR_SHAPE;
     if (B <= 0 || Bc <= 0 || C <= 0 || (size_t)Bc * 2 * sizeof(float) > 64 * 1024) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(damsm_sent_bwd_kernel, dim3(B), dim3(NT2), (size_t)Bc * 2 * sizeof(float), stream, cnn, rnn, dsim, Bc,
                        C, gamma3, eps, dcnn);
@@ -729,7 +740,8 @@ int mogan_retrieval_rank(const float* code, const float* pos, const float* bank,
 }
 
 int mogan_scalar_sum(const float* const* in, const float* weights, int n, float* out, hipStream_t stream) {
-    if (n <= 0 || n > 8) return MOGAN_ERR_SHAPE;
+    if (!in || !weights || !out || n <= 0 || n > 8) return MOGAN_ERR_SHAPE;
+    for (int k = 0; k < n; ++k) if (!in[k]) return MOGAN_ERR_SHAPE;
     ScalarSumP p{};
     p.n = n;
     for (int k = 0; k < n; ++k) { p.in[k] = in[k]; p.w[k] = weights[k]; }
@@ -738,7 +750,8 @@ int mogan_scalar_sum(const float* const* in, const float* weights, int n, float*
 }
 
 int mogan_scalar_scale(const float* g, const float* weights, int n, float* const* out, hipStream_t stream) {
-    if (n <= 0 || n > 8) return MOGAN_ERR_SHAPE;
+    if (!g || !weights || !out || n <= 0 || n > 8) return MOGAN_ERR_SHAPE;
+    for (int k = 0; k < n; ++k) if (!out[k]) return MOGAN_ERR_SHAPE;
     ScalarScaleP p{};
     p.n = n;
     for (int k = 0; k < n; ++k) { p.out[k] = out[k]; p.w[k] = weights[k]; }

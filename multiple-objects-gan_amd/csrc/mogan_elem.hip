@@ -691,48 +691,48 @@ int mogan_softmax_bwd(const float* y, const float* dy, float* dx, const int32_t*
 }
 
 int mogan_bce_fwd(const float* p, float target, float weight, float* loss, int n, int accumulate, hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (!p || !loss || n <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(bce_fwd_kernel, dim3(1), dim3(256), 0, stream, p, target, weight, loss, n, accumulate);
     return ok_launch();
 }
 int mogan_bce_bwd(const float* p, float target, float weight, const float* gout, float* dp, int n, hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (!p || !gout || !dp || n <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(bce_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, p, target, weight, gout, dp, n);
     return ok_launch();
 }
 int mogan_bce_logits_fwd(const float* x, float target, float weight, float* loss, int n, int accumulate,
                          hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (!x || !loss || n <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(bce_logits_fwd_kernel, dim3(1), dim3(256), 0, stream, x, target, weight, loss, n, accumulate);
     return ok_launch();
 }
 int mogan_bce_logits_bwd(const float* x, float target, float weight, const float* gout, float* dx, int n,
                          hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (!x || !gout || !dx || n <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(bce_logits_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, target, weight, gout, dx,
                        n);
     return ok_launch();
 }
 int mogan_kl_fwd(const float* mu, const float* logvar, float* loss, int n, hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (!mu || !logvar || !loss || n <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(kl_fwd_kernel, dim3(1), dim3(256), 0, stream, mu, logvar, loss, n);
     return ok_launch();
 }
 int mogan_kl_bwd(const float* mu, const float* logvar, const float* gout, float* dmu, float* dlogvar, int n,
                  hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (!mu || !logvar || !gout || !dmu || !dlogvar || n <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(kl_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mu, logvar, gout, dmu, dlogvar, n);
     return ok_launch();
 }
 
 int mogan_reparam_fwd(const float* mu, const float* logvar, const float* eps, float* c, int n, hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (!mu || !logvar || !eps || !c || n <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(reparam_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mu, logvar, eps, c, n);
     return ok_launch();
 }
 int mogan_reparam_bwd(const float* logvar, const float* eps, const float* dc, float* dmu, float* dlogvar, int n,
                       hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (!logvar || !eps || !dc || !dmu || !dlogvar || n <= 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(reparam_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, logvar, eps, dc, dmu, dlogvar, n);
     return ok_launch();
 }
@@ -859,13 +859,14 @@ int mogan_bilinear_bwd(const float* dy, float* dx, int planes, int H, int W, int
 int mogan_adam_step(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr, float beta1,
                     float beta2, float eps, int step, float* dev_state, int eps_mode, float grad_scale,
                     float ema_decay, hipStream_t stream) {
-    if (n <= 0 || (!dev_state && step < 1)) return MOGAN_ERR_SHAPE;
+    // every argument check stands in front of the first launch: a rejected call must not advance the device-resident step count
+    if (!p || !g || !m || !v || n <= 0 || (!dev_state && step < 1)) return MOGAN_ERR_SHAPE;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) != 0) return MOGAN_ERR_SHAPE;
     if (dev_state) { hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, stream, dev_state, lr, beta1, beta2, eps_mode); step = 1; }
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     const float step_size = eps_mode == 0 ? (float)(lr / bc1) : (float)(lr * sqrt(bc2) / bc1);
     const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
     const long long n4 = (n + 3) / 4;
-    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) != 0) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(adam_kernel, dim3(nblk(n4)), dim3(256), 0, stream, p, g, m, v, ema, n4, n, beta1, beta2, eps,
                        step_size, inv_sqrt_bc2, eps_mode, grad_scale, ema_decay, (const float*)dev_state);
     return ok_launch();

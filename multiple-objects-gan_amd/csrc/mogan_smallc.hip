@@ -669,6 +669,7 @@ extern "C" {
 
 int mogan_logits_head_fwd(const float* x, const float* w, const float* bias, float* p, int B, int K, int Cout,
                           hipStream_t stream) {
+    if (!x || !w || !p) return MOGAN_ERR_SHAPE;                   // (bias is nullable: no bias)
     if (B <= 0 || K <= 0 || (K & 3) || Cout < 1 || Cout > 4 || ((((uintptr_t)x) | ((uintptr_t)w)) & 15)) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(logits_head_fwd_kernel, dim3((unsigned)(B * Cout)), dim3(256), 0, stream, x, w, bias, p, K, Cout);
     return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH;
@@ -676,6 +677,7 @@ int mogan_logits_head_fwd(const float* x, const float* w, const float* bias, flo
 
 int mogan_logits_head_bwd(const float* dp, const float* p, const float* x, const float* w, float* dx, float* dw, float* db,
                           int B, int K, int Cout, int accumulate, hipStream_t stream) {
+    if (!dp || !p || !x || !w) return MOGAN_ERR_SHAPE;            // (dx, dw, db are nullable: not wanted)
     if (B <= 0 || K <= 0 || Cout < 1 || Cout > 4 || (long long)B * K >= (1ll << 31)) return MOGAN_ERR_SHAPE;
     const unsigned nbx = dx ? (unsigned)(((long long)B * K + 255) / 256) : 0u;
     const unsigned nbw = dw ? (unsigned)((Cout * K + 255) / 256) : 0u;

@@ -335,7 +335,8 @@ def test_stn(ac):
 def test_logits_head_and_conv_lrelu(B, Cin, Cout):
     """mogan_logits_head_fwd / _bwd (full-map Conv2d + bias + Sigmoid, model.py:626-627, 640-641) and mogan_conv2d_lrelu_fwd
     (first discriminator layer: Conv2d(3, ndf, 4, 2, 1) + LeakyReLU(0.2), model.py:597-598) against torch in fp64: value,
-    input gradient, weight / bias gradients -- returned and accumulated into existing .grad buffers."""
+    input gradient, weight / bias gradients -- returned and accumulated into existing .grad buffers.  (The head's two entry
+    points per element and in guarded memory: tests/test_loss_entry_points_gpu.py.)"""
     x = T("lh.x%d" % Cin, (B, Cin, 4, 4)).requires_grad_(True)
     w = T("lh.w%d" % Cin, (Cout, Cin, 4, 4), 0.05).requires_grad_(True)
     b = T("lh.b%d" % Cin, (Cout,), 0.1).requires_grad_(True)
@@ -582,6 +583,8 @@ def test_softmax_masked_and_scaled():
 
 
 def test_losses_bce_kl():
+    """the BCE and KL losses through their autograd wrappers (the entry points per element, with accumulate / weight / gout
+    and the BCE-with-logits and reparametrisation entries: tests/test_loss_entry_points_gpu.py)"""
     p = torch.sigmoid(T("bcep", (16,), 2.0)).requires_grad_(True)
     for tgt in (0.0, 1.0):
         p.grad = None
@@ -659,6 +662,8 @@ def test_bilinear_resize_backward_gather(shape, out):
 
 @pytest.mark.parametrize("eps_mode", [0, 1])
 def test_adam_ema(eps_mode):
+    """three steps of the fused Adam + EMA through ops.adam_step (the entry point per element, every tail length, ema = NULL,
+    grad_scale and the device counter: tests/test_loss_entry_points_gpu.py)"""
     n = 10007
     p, g = T("adp", (n,)), T("adg", (n,), 0.01)
     net = {"w": p.clone().double().requires_grad_(True)}
@@ -685,7 +690,8 @@ def test_adam_ema(eps_mode):
 def test_damsm_words_and_sentence_losses(B, C, hw, Tw, same_class):
     """mogan_damsm_words_fwd/bwd + mogan_damsm_ce_* + mogan_damsm_sent_* (miscc/losses.py:20-132, one func_attention per
     caption in the reference) against the fp64 oracle: both cross-entropies, the attention maps, the gradients w.r.t.
-    the region features / the image code; ragged caption lengths, optional same-class mask, full benchmark size."""
+    the region features / the image code; ragged caption lengths, optional same-class mask, full benchmark size.
+    (Every entry point of the family per element, at every kernel path and in guarded memory: tests/test_loss_entry_points_gpu.py.)"""
     from mogan_amd.attngan.miscc import losses as L
     from mogan_amd.attngan.miscc.config import cfg
     cfg.TRAIN.SMOOTH.GAMMA1, cfg.TRAIN.SMOOTH.GAMMA2, cfg.TRAIN.SMOOTH.GAMMA3 = 4.0, 5.0, 10.0
