@@ -729,7 +729,7 @@ int mogan_retrieval_rank(const float* code, const float* pos, const float* bank,
 
 /* fp64 moments of a set of feature codes: what the Frechet distance is computed from (the reference has no code for it --
  * DESIGN.md section 9d; csrc/mogan_stats.hip).  x is fp32 (N, D), dense, widened exactly; mean (D) and cov (D, D) are fp64 -- with
- * the sums of mogan_poly3_mmd_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
+ * the sums of mogan_poly3_mmd_f64 and the radii of mogan_knn_sqdist_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
  * workgroup to workgroup: every sum over n runs in one fixed order, so the same inputs give the same bits on every call.
  *   mean[j]   = (sum_n (double)x[n][j]) / N
  *   cov[i][j] = (sum_n (x[n][i] - mean[i]) (x[n][j] - mean[j])) / (N - 1)       (numpy.cov(x, rowvar=False))
@@ -762,6 +762,34 @@ int mogan_cov_f64(const float* x, const double* mean, long long N, int D, double
 size_t mogan_poly3_mmd_ws_bytes(int S, int s);
 int mogan_poly3_mmd_f64(const float* x, long long Nx, const float* y, long long Ny, int D, const int32_t* ix, const int32_t* iy,
                         int S, int s, double gamma, double coef0, double* sums, void* ws, size_t ws_bytes, hipStream_t stream);
+
+/* Nearest-neighbour radii and ball membership for precision / recall and density / coverage (DESIGN.md section 9f;
+ * csrc/mogan_knn.hip; the reference has no code for it), on squared Euclidean distances of fp32 rows, dense, widened exactly:
+ *   d2(a, b) = max((|a|^2 + |b|^2) - 2 <a, b>, 0)                                  everything after the load in fp64
+ * <a, b> on v_mfma_f64_16x16x4_f64 in 64 x 64 tiles, K steps along the features in index order; the row norms are the diagonal of
+ * the same tile loop run on a 64-row group against itself (one small launch per set, into the workspace).  A distance's bits
+ * therefore depend on the two rows only -- not on the tile, the wave or which operand a row is: a bit copy of a row is at exactly 0,
+ * d2(i, j) = d2(j, i) bitwise, and a permutation of the rows permutes the results bitwise.  No distance matrix is written, there
+ * are no atomics, and the same inputs give the same bits on every call.
+ * mogan_knn_sqdist_f64: out (N, K) fp64, row i = the K smallest d2(x_i, x_j) over j != i, ascending; j != i by POSITION (a duplicate
+ *   of row i elsewhere is a neighbour at distance 0).  1 <= K <= 8, N >= K + 1.
+ * mogan_ball_count_f64: count (M, R) int32, count[j][c] = #{ i : d2(q_j, p_i) <= r2[.][c] } for queries q (M, D) and support points
+ *   p (N, D); side 0: the radius is the support point's, r2 (N, R) indexed by i; side 1: the query's, r2 (M, R) indexed by j.
+ *   1 <= R <= 4; <= includes equality; a NaN radius counts nothing.
+ * A workgroup owns a stripe of 64 rows / queries and walks the column / support tiles; where the stripes alone would not fill the
+ * device the tiles are split into `shares` = min(ceil(512 / Tr), Tc, 64) parts (Tr, Tc = ceil(rows / 64), ceil(columns / 64)), each
+ * leaving its K smallest / its counts in the workspace, merged by a last launch of the same call (the K smallest of a multiset and a
+ * sum of integers do not depend on the partition).  The workspace is required, 8-byte aligned:
+ *   mogan_knn_sqdist_ws_bytes(N, K)    = 8 (N + shares N K)
+ *   mogan_ball_count_ws_bytes(M, N, R) = 8 (M + N) + 4 shares M R rounded up to 8            (0 for arguments the call rejects)
+ * MOGAN_ERR_WS where ws is NULL, misaligned or shorter, nothing launched.  MOGAN_ERR_SHAPE before any HIP call (and before the
+ * workspace is looked at): a NULL x / out / q / p / r2 / count, K < 1, K > 8, N < K + 1, R < 1, R > 4, M < 1, N < 1, M or N >
+ * 2^31 - 1, D < 1, D > 65536, a side other than 0 / 1. */
+size_t mogan_knn_sqdist_ws_bytes(long long N, int K);
+int mogan_knn_sqdist_f64(const float* x, long long N, int D, int K, double* out, void* ws, size_t ws_bytes, hipStream_t stream);
+size_t mogan_ball_count_ws_bytes(long long M, long long N, int R);
+int mogan_ball_count_f64(const float* q, long long M, const float* p, long long N, int D, const double* r2, int R, int side,
+                         int32_t* count, void* ws, size_t ws_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -65,11 +65,19 @@ def parse_args(argv=None):
     parser.add_argument('--kid_subsets', type=int, default=100, metavar='N', help='with --kid: number of random subset pairs')
     parser.add_argument('--kid_subset_size', type=int, default=1000, metavar='N',
                         help='with --kid: codes per subset (lowered to the number of images where there are fewer)')
+    parser.add_argument('--prdc', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): improved precision / recall and density / coverage between the same pool '
+                             'codes (condGANTrainer.prdc: "collapsed" and "sloppy" told apart) -> <NET_G minus .pth>/<split>/prdc.json; '
+                             'any of --fid --kid --prdc together take one pass; not together with --sampling or --r_precision')
+    parser.add_argument('--prdc_k_pr', type=int, default=3, metavar='K', help='with --prdc: neighbours of precision / recall (1..8)')
+    parser.add_argument('--prdc_k_dc', type=int, default=5, metavar='K', help='with --prdc: neighbours of density / coverage (1..8)')
     args = parser.parse_args(argv)
     if args.fid and (args.sampling or args.r_precision):
         parser.error('--fid cannot be combined with --sampling or --r_precision')
     if args.kid and (args.sampling or args.r_precision):
         parser.error('--kid cannot be combined with --sampling or --r_precision')
+    if args.prdc and (args.sampling or args.r_precision):
+        parser.error('--prdc cannot be combined with --sampling or --r_precision')
     return args
 
 
@@ -121,7 +129,7 @@ def main(argv=None):
         output_dir = args.resume
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
-    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -144,15 +152,21 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
-    elif args.fid and args.kid:
-        codes = algo.pool_codes(split_dir, seed=args.manualSeed)                    # one pass over the loader and the trunk for both
+    elif args.fid + args.kid + args.prdc > 1:
+        codes = algo.pool_codes(split_dir, seed=args.manualSeed)                    # one pass over the loader and the trunk for all
         if codes is not None:
-            algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats, codes=codes)
-            algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size, codes=codes)
+            if args.fid:
+                algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats, codes=codes)
+            if args.kid:
+                algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size, codes=codes)
+            if args.prdc:
+                algo.prdc(split_dir, seed=args.manualSeed, k_pr=args.prdc_k_pr, k_dc=args.prdc_k_dc, codes=codes)
     elif args.fid:
         algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats)
     elif args.kid:
         algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size)
+    elif args.prdc:
+        algo.prdc(split_dir, seed=args.manualSeed, k_pr=args.prdc_k_pr, k_dc=args.prdc_k_dc)
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:

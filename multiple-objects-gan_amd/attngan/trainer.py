@@ -1811,6 +1811,60 @@ class condGANTrainer(object):
             return out, {"real": real_codes.cpu(), "fake": fake_codes.cpu()}
         return out
 
+    def prdc(self, split_dir, num_samples=30000, seed=100, k_pr=3, k_dc=5, codes=None, return_codes=False):
+        """Improved precision / recall (k_pr nearest neighbours) and density / coverage (k_dc) between real and generated images of
+        the checkpoint TRAIN.NET_G in the Inception pool codes of TRAIN.NET_E's image encoder (attngan/prdc.py
+        has the definitions): where the Frechet distance and KID give one number, these tell a generator whose images are sharp but
+        alike (precision high, recall low) from one whose images are varied but poor.  The codes are those of fid() -- ONE pass over
+        the data loader (pool_codes), or the `codes` a caller hands over from a pass of its own -- and stay on the device: two
+        calls of hip/ops.knn_sqdist give every code's radii inside its own set, three of hip/ops.ball_counts the memberships
+        between the sets, and the counts are read back once; the k's are lowered to n - 1 where there are fewer images.  All four
+        figures depend on n.  The real images always go through the trunk.  Writes <NET_G minus .pth>/<split>/prdc.json and
+        returns its content; with return_codes also a dict of the two code matrices on the host, "real" and "fake"."""
+        import json
+        from . import prdc as PRDC
+        if cfg.TRAIN.NET_G == '':
+            print('Error: the path for model NET_G is not found!')
+            return None
+        if codes is None:
+            codes = self.pool_codes(split_dir, num_samples, seed, True)
+        else:
+            self._check_handed_codes("prdc", codes, seed)
+        if codes["real"] is None:
+            raise ValueError("prdc: the codes handed over hold no real side")
+        save_dir = self._eval_save_dir(split_dir)
+        n, digest = codes["n"], codes["trunk_digest"]
+        if n < 2:
+            raise ValueError("prdc: the data loader gave %d images; a nearest neighbour needs two at least" % n)
+        real_codes, fake_codes = codes["real"][:n], codes["fake"][:n]
+        kp, kd = PRDC.neighbours(n, n, k_pr, k_dc)
+        real_r2 = ops.knn_sqdist(real_codes, max(kp, kd))                                  # every real code's radii, both k's
+        fake_r2 = ops.knn_sqdist(fake_codes, kp)
+        fake_in_real = ops.ball_counts(fake_codes, real_codes, real_r2[:, [kp - 1, kd - 1]].contiguous(), "support")
+        real_in_fake = ops.ball_counts(real_codes, fake_codes, fake_r2[:, kp - 1].contiguous(), "support")
+        real_own = ops.ball_counts(real_codes, fake_codes, real_r2[:, kd - 1].contiguous(), "query")
+        counts = torch.cat([fake_in_real, real_in_fake, real_own], dim=1).cpu().numpy()      # (n, 4): the one read-back
+        scores = PRDC.scores_from_counts(counts[:, 0:2], counts[:, 2], counts[:, 3], kd)
+        note = ("Improved precision / recall (k_pr nearest neighbours) and density / coverage (k_dc) of Inception "
+                "pool codes under the trunk of NET_E's image encoder: the published scores under torchvision's "
+                "Inception-v3 if that trunk holds ImageNet weights (published figures mostly use the TF-ported network), scores "
+                "in random convolutional features -- comparable between checkpoints under this trunk only -- if it is random-init."
+                " All four figures depend on the number of images and are comparable at equal n only.")
+        for name, asked, k in (("k_pr", k_pr, kp), ("k_dc", k_dc, kd)):
+            if k < int(asked):
+                note += (" %s lowered from %d to %d: there are only %d images per side." % (name, asked, k, n))
+                print("PRDC: %d images per side -- %s = %d instead of %d (the JSON records it)" % (n, name, k, asked))
+        out = dict(scores)
+        out.update({"k_pr": int(kp), "k_dc": int(kd), "n_real": int(n), "n_fake": int(n), "seed": int(seed), "NET_G": cfg.TRAIN.NET_G,
+                    "NET_E": cfg.TRAIN.NET_E, "trunk_digest": digest, "note": note})
+        with open('%s/prdc.json' % save_dir, 'w') as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+        print("PRDC (%d real, %d generated images; k = %d / %d): precision %.4f recall %.4f density %.4f coverage %.4f -> %s/prdc.json"
+              % (n, n, kp, kd, out["precision"], out["recall"], out["density"], out["coverage"], save_dir))
+        if return_codes:
+            return out, {"real": real_codes.cpu(), "fake": fake_codes.cpu()}
+        return out
+
     def sample(self, split_dir, num_samples=25, draw_bbox=False):
         """trainer.py:474-579 (what main.py:158 runs for B_VALIDATION): for the first `num_samples` batches of an
         eval-mode loader take the FIRST sample of the sorted batch, generate nine 256x256 images for its caption /

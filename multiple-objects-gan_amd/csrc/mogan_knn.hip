@@ -1,0 +1,421 @@
+// mogan_knn.hip -- what improved precision / recall and density / coverage of DESIGN.md section 9f are computed from: k-nearest-
+// neighbour radii inside a set of codes and ball membership between two sets, on squared Euclidean distances
+//
+//   d2(a, b) = max((|a|^2 + |b|^2) - 2 <a, b>, 0)
+//
+// of fp32 rows, widened exactly; everything after the load is fp64 and no distance matrix is ever written.  The reference
+// repository has no code for this.
+//
+// gram_tile: the main loop of poly3_mmd_kernel (csrc/mogan_mmd.hip), written once for the three kernels below: one 64 x 64 tile of
+// <a_i, b_j> per 4-wave block on v_mfma_f64_16x16x4_f64.  Per chunk of 32 features a thread loads 8 contiguous floats of one row of
+// each panel (two 16-byte loads where D and the base pointers allow, scalar loads otherwise), widens them and transposes them into
+// the [k][row] LDS image with row stride 80 doubles; lane l of a wave holds k = l >> 4, row l & 15 of both MFMA operands; a wave
+// owns a 32 x 32 quarter as 2 x 2 MFMA tiles; the next chunk's global loads are issued before the current chunk's MFMAs; the K
+// steps run along the feature axis in index order; rows past the set and features past D enter as zeros.
+//
+// The scores are decisions (<=), so two properties are part of the contract:
+//   * a distance's bits depend on the two rows only -- not on the tile, the wave, or which operand a row is.  The products of an
+//     MFMA commute and every accumulator sees the same K steps in the same order, so <a, b> has that property; the row norms are
+//     the DIAGONAL of the same tile loop run on a 64-row group against itself (row_norm_kernel, one launch per set into the
+//     workspace), never a scalar fma chain.  A bit copy of a row is then at (n + n) - 2 n = 0 exactly, d2(i, j) = d2(j, i) bitwise
+//     and a permutation of the rows permutes the results bitwise.
+//   * no atomics; the same inputs give the same bits on every call.
+//
+// knn_kernel: a block owns a 64-row stripe and walks the column tiles of its share (grid.y shares where the stripes alone would
+// not fill the device).  Per tile the distances go through LDS (the staging image, free after the loop) to one thread per row,
+// which keeps the 8 smallest in registers, sorted (compare against the 8th, insert); j = i by POSITION and columns past N are
+// left out.  The K smallest of a share go to the workspace and knn_merge_kernel merges the shares per row: the K smallest values
+// of a multiset do not depend on how it was partitioned.
+//
+// ball_kernel: a block owns a 64-query stripe and walks the support tiles of its share; a lane counts d2 <= r2 for its 8 rows x
+// R radii in registers over all its tiles, the 16 lanes of a row meet by a fixed butterfly, the two waves of a row in LDS, the
+// shares in ball_finish_kernel in share order (integers: any fixed order gives the same result).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <cmath>
+#include "../../include/mogan_hip.h"
+
+namespace {
+
+constexpr int NT = 256;        // 4 wave64
+constexpr int CT = 64;         // tile edge
+constexpr int KC = 32;         // features per staged chunk (8 MFMA k-steps of 4)
+constexpr int LDW = 80;        // LDS row stride in doubles, as in mogan_mmd.hip / mogan_stats.hip
+constexpr int KPT = KC * CT / NT;   // staged features per thread and panel: 8 contiguous floats of one row
+constexpr int LDD = CT + 1;    // row stride of the distance tile in LDS
+constexpr long long N_MAX = 2147483647LL;
+constexpr int D_MAX = 65536;
+constexpr int K_MAX = 8;
+constexpr int R_MAX = 4;
+constexpr int SPLIT_BLOCKS = 512;   // shares are added until the grid has this many blocks
+constexpr int SPLIT_MAX = 64;
+
+static_assert(CT * LDD <= 2 * KC * LDW, "the distance tile lives in the staging image");
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+static inline int ok_launch() { return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH; }
+
+__host__ __device__ static inline long long tiles_of(long long n) { return (n + CT - 1) / CT; }
+
+// the number of shares the column tiles are split into: a function of the two tile counts only
+static inline int shares_of(long long rows, long long cols) {
+    const long long tr = tiles_of(rows), tc = tiles_of(cols);
+    long long s = (SPLIT_BLOCKS + tr - 1) / tr;
+    if (s > tc) s = tc;
+    if (s > SPLIT_MAX) s = SPLIT_MAX;
+    return s < 1 ? 1 : (int)s;
+}
+
+// acc = <a_i, b_j> for rows a0 .. a0 + 63 of A against rows b0 .. b0 + 63 of B; wave -> quarter (wave >> 1, wave & 1), the f64 C/D
+// map inside a 16 x 16 tile: column = lane & 15, row = (lane >> 4) + 4 * reg.  `same`: B's panel is A's (one panel staged).
+// Ends behind a barrier: sm is free on return.
+template <bool VEC>
+__device__ __forceinline__ void gram_tile(const float* __restrict__ A, long long NA, long long a0, const float* __restrict__ B,
+                                          long long NB, long long b0, int D, bool same, double (&sm)[2][KC][LDW],
+                                          f64x4 (&acc)[2][2]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // staging: thread -> row tid >> 2 of both panels, features (tid & 3) * 8 .. + 7 of the chunk
+    const int srow = tid >> 2, sk = (tid & 3) * KPT;
+    const long long pa = a0 + srow, pb = b0 + srow;
+    const bool va = pa < NA, vb = !same && pb < NB;
+    const float* xa = A + (size_t)(va ? pa : 0) * D;
+    const float* xb = B + (size_t)(vb ? pb : 0) * D;
+    float ra[KPT], rb[KPT];
+    auto fetch = [&](int k0) {
+        if (VEC) {                                            // D % 4 == 0: a group of 4 features is inside D or past it
+#pragma unroll
+            for (int h = 0; h < KPT / 4; ++h) {
+                const int k = k0 + sk + 4 * h;
+                const bool in = k < D;
+                const float4 a = (va && in) ? *reinterpret_cast<const float4*>(xa + k) : float4{0.f, 0.f, 0.f, 0.f};
+                const float4 b = (vb && in) ? *reinterpret_cast<const float4*>(xb + k) : float4{0.f, 0.f, 0.f, 0.f};
+                ra[4 * h] = a.x; ra[4 * h + 1] = a.y; ra[4 * h + 2] = a.z; ra[4 * h + 3] = a.w;
+                rb[4 * h] = b.x; rb[4 * h + 1] = b.y; rb[4 * h + 2] = b.z; rb[4 * h + 3] = b.w;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                const int k = k0 + sk + j;
+                const bool in = k < D;
+                ra[j] = (va && in) ? xa[k] : 0.f;
+                rb[j] = (vb && in) ? xb[k] : 0.f;
+            }
+        }
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            sm[0][sk + j][srow] = (double)ra[j];
+            if (!same) sm[1][sk + j][srow] = (double)rb[j];
+        }
+    };
+    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
+    const double* qa = &sm[0][lk][wr * 32 + lc];
+    const double* qb = &sm[same ? 0 : 1][lk][wc * 32 + lc];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+    fetch(0);
+    for (int k0 = 0; k0 < D; k0 += KC) {
+        stash();
+        __syncthreads();
+        if (k0 + KC < D) fetch(k0 + KC);
+#pragma unroll
+        for (int kk = 0; kk < KC / 4; ++kk) {
+            const double a0v = qa[kk * 4 * LDW], a1v = qa[kk * 4 * LDW + 16];
+            const double b0v = qb[kk * 4 * LDW], b1v = qb[kk * 4 * LDW + 16];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0v, b0v, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0v, b1v, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1v, b0v, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1v, b1v, acc[1][1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+}
+
+// the one expression of a distance: symmetric in (na, nb), exactly 0 where na == nb == g
+__device__ __forceinline__ double sqdist(double na, double nb, double g) {
+#pragma clang fp contract(off)
+    const double s = na + nb;
+    const double t = 2.0 * g;
+    return fmax(s - t, 0.0);
+}
+
+// norms[i] = <x_i, x_i> as the diagonal of gram_tile on rows 64 b .. 64 b + 63 against themselves
+template <bool VEC>
+__global__ __launch_bounds__(NT) void row_norm_kernel(const float* __restrict__ x, long long N, int D,
+                                                      double* __restrict__ norms) {
+    __shared__ double sm[2][KC][LDW];
+    const long long r0 = (long long)blockIdx.x * CT;
+    f64x4 acc[2][2];
+    gram_tile<VEC>(x, N, r0, x, N, r0, D, true, sm, acc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
+    if (wr != wc) return;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (lk + 4 * j == lc) {                                    // row == column inside the 16 x 16 tile (m, m)
+                const long long row = r0 + wr * 32 + m * 16 + lc;
+                if (row < N) norms[row] = acc[m][m][j];
+            }
+}
+
+// v into the sorted list of the 8 smallest (the caller has seen v < best[7])
+__device__ __forceinline__ void insert8(double (&best)[K_MAX], double v) {
+    best[K_MAX - 1] = v;
+#pragma unroll
+    for (int t = K_MAX - 1; t > 0; --t) {
+        const double lo = fmin(best[t - 1], best[t]), hi = fmax(best[t - 1], best[t]);
+        best[t - 1] = lo;
+        best[t] = hi;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(NT) void knn_kernel(const float* __restrict__ x, long long N, int D, int K,
+                                                 const double* __restrict__ norms, double* __restrict__ part) {
+    __shared__ double sm[2][KC][LDW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
+    const long long r0 = (long long)blockIdx.x * CT;
+    const long long T = tiles_of(N);
+    const long long t_lo = T * blockIdx.y / gridDim.y, t_hi = T * (blockIdx.y + 1) / gridDim.y;
+    double na[8];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long row = r0 + wr * 32 + m * 16 + lk + 4 * j;
+            na[m * 4 + j] = row < N ? norms[row] : 0.0;
+        }
+    double best[K_MAX];
+#pragma unroll
+    for (int t = 0; t < K_MAX; ++t) best[t] = INFINITY;
+    double* dist = &sm[0][0][0];
+    const long long own = r0 + tid;                                    // the row of the selecting thread (tid < 64)
+    f64x4 acc[2][2];
+    for (long long bt = t_lo; bt < t_hi; ++bt) {
+        const long long c0 = bt * CT;
+        gram_tile<VEC>(x, N, r0, x, N, c0, D, false, sm, acc);
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const int cl = wc * 32 + n * 16 + lc;
+            const double nb = c0 + cl < N ? norms[c0 + cl] : 0.0;
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int rl = wr * 32 + m * 16 + lk + 4 * j;
+                    dist[rl * LDD + cl] = sqdist(na[m * 4 + j], nb, acc[m][n][j]);
+                }
+        }
+        __syncthreads();
+        if (tid < CT) {
+            const long long lim = N - c0 < CT ? N - c0 : CT;
+            for (int c = 0; c < (int)lim; ++c) {
+                const double v = dist[tid * LDD + c];
+                if (c0 + c != own && v < best[K_MAX - 1]) insert8(best, v);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < CT && own < N) {
+        double* o = part + ((size_t)blockIdx.y * (size_t)N + (size_t)own) * K;
+#pragma unroll
+        for (int t = 0; t < K_MAX; ++t)
+            if (t < K) o[t] = best[t];
+    }
+}
+
+__global__ __launch_bounds__(NT) void knn_merge_kernel(const double* __restrict__ part, long long N, int K, int shares,
+                                                       double* __restrict__ out) {
+    const long long row = (long long)blockIdx.x * NT + threadIdx.x;
+    if (row >= N) return;
+    double best[K_MAX];
+#pragma unroll
+    for (int t = 0; t < K_MAX; ++t) best[t] = INFINITY;
+    for (int s = 0; s < shares; ++s) {
+        const double* p = part + ((size_t)s * (size_t)N + (size_t)row) * K;
+        for (int t = 0; t < K; ++t) {
+            const double v = p[t];
+            if (v < best[K_MAX - 1]) insert8(best, v);
+        }
+    }
+    double* o = out + (size_t)row * K;
+#pragma unroll
+    for (int t = 0; t < K_MAX; ++t)
+        if (t < K) o[t] = best[t];
+}
+
+// SIDE 0: the radius belongs to the support point (r2 (N, R), by column); SIDE 1: to the query (r2 (M, R), by row)
+template <bool VEC, int SIDE>
+__global__ __launch_bounds__(NT) void ball_kernel(const float* __restrict__ q, long long M, const float* __restrict__ p, long long N,
+                                                  int D, const double* __restrict__ r2, int R, const double* __restrict__ nq,
+                                                  const double* __restrict__ np, int32_t* __restrict__ part) {
+    __shared__ double sm[2][KC][LDW];
+    __shared__ double rq[CT][R_MAX];
+    __shared__ int32_t red[2][CT][R_MAX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
+    const long long r0 = (long long)blockIdx.x * CT;
+    const long long T = tiles_of(N);
+    const long long t_lo = T * blockIdx.y / gridDim.y, t_hi = T * (blockIdx.y + 1) / gridDim.y;
+    // a radius of -1 counts nothing (d2 >= 0): radii past R, past M, past N
+    if (SIDE == 1) {
+        const int rl = tid >> 2, c = tid & 3;
+        rq[rl][c] = (c < R && r0 + rl < M) ? r2[(size_t)(r0 + rl) * R + c] : -1.0;
+    }
+    double na[8];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long row = r0 + wr * 32 + m * 16 + lk + 4 * j;
+            na[m * 4 + j] = row < M ? nq[row] : 0.0;
+        }
+    int32_t cnt[8][R_MAX];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int c = 0; c < R_MAX; ++c) cnt[i][c] = 0;
+    f64x4 acc[2][2];
+    for (long long bt = t_lo; bt < t_hi; ++bt) {
+        const long long c0 = bt * CT;
+        gram_tile<VEC>(q, M, r0, p, N, c0, D, false, sm, acc);         // its barriers also order rq's fill before its use
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const long long col = c0 + wc * 32 + n * 16 + lc;
+            const bool vc = col < N;
+            const double nb = vc ? np[col] : 0.0;
+            double rr[R_MAX];
+#pragma unroll
+            for (int c = 0; c < R_MAX; ++c) rr[c] = (SIDE == 0 && vc && c < R) ? r2[(size_t)col * R + c] : -1.0;
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int rl = wr * 32 + m * 16 + lk + 4 * j;
+                    const double d = sqdist(na[m * 4 + j], nb, acc[m][n][j]);
+#pragma unroll
+                    for (int c = 0; c < R_MAX; ++c) {
+                        const double r = SIDE == 1 ? rq[rl][c] : rr[c];
+                        cnt[m * 4 + j][c] += (vc && d <= r) ? 1 : 0;
+                    }
+                }
+        }
+    }
+    // the 16 lanes of a row (same lane >> 4), then the two waves of a row
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int c = 0; c < R_MAX; ++c) {
+            int32_t v = cnt[i][c];
+#pragma unroll
+            for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+            cnt[i][c] = v;
+        }
+    if (lc == 0) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int c = 0; c < R_MAX; ++c) red[wc][wr * 32 + m * 16 + lk + 4 * j][c] = cnt[m * 4 + j][c];
+    }
+    __syncthreads();
+    {
+        const int rl = tid >> 2, c = tid & 3;
+        if (c < R && r0 + rl < M)
+            part[((size_t)blockIdx.y * (size_t)M + (size_t)(r0 + rl)) * R + c] = red[0][rl][c] + red[1][rl][c];
+    }
+}
+
+__global__ __launch_bounds__(NT) void ball_finish_kernel(const int32_t* __restrict__ part, long long MR, int shares,
+                                                         int32_t* __restrict__ count) {
+    const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+    if (i >= MR) return;
+    int32_t t = 0;
+    for (int s = 0; s < shares; ++s) t += part[(size_t)s * (size_t)MR + (size_t)i];
+    count[i] = t;
+}
+
+static int launch_norms(const float* x, long long N, int D, double* norms, bool vec, hipStream_t stream) {
+    const dim3 grid((unsigned)tiles_of(N));
+    if (vec)
+        hipLaunchKernelGGL(row_norm_kernel<true>, grid, dim3(NT), 0, stream, x, N, D, norms);
+    else
+        hipLaunchKernelGGL(row_norm_kernel<false>, grid, dim3(NT), 0, stream, x, N, D, norms);
+    return ok_launch();
+}
+
+static inline size_t up8(size_t b) { return (b + 7) & ~(size_t)7; }
+
+}  // namespace
+
+extern "C" {
+
+size_t mogan_knn_sqdist_ws_bytes(long long N, int K) {
+    if (K < 1 || K > K_MAX || N < (long long)K + 1 || N > N_MAX) return 0;
+    return ((size_t)N + (size_t)shares_of(N, N) * (size_t)N * (size_t)K) * sizeof(double);
+}
+
+int mogan_knn_sqdist_f64(const float* x, long long N, int D, int K, double* out, void* ws, size_t ws_bytes, hipStream_t stream) {
+    if (!x || !out || K < 1 || K > K_MAX || N < (long long)K + 1 || N > N_MAX || D < 1 || D > D_MAX) return MOGAN_ERR_SHAPE;
+    if (!ws || ((uintptr_t)ws & 7) != 0 || ws_bytes < mogan_knn_sqdist_ws_bytes(N, K)) return MOGAN_ERR_WS;
+    const bool vec = D % 4 == 0 && ((uintptr_t)x & 15) == 0;
+    double* norms = (double*)ws;
+    double* part = norms + N;
+    const int shares = shares_of(N, N);
+    if (launch_norms(x, N, D, norms, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
+    const dim3 grid((unsigned)tiles_of(N), shares);
+    if (vec)
+        hipLaunchKernelGGL(knn_kernel<true>, grid, dim3(NT), 0, stream, x, N, D, K, (const double*)norms, part);
+    else
+        hipLaunchKernelGGL(knn_kernel<false>, grid, dim3(NT), 0, stream, x, N, D, K, (const double*)norms, part);
+    if (ok_launch() != 0) return MOGAN_ERR_LAUNCH;
+    hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((N + NT - 1) / NT)), dim3(NT), 0, stream, (const double*)part, N, K,
+                       shares, out);
+    return ok_launch();
+}
+
+size_t mogan_ball_count_ws_bytes(long long M, long long N, int R) {
+    if (R < 1 || R > R_MAX || M < 1 || N < 1 || M > N_MAX || N > N_MAX) return 0;
+    return ((size_t)M + (size_t)N) * sizeof(double) + up8((size_t)shares_of(M, N) * (size_t)M * (size_t)R * sizeof(int32_t));
+}
+
+int mogan_ball_count_f64(const float* q, long long M, const float* p, long long N, int D, const double* r2, int R, int side,
+                         int32_t* count, void* ws, size_t ws_bytes, hipStream_t stream) {
+    if (!q || !p || !r2 || !count || M < 1 || N < 1 || M > N_MAX || N > N_MAX || D < 1 || D > D_MAX || R < 1 || R > R_MAX ||
+        (side != 0 && side != 1))
+        return MOGAN_ERR_SHAPE;
+    if (!ws || ((uintptr_t)ws & 7) != 0 || ws_bytes < mogan_ball_count_ws_bytes(M, N, R)) return MOGAN_ERR_WS;
+    const bool vec = D % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)p & 15) == 0;
+    double* nq = (double*)ws;
+    double* np = nq + M;
+    int32_t* part = (int32_t*)(np + N);
+    const int shares = shares_of(M, N);
+    if (launch_norms(q, M, D, nq, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
+    if (launch_norms(p, N, D, np, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
+    const dim3 grid((unsigned)tiles_of(M), shares);
+#define MOGAN_BALL(V, S)                                                                                                  \
+    hipLaunchKernelGGL((ball_kernel<V, S>), grid, dim3(NT), 0, stream, q, M, p, N, D, r2, R, (const double*)nq, (const double*)np, \
+                       part)
+    if (vec) {
+        if (side == 0) MOGAN_BALL(true, 0); else MOGAN_BALL(true, 1);
+    } else {
+        if (side == 0) MOGAN_BALL(false, 0); else MOGAN_BALL(false, 1);
+    }
+#undef MOGAN_BALL
+    if (ok_launch() != 0) return MOGAN_ERR_LAUNCH;
+    const long long MR = M * R;
+    hipLaunchKernelGGL(ball_finish_kernel, dim3((unsigned)((MR + NT - 1) / NT)), dim3(NT), 0, stream, (const int32_t*)part, MR,
+                       shares, count);
+    return ok_launch();
+}
+
+}  // extern "C"

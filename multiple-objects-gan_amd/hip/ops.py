@@ -1823,6 +1823,82 @@ def poly_mmd_sums(x, y, ix, iy, gamma=None, coef0=1.0):
     return sums
 
 
+def _codes(who, pairs):
+    """the contract of the fp64 score ops for their fp32 code matrices: dtype, rank, contiguity, one device, one width"""
+    for name, t in pairs:
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError("%s: fp32 codes expected, %s is %s" % (who, name, getattr(t, "dtype", type(t))))
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("%s: codes (N, D) expected, %s is %s" % (who, name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: contiguous codes expected (%s has strides %s)" % (who, name, tuple(t.stride())))
+        if t.shape[1] != pairs[0][1].shape[1]:
+            raise ValueError("%s: the codes differ in width: %s, %s" % (who, tuple(pairs[0][1].shape), tuple(t.shape)))
+        if t.device != pairs[0][1].device:
+            raise ValueError("%s: the codes must be on one device (%s, %s)" % (who, pairs[0][1].device, t.device))
+
+
+def _scratch(device, need):
+    """(pointer, bytes, owner): the shared workspace where it is large enough, else a tensor of its own (to be record_stream'ed)"""
+    ws, ws_bytes = workspace(device)
+    if ws_bytes >= need:
+        return ws, ws_bytes, None
+    own = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    return own.data_ptr(), own.numel(), own
+
+
+def knn_sqdist(x, K):
+    """The K smallest squared Euclidean distances from every row of fp32 codes x (N, D) to the OTHER rows (by position: a duplicate
+    elsewhere is a neighbour at distance 0), ascending: (N, K) fp64 on the device (mogan_knn_sqdist_f64: fp64 MFMA, no distance
+    matrix written, a distance's bits depend on the two rows only, same bits on every call).  1 <= K <= min(8, N - 1).  No gradient.
+    Nothing is converted or copied for the caller: a wrong dtype or rank, a non-contiguous input, a K out of range are a ValueError."""
+    _codes("knn_sqdist", (("x", x),))
+    K = int(K)
+    N, D = x.shape
+    if K < 1 or K > 8 or K > N - 1:
+        raise ValueError("knn_sqdist: 1 <= K <= min(8, N - 1) expected, got K = %d for %d rows" % (K, N))
+    x = x.detach()
+    px = ptr(x)
+    ws, ws_bytes, own = _scratch(x.device, int(lib.load().mogan_knn_sqdist_ws_bytes(N, K)))
+    out = torch.empty((N, K), dtype=torch.float64, device=x.device)
+    call("mogan_knn_sqdist_f64", px, N, D, K, ptr(out), ws, ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(x.device))
+    return out
+
+
+def ball_counts(q, p, r2, side="support"):
+    """count (M, R) int32 on the device, count[j, c] = #{ i : d2(q_j, p_i) <= r2[., c] } for fp32 queries q (M, D), fp32 support
+    points p (N, D) and fp64 squared radii r2 (mogan_ball_count_f64; the distances are knn_sqdist's, bit for bit).  side
+    "support": the radius is the support point's, r2 (N, R) or (N,); side "query": the query's, r2 (M, R) or (M,).  1 <= R <= 4.
+    No gradient.  Nothing is converted or copied for the caller: a wrong dtype or rank, a width or length mismatch, a
+    non-contiguous input, another device, R > 4, another `side` are a ValueError."""
+    _codes("ball_counts", (("q", q), ("p", p)))
+    if side not in ("support", "query"):
+        raise ValueError("ball_counts: side must be 'support' or 'query', got %r" % (side,))
+    if not torch.is_tensor(r2) or r2.dtype != torch.float64:
+        raise ValueError("ball_counts: fp64 radii expected, r2 is %s" % (getattr(r2, "dtype", type(r2)),))
+    if r2.dim() not in (1, 2):
+        raise ValueError("ball_counts: radii (rows, R) or (rows,) expected, r2 is %s" % (tuple(r2.shape),))
+    M, N, D = q.shape[0], p.shape[0], q.shape[1]
+    rows = N if side == "support" else M
+    R = 1 if r2.dim() == 1 else int(r2.shape[1])
+    if r2.shape[0] != rows or R < 1 or R > 4:
+        raise ValueError("ball_counts: side %r needs radii (%d, 1..4), r2 is %s" % (side, rows, tuple(r2.shape)))
+    if not r2.is_contiguous():
+        raise ValueError("ball_counts: contiguous radii expected (r2 has strides %s)" % (tuple(r2.stride()),))
+    if r2.device != q.device:
+        raise ValueError("ball_counts: r2 must be on the codes' device (%s, %s)" % (r2.device, q.device))
+    q, p, r2 = q.detach(), p.detach(), r2.detach()
+    pq, pp, pr = ptr(q), ptr(p), ptr(r2)
+    ws, ws_bytes, own = _scratch(q.device, int(lib.load().mogan_ball_count_ws_bytes(M, N, R)))
+    count = torch.empty((M, R), dtype=torch.int32, device=q.device)
+    call("mogan_ball_count_f64", pq, M, pp, N, D, pr, R, 0 if side == "support" else 1, ptr(count), ws, ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(q.device))
+    return count
+
+
 class ScalarSumFn(torch.autograd.Function):
     """sum_k w_k * x_k over up to 8 zero-dim device scalars in ONE launch (forward) / one launch (backward): the loss sums
     of miscc/losses.py:169-174,203,221 and trainer.py:330 otherwise cost a chain of 0-dim aten kernels each way."""
