@@ -6,12 +6,8 @@
 // of fp32 rows, widened exactly; everything after the load is fp64 and no distance matrix is ever written.  The reference
 // repository has no code for this.
 //
-// gram_tile: the main loop of poly3_mmd_kernel (csrc/mogan_mmd.hip), written once for the three kernels below: one 64 x 64 tile of
-// <a_i, b_j> per 4-wave block on v_mfma_f64_16x16x4_f64.  Per chunk of 32 features a thread loads 8 contiguous floats of one row of
-// each panel (two 16-byte loads where D and the base pointers allow, scalar loads otherwise), widens them and transposes them into
-// the [k][row] LDS image with row stride 80 doubles; lane l of a wave holds k = l >> 4, row l & 15 of both MFMA operands; a wave
-// owns a 32 x 32 quarter as 2 x 2 MFMA tiles; the next chunk's global loads are issued before the current chunk's MFMAs; the K
-// steps run along the feature axis in index order; rows past the set and features past D enter as zeros.
+// gram_tile: one 64 x 64 tile of <a_i, b_j> per 4-wave block, gram64_tile of csrc/mogan_gram64.h on two row panels, for the three
+// kernels below; the K steps run along the feature axis in index order; rows past the set and features past D enter as zeros.
 //
 // The scores are decisions (<=), so two properties are part of the contract:
 //   * a distance's bits depend on the two rows only -- not on the tile, the wave, or which operand a row is.  The products of an
@@ -31,30 +27,18 @@
 // R radii in registers over all its tiles, the 16 lanes of a row meet by a fixed butterfly, the two waves of a row in LDS, the
 // shares in ball_finish_kernel in share order (integers: any fixed order gives the same result).
 #include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <cmath>
-#include "../../include/mogan_hip.h"
+#include "mogan_gram64.h"
 
 namespace {
 
-constexpr int NT = 256;        // 4 wave64
-constexpr int CT = 64;         // tile edge
-constexpr int KC = 32;         // features per staged chunk (8 MFMA k-steps of 4)
-constexpr int LDW = 80;        // LDS row stride in doubles, as in mogan_mmd.hip / mogan_stats.hip
-constexpr int KPT = KC * CT / NT;   // staged features per thread and panel: 8 contiguous floats of one row
 constexpr int LDD = CT + 1;    // row stride of the distance tile in LDS
-constexpr long long N_MAX = 2147483647LL;
-constexpr int D_MAX = 65536;
 constexpr int K_MAX = 8;
 constexpr int R_MAX = 4;
 constexpr int SPLIT_BLOCKS = 512;   // shares are added until the grid has this many blocks
 constexpr int SPLIT_MAX = 64;
 
 static_assert(CT * LDD <= 2 * KC * LDW, "the distance tile lives in the staging image");
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-static inline int ok_launch() { return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH; }
 
 __host__ __device__ static inline long long tiles_of(long long n) { return (n + CT - 1) / CT; }
 
@@ -67,73 +51,15 @@ static inline int shares_of(long long rows, long long cols) {
     return s < 1 ? 1 : (int)s;
 }
 
-// acc = <a_i, b_j> for rows a0 .. a0 + 63 of A against rows b0 .. b0 + 63 of B; wave -> quarter (wave >> 1, wave & 1), the f64 C/D
-// map inside a 16 x 16 tile: column = lane & 15, row = (lane >> 4) + 4 * reg.  `same`: B's panel is A's (one panel staged).
+// acc = <a_i, b_j> for rows a0 .. a0 + 63 of A against rows b0 .. b0 + 63 of B.  `same`: B's panel is A's (one panel staged).
 // Ends behind a barrier: sm is free on return.
 template <bool VEC>
 __device__ __forceinline__ void gram_tile(const float* __restrict__ A, long long NA, long long a0, const float* __restrict__ B,
-                                          long long NB, long long b0, int D, bool same, double (&sm)[2][KC][LDW],
-                                          f64x4 (&acc)[2][2]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // staging: thread -> row tid >> 2 of both panels, features (tid & 3) * 8 .. + 7 of the chunk
-    const int srow = tid >> 2, sk = (tid & 3) * KPT;
-    const long long pa = a0 + srow, pb = b0 + srow;
+                                          long long NB, long long b0, int D, bool same, GramLds& sm, f64x4 (&acc)[2][2]) {
+    const long long pa = a0 + RowPanels<VEC>::stage_row(), pb = b0 + RowPanels<VEC>::stage_row();
     const bool va = pa < NA, vb = !same && pb < NB;
-    const float* xa = A + (size_t)(va ? pa : 0) * D;
-    const float* xb = B + (size_t)(vb ? pb : 0) * D;
-    float ra[KPT], rb[KPT];
-    auto fetch = [&](int k0) {
-        if (VEC) {                                            // D % 4 == 0: a group of 4 features is inside D or past it
-#pragma unroll
-            for (int h = 0; h < KPT / 4; ++h) {
-                const int k = k0 + sk + 4 * h;
-                const bool in = k < D;
-                const float4 a = (va && in) ? *reinterpret_cast<const float4*>(xa + k) : float4{0.f, 0.f, 0.f, 0.f};
-                const float4 b = (vb && in) ? *reinterpret_cast<const float4*>(xb + k) : float4{0.f, 0.f, 0.f, 0.f};
-                ra[4 * h] = a.x; ra[4 * h + 1] = a.y; ra[4 * h + 2] = a.z; ra[4 * h + 3] = a.w;
-                rb[4 * h] = b.x; rb[4 * h + 1] = b.y; rb[4 * h + 2] = b.z; rb[4 * h + 3] = b.w;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                const int k = k0 + sk + j;
-                const bool in = k < D;
-                ra[j] = (va && in) ? xa[k] : 0.f;
-                rb[j] = (vb && in) ? xb[k] : 0.f;
-            }
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            sm[0][sk + j][srow] = (double)ra[j];
-            if (!same) sm[1][sk + j][srow] = (double)rb[j];
-        }
-    };
-    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
-    const double* qa = &sm[0][lk][wr * 32 + lc];
-    const double* qb = &sm[same ? 0 : 1][lk][wc * 32 + lc];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
-
-    fetch(0);
-    for (int k0 = 0; k0 < D; k0 += KC) {
-        stash();
-        __syncthreads();
-        if (k0 + KC < D) fetch(k0 + KC);
-#pragma unroll
-        for (int kk = 0; kk < KC / 4; ++kk) {
-            const double a0v = qa[kk * 4 * LDW], a1v = qa[kk * 4 * LDW + 16];
-            const double b0v = qb[kk * 4 * LDW], b1v = qb[kk * 4 * LDW + 16];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0v, b0v, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0v, b1v, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1v, b0v, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1v, b1v, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
+    RowPanels<VEC> src(A + (size_t)(va ? pa : 0) * D, va, B + (size_t)(vb ? pb : 0) * D, vb, D, same);
+    gram64_tile(src, sm, acc);
 }
 
 // the one expression of a distance: symmetric in (na, nb), exactly 0 where na == nb == g
@@ -148,19 +74,18 @@ __device__ __forceinline__ double sqdist(double na, double nb, double g) {
 template <bool VEC>
 __global__ __launch_bounds__(NT) void row_norm_kernel(const float* __restrict__ x, long long N, int D,
                                                       double* __restrict__ norms) {
-    __shared__ double sm[2][KC][LDW];
+    __shared__ GramLds sm;
     const long long r0 = (long long)blockIdx.x * CT;
     f64x4 acc[2][2];
     gram_tile<VEC>(x, N, r0, x, N, r0, D, true, sm, acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
-    if (wr != wc) return;
+    const GramLane ln;
+    if (ln.wr != ln.wc) return;
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (lk + 4 * j == lc) {                                    // row == column inside the 16 x 16 tile (m, m)
-                const long long row = r0 + wr * 32 + m * 16 + lc;
+            if (ln.lk + 4 * j == ln.lc) {                              // row == column inside the 16 x 16 tile (m, m)
+                const long long row = ln.col(r0, m);                   // of a diagonal quarter: its row as well
                 if (row < N) norms[row] = acc[m][m][j];
             }
 }
@@ -179,9 +104,9 @@ __device__ __forceinline__ void insert8(double (&best)[K_MAX], double v) {
 template <bool VEC>
 __global__ __launch_bounds__(NT) void knn_kernel(const float* __restrict__ x, long long N, int D, int K,
                                                  const double* __restrict__ norms, double* __restrict__ part) {
-    __shared__ double sm[2][KC][LDW];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
+    __shared__ GramLds sm;
+    const int tid = threadIdx.x;
+    const GramLane ln;
     const long long r0 = (long long)blockIdx.x * CT;
     const long long T = tiles_of(N);
     const long long t_lo = T * blockIdx.y / gridDim.y, t_hi = T * (blockIdx.y + 1) / gridDim.y;
@@ -190,7 +115,7 @@ __global__ __launch_bounds__(NT) void knn_kernel(const float* __restrict__ x, lo
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const long long row = r0 + wr * 32 + m * 16 + lk + 4 * j;
+            const long long row = ln.row(r0, m, j);
             na[m * 4 + j] = row < N ? norms[row] : 0.0;
         }
     double best[K_MAX];
@@ -204,15 +129,12 @@ __global__ __launch_bounds__(NT) void knn_kernel(const float* __restrict__ x, lo
         gram_tile<VEC>(x, N, r0, x, N, c0, D, false, sm, acc);
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-            const int cl = wc * 32 + n * 16 + lc;
+            const int cl = ln.col(0, n);
             const double nb = c0 + cl < N ? norms[c0 + cl] : 0.0;
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int rl = wr * 32 + m * 16 + lk + 4 * j;
-                    dist[rl * LDD + cl] = sqdist(na[m * 4 + j], nb, acc[m][n][j]);
-                }
+                for (int j = 0; j < 4; ++j) dist[ln.row(0, m, j) * LDD + cl] = sqdist(na[m * 4 + j], nb, acc[m][n][j]);
         }
         __syncthreads();
         if (tid < CT) {
@@ -257,11 +179,11 @@ template <bool VEC, int SIDE>
 __global__ __launch_bounds__(NT) void ball_kernel(const float* __restrict__ q, long long M, const float* __restrict__ p, long long N,
                                                   int D, const double* __restrict__ r2, int R, const double* __restrict__ nq,
                                                   const double* __restrict__ np, int32_t* __restrict__ part) {
-    __shared__ double sm[2][KC][LDW];
+    __shared__ GramLds sm;
     __shared__ double rq[CT][R_MAX];
     __shared__ int32_t red[2][CT][R_MAX];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
+    const int tid = threadIdx.x;
+    const GramLane ln;
     const long long r0 = (long long)blockIdx.x * CT;
     const long long T = tiles_of(N);
     const long long t_lo = T * blockIdx.y / gridDim.y, t_hi = T * (blockIdx.y + 1) / gridDim.y;
@@ -275,7 +197,7 @@ __global__ __launch_bounds__(NT) void ball_kernel(const float* __restrict__ q, l
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const long long row = r0 + wr * 32 + m * 16 + lk + 4 * j;
+            const long long row = ln.row(r0, m, j);
             na[m * 4 + j] = row < M ? nq[row] : 0.0;
         }
     int32_t cnt[8][R_MAX];
@@ -289,7 +211,7 @@ __global__ __launch_bounds__(NT) void ball_kernel(const float* __restrict__ q, l
         gram_tile<VEC>(q, M, r0, p, N, c0, D, false, sm, acc);         // its barriers also order rq's fill before its use
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-            const long long col = c0 + wc * 32 + n * 16 + lc;
+            const long long col = ln.col(c0, n);
             const bool vc = col < N;
             const double nb = vc ? np[col] : 0.0;
             double rr[R_MAX];
@@ -299,7 +221,7 @@ __global__ __launch_bounds__(NT) void ball_kernel(const float* __restrict__ q, l
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int rl = wr * 32 + m * 16 + lk + 4 * j;
+                    const int rl = ln.row(0, m, j);
                     const double d = sqdist(na[m * 4 + j], nb, acc[m][n][j]);
 #pragma unroll
                     for (int c = 0; c < R_MAX; ++c) {
@@ -319,13 +241,13 @@ __global__ __launch_bounds__(NT) void ball_kernel(const float* __restrict__ q, l
             for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
             cnt[i][c] = v;
         }
-    if (lc == 0) {
+    if (ln.lc == 0) {
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int c = 0; c < R_MAX; ++c) red[wc][wr * 32 + m * 16 + lk + 4 * j][c] = cnt[m * 4 + j][c];
+                for (int c = 0; c < R_MAX; ++c) red[ln.wc][ln.row(0, m, j)][c] = cnt[m * 4 + j][c];
     }
     __syncthreads();
     {

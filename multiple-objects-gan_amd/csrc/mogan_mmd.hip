@@ -11,43 +11,25 @@
 // poly3_mmd_kernel: one 64 x 64 tile of one subset's kernel matrix per 4-wave block and none of the matrix ever written.  Grid
 // (tile, subset), the tile index fastest -- one subset's rows are in flight together.  Per subset the tiles are counted as: the
 // P = T (T + 1) / 2 tiles on and above the diagonal of xx row by row, the same P of yy, then all T^2 of xy row by row
-// (T = ceil(s / 64): 528 tiles at s = 1000).  The reduction runs along the FEATURE axis: per chunk of 32 features a thread loads 8
-// contiguous floats of one gathered row of each panel (two 16-byte loads where D and the base pointers allow, scalar loads
-// otherwise), widens them and transposes them into the [k][row] LDS image of cov_f64_kernel (csrc/mogan_stats.hip: row stride 80
-// doubles, so the 16 lanes of k and of k + 1 fall on opposite halves of the 64 banks); both operands of v_mfma_f64_16x16x4_f64 are
-// read from that image exactly as there -- lane l holds k = l >> 4, row l & 15 -- and a diagonal tile stages one panel only.  A wave
-// owns a 32 x 32 quarter as 2 x 2 MFMA tiles; the next chunk's global loads are issued before the current chunk's MFMAs.  The sum
-// over the features runs in index order in every accumulator; rows past s and features past D enter as zeros.  An index outside
-// [0, N) is clamped, so a bad device index cannot read outside x or y.
+// (T = ceil(s / 64): 528 tiles at s = 1000).  The tile of <a_i, b_j> is gram64_tile of csrc/mogan_gram64.h on two row panels of
+// GATHERED rows: the reduction runs along the feature axis in index order in every accumulator; rows past s and features past D
+// enter as zeros.  An index outside [0, N) is clamped, so a bad device index cannot read outside x or y.
 //
-// Epilogue.  C/D of the f64 MFMA: column = lane & 15, row = (lane >> 4) + 4 * reg -- NOT the f32 map.  t = acc * gamma + coef0,
-// value (t * t) * t, no contraction.  A zero row is not a zero kernel value (k = coef0^3), so rows and columns past s are masked
-// out of the sum again; a diagonal tile of xx / yy keeps i < j only.  A lane adds its 16 masked values in register order, the
-// wave reduces in a fixed butterfly (xor 32, 16, 8, 4, 2, 1), the four waves meet in LDS and are added in wave order; tiles of xx /
-// yy are doubled (exact) and the block writes ONE double to ws[subset][tile].  No atomics.
+// Epilogue.  t = acc * gamma + coef0, value (t * t) * t, no contraction.  A zero row is not a zero kernel value (k = coef0^3), so
+// rows and columns past s are masked out of the sum again; a diagonal tile of xx / yy keeps i < j only.  A lane adds its 16 masked
+// values in register order, the wave reduces in a fixed butterfly (xor 32, 16, 8, 4, 2, 1), the four waves meet in LDS and are
+// added in wave order; tiles of xx / yy are doubled (exact) and the block writes ONE double to ws[subset][tile].  No atomics.
 //
 // poly3_mmd_finish_kernel: one block per subset, three threads; thread q adds the tile partials of sum q in tile order.  A
 // subset's three sums depend on nothing but that subset's rows, and the same inputs give the same bits on every call.
 #include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <cmath>
-#include "../../include/mogan_hip.h"
+#include "mogan_gram64.h"
 
 namespace {
 
-constexpr int NT = 256;        // 4 wave64
-constexpr int CT = 64;         // tile edge
-constexpr int KC = 32;         // features per staged chunk (8 MFMA k-steps of 4)
-constexpr int LDW = 80;        // LDS row stride in doubles (64 rows + 16: 160 dwords = 32 banks mod 64), as in mogan_stats.hip
-constexpr int KPT = KC * CT / NT;   // staged features per thread and panel: 8 contiguous floats of one row
-constexpr long long N_MAX = 2147483647LL;    // the index tables are int32
-constexpr int D_MAX = 65536;
 constexpr int S_MAX = 65535;                 // grid.y
 constexpr int SUB_MAX = 1 << 20;             // T <= 16384: 2 T^2 + T tiles stay below 2^31
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-static inline int ok_launch() { return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH; }
 
 static inline long long tiles_of(int s) {
     const long long T = (s + CT - 1) / CT;
@@ -59,18 +41,15 @@ __global__ __launch_bounds__(NT) void poly3_mmd_kernel(const float* __restrict__
                                                        long long Ny, int D, const int32_t* __restrict__ ix,
                                                        const int32_t* __restrict__ iy, int s, int T, double gamma, double coef0,
                                                        double* __restrict__ ws) {
-    __shared__ double sm[2][KC][LDW];
+    __shared__ GramLds sm;
     __shared__ double red[NT / 64];
     const int P = T * (T + 1) / 2;
     const int tile = blockIdx.x, subset = blockIdx.y;
-    // kind 0 = xx, 1 = yy (upper triangle, row by row: (0,0) .. (0,T-1), (1,1) .. (1,T-1), ...), 2 = xy (all tiles, row by row)
+    // kind 0 = xx, 1 = yy (upper triangle, row by row), 2 = xy (all tiles, row by row)
     int kind, bi, bj;
     if (tile < 2 * P) {
         kind = tile >= P ? 1 : 0;
-        int rem = tile - kind * P;
-        bi = 0;
-        while (rem >= T - bi) { rem -= T - bi; ++bi; }
-        bj = bi + rem;
+        gram_upper_tile(tile - kind * P, T, bi, bj);
     } else {
         kind = 2;
         const int r = tile - 2 * P;
@@ -85,72 +64,17 @@ __global__ __launch_bounds__(NT) void poly3_mmd_kernel(const float* __restrict__
     const int32_t* ib = (kind == 0 ? ix : iy) + (size_t)subset * s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    // staging: thread -> row tid >> 2 of both panels, features (tid & 3) * 8 .. + 7 of the chunk
-    const int srow = tid >> 2, sk = (tid & 3) * KPT;
-    const int pa = bi * CT + srow, pb = bj * CT + srow;
+    // the staged rows of this thread: subset positions pa, pb -> gathered, clamped rows of A and B
+    const int pa = bi * CT + RowPanels<VEC>::stage_row(), pb = bj * CT + RowPanels<VEC>::stage_row();
     const bool va = pa < s, vb = !diag && pb < s;
     long long ra_i = va ? (long long)ia[pa] : 0, rb_i = vb ? (long long)ib[pb] : 0;
     ra_i = ra_i < 0 ? 0 : (ra_i > NA - 1 ? NA - 1 : ra_i);
     rb_i = rb_i < 0 ? 0 : (rb_i > NB - 1 ? NB - 1 : rb_i);
-    const float* xa = A + (size_t)ra_i * D;
-    const float* xb = B + (size_t)rb_i * D;
-    float ra[KPT], rb[KPT];
-    auto fetch = [&](int k0) {
-        if (VEC) {                                            // D % 4 == 0: a group of 4 features is inside D or past it
-#pragma unroll
-            for (int h = 0; h < KPT / 4; ++h) {
-                const int k = k0 + sk + 4 * h;
-                const bool in = k < D;
-                const float4 a = (va && in) ? *reinterpret_cast<const float4*>(xa + k) : float4{0.f, 0.f, 0.f, 0.f};
-                const float4 b = (vb && in) ? *reinterpret_cast<const float4*>(xb + k) : float4{0.f, 0.f, 0.f, 0.f};
-                ra[4 * h] = a.x; ra[4 * h + 1] = a.y; ra[4 * h + 2] = a.z; ra[4 * h + 3] = a.w;
-                rb[4 * h] = b.x; rb[4 * h + 1] = b.y; rb[4 * h + 2] = b.z; rb[4 * h + 3] = b.w;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                const int k = k0 + sk + j;
-                const bool in = k < D;
-                ra[j] = (va && in) ? xa[k] : 0.f;
-                rb[j] = (vb && in) ? xb[k] : 0.f;
-            }
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            sm[0][sk + j][srow] = (double)ra[j];
-            if (!diag) sm[1][sk + j][srow] = (double)rb[j];
-        }
-    };
-
-    // compute: wave -> quarter (wr, wc) of the tile; lane -> k = lane >> 4 of a k-step, row lane & 15 of an MFMA tile
-    const int wr = wave >> 1, wc = wave & 1, lk = lane >> 4, lc = lane & 15;
-    const double* qa = &sm[0][lk][wr * 32 + lc];
-    const double* qb = &sm[diag ? 0 : 1][lk][wc * 32 + lc];
+    RowPanels<VEC> src(A + (size_t)ra_i * D, va, B + (size_t)rb_i * D, vb, D, diag);
     f64x4 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
+    gram64_tile(src, sm, acc);
 
-    fetch(0);
-    for (int k0 = 0; k0 < D; k0 += KC) {
-        stash();
-        __syncthreads();
-        if (k0 + KC < D) fetch(k0 + KC);
-#pragma unroll
-        for (int kk = 0; kk < KC / 4; ++kk) {
-            const double a0 = qa[kk * 4 * LDW], a1 = qa[kk * 4 * LDW + 16];
-            const double b0 = qb[kk * 4 * LDW], b1 = qb[kk * 4 * LDW + 16];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
+    const GramLane ln;
     double part = 0.0;
     {
 #pragma clang fp contract(off)
@@ -160,8 +84,7 @@ __global__ __launch_bounds__(NT) void poly3_mmd_kernel(const float* __restrict__
             for (int n = 0; n < 2; ++n)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int row = bi * CT + wr * 32 + m * 16 + lk + 4 * j;       // f64 C/D map: row = (lane >> 4) + 4 * reg
-                    const int col = bj * CT + wc * 32 + n * 16 + lc;
+                    const int row = ln.row(bi * CT, m, j), col = ln.col(bj * CT, n);
                     const bool keep = row < s && col < s && (!diag || row < col);
                     const double t = acc[m][n][j] * gamma + coef0;
                     const double v = (t * t) * t;
