@@ -6,7 +6,9 @@
 // Forward / data gradient (wino3_fwd_kernel, split-bf16 build): a block owns 96 output channels x 32 tiles (2 tile rows x 16 tile
 // columns = 4 x 32 output pixels) of one image, 8 waves, wave w the two transform positions 2w, 2w + 1; the transformed filters
 // arrive pre-split in lane order (wino3_weight_kernel), the halo is staged and transformed in LDS (see the kernel's comment).
-// Weight gradient (wino_wgrad_kernel + wino_wgrad_finish): tiles on K, both operands transformed in LDS, K-split partials.
+// Weight gradient (wino_wgrad_kernel / wg32::wino_wgrad_ci32_kernel + wino_wgrad_finish): tiles on K, both operands transformed in
+// LDS, K-split partials.  Input channels in multiples of 96: a block owns one row of the 4 x 4 positions for 96 co x 96 ci and
+// transforms only that row, each operand value once per launch; other counts: a block owns 96 co x 32 ci for all 16 positions.
 // One forward form since round 5: the round-2 kernel (fp32 filter planes split in registers), the prepared-planes entry points
 // and the lab switches lost their A/Bs and were removed; the native-fp32 build takes the direct kernels for these layers.
 #include <hip/hip_runtime.h>
@@ -22,6 +24,9 @@
 #endif
 #ifndef WGRAD_XCD
 #define WGRAD_XCD 1
+#endif
+#ifndef WGRAD_BLOCKS
+#define WGRAD_BLOCKS 256
 #endif
 #ifndef W5_XCD
 #define W5_XCD 1
@@ -563,15 +568,285 @@ __global__ __launch_bounds__(1024) void wino5_fwd_kernel(const float* __restrict
 
 // ------------------------------------------------------------------------------------------ weight gradient
 // dW = G^t [ sum over tiles (A dY A^t) .* (B^t d B) ] G: per position xi a GEMM dU_xi[co][ci] = sum_tiles Q_xi[co][tile]
-// V_xi[ci][tile] with the tiles on K.  A block owns 96 co x 32 ci for all 16 positions (wave w: xi = 2w, 2w+1; 2 x 3
-// accumulator tiles) and walks a contiguous range of K-chunks; a chunk = 8 tiles of one tile row (2 x 16 output pixels).
-// Per chunk: dY (96 x 2 x 16, straight from global into the threads that transform it) -> Qs[xi][tile][co], the input halo
-// (32 ci x 4 x 18) -> Xs -> Vs[xi][tile][ci]; both double buffered, one barrier per chunk, preparation of chunk c+1 in the
-// shadow of the MFMAs of chunk c.  The partial dU of every block goes to the workspace; wino_wgrad_finish sums the
-// K-splits in order and applies G^t (.) G.
+// V_xi[ci][tile] with the tiles on K.  A block owns ONE ROW g of the 4 x 4 transform positions for 96 co x 96 ci: 4 waves, wave w
+// the position xi = 4 g + w with 3 x 3 accumulator tiles, one wave per SIMD (the blocks of a launch split the positions, not the
+// input channels: every operand value of a chunk is transformed, written to LDS, read and split by exactly one wave of the
+// launch, where the 96 x 32 x 16-position block of rounds 2-6 transformed dY in each of its Cin / 32 blocks and the halo in each
+// of its Cout / 96).  It walks a contiguous range of K-chunks; a chunk = 8 tiles of one tile row (2 x 16 output pixels).
+// Per chunk, for row g only:
+//   Q row g = (A dY)[g] A^t: (A dY)[g] = dY0, dY0 + dY1, dY0 - dY1, -dY1 -- rows 0 / 3 load one dY row, not two -- 96 co x 8
+//             tiles x 4 columns, straight from global into the threads that transform it -> Qs[w][tile][co];
+//   V row g = (B^t d)[g] B:   (B^t d)[g] = d0 - d2, d1 + d2, d2 - d1, d1 - d3: the TWO halo rows it touches (96 ci x 2 x 20,
+//             as aligned column pairs ox - 2 .. ox + 17 of which 18 are used) -> Xs -> Vs[w][tile][ci].
+// All three double buffered, one barrier per chunk, preparation of chunk c+1 in the shadow of the MFMAs of chunk c.  The
+// partial dU of every block goes to the workspace; wino_wgrad_finish sums the K-splits in order and applies G^t (.) G.
+// Input channels come in multiples of 96 here (any other count takes wg32::wino_wgrad_ci32_kernel below).  FULL = the output
+// channels too (the generator's): no channel tests; otherwise an empty 32-wide co tile of the last co block is skipped by a
+// wave-uniform branch, split and MFMAs alike.
+// LDS 81,216 bytes (dynamic).  Registers (compiler's resource report): see the launch site.
+constexpr int WCT = 8, WBN = 96, WNP = 4, LDQ = BM + 4, LDV = WBN, WXC = 2 * WCT + 4, LDX = WBN + 1;
+constexpr int WG_QSZ = WNP * WCT * LDQ, WG_VSZ = WNP * WCT * LDV, WG_XSZ = 2 * WXC * LDX;
+constexpr size_t WG_LDS = (size_t)(2 * WG_QSZ + 2 * WG_VSZ + 2 * WG_XSZ) * sizeof(float);
+
+struct WgChunk { int k, cg, tr, img; };     // a chunk index and its tile column group / tile row / image
+
+template <bool FULL>
+__global__ __launch_bounds__(256) void wino_wgrad_kernel(const float* __restrict__ dY, const float* __restrict__ X,
+                                                         float* __restrict__ part, int Cin, int H, int W, int Cout,
+                                                         int nchunk, int cps, unsigned y_bytes, unsigned x_bytes) {
+    extern __shared__ __attribute__((aligned(16))) float wg_lds[];
+    float* const Qs = wg_lds;
+    float* const Vs = Qs + 2 * WG_QSZ;
+    float* const Xs = Vs + 2 * WG_VSZ;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l31 = lane & 31;
+    // (the blocks of one K range -- all (ci, co, row) blocks read the same dY / x chunks -- on one XCD: mma_xcd_block)
+#if WGRAD_XCD
+    unsigned bx_, by_, bz_; mma_xcd_block(bx_, by_, bz_);
+#else
+    const unsigned bx_ = blockIdx.x, by_ = blockIdx.y, bz_ = blockIdx.z;
+#endif
+    const int g = by_ & 3, n0 = bx_ * WBN, m0 = (by_ >> 2) * BM, sp = bz_;
+    const int na = FULL ? 3 : min(3, (Cout - m0 + 31) >> 5);   // non-empty 32-wide co tiles of the block
+    const int k_beg = sp * cps, k_end = min(nchunk, k_beg + cps);
+    const int plane = H * W;
+    const int cgs = W / (2 * WCT), trs = H / 2;             // chunks per tile row, tile rows per image
+    const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc((void*)dY, (short)0, (int)y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)X, (short)0, (int)x_bytes, 0x00020000);
+
+    f32x16 acc[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+    // dY role: pair e = tid + 256 r (r < 3; 768 pairs): co = e >> 3, tile column = e & 7
+    constexpr int NYE = BM * WCT / 256;                     // 3
+    unsigned yoff[NYE], ykill[NYE];
+#pragma unroll
+    for (int r = 0; r < NYE; ++r) {
+        const int e = tid + 256 * r, co = e >> 3, tc = e & 7;
+        ykill[r] = FULL || m0 + co < Cout ? 0u : 0xFFFFFFF8u;
+        yoff[r] = (unsigned)(m0 + co) * plane + 2 * tc;
+    }
+    const bool yrow0 = g != 3, yrow1 = g != 0;              // the dY rows that (A dY)[g] = dY0 + ys dY1 touches
+    const float ys = g == 1 ? 1.f : -1.f;
+    // X staging role: column pair e = tid + 256 i (i < 8; 1920 pairs): ci = e / 20, halo row hr = 0 / 1, pair hp (lanes run along
+    // the columns); xneed: which bits of the chunk's mask {row 0, row 1, left neighbour, right neighbour inside the image} it needs
+    constexpr int NXP = WBN * 2 * (WXC / 2), NXE = (NXP + 255) / 256;      // 1920, 8
+    const int h0 = g == 0 ? 0 : 1, h1 = g == 3 ? 3 : 2;    // the halo rows that (B^t d)[g] = vsa d[h0] + vsb d[h1] touches
+    const float vsa = g == 2 ? -1.f : 1.f, vsb = (g == 1 || g == 2) ? 1.f : -1.f;
+    int xl[NXE], xneed[NXE]; unsigned xoff[NXE];
+#pragma unroll
+    for (int i = 0; i < NXE; ++i) {
+        const int e = tid + 256 * i;
+        const int ci = e / WXC, r = e - ci * WXC;
+        const int hr = r / (WXC / 2), hp = r - hr * (WXC / 2);
+        const bool valid = e < NXP;
+        // (a thread past the last pair stores into the columns 19 of row 0 and 0 of row 1, which nobody reads)
+        xl[i] = e < NXP ? (hr * WXC + 2 * hp) * LDX + ci : (WXC - 1) * LDX;
+        xoff[i] = (unsigned)(n0 + ci) * plane + (unsigned)((hr ? h1 : h0) * W + 2 * hp - 2);
+        xneed[i] = (hr ? 2 : 1) | (hp == 0 ? 4 : 0) | (hp == WXC / 2 - 1 ? 8 : 0) | (valid ? 0 : 16) | 32;
+    }
+    // V role: item e = tid + 256 r (r < 3; 768 items): ci = e % 96, tile column = e / 96
+    int vx[NYE], vv[NYE];
+#pragma unroll
+    for (int r = 0; r < NYE; ++r) {
+        const int e = tid + 256 * r, tc = e / WBN, ci = e - tc * WBN;
+        vx[r] = (2 * tc + 1) * LDX + ci;
+        vv[r] = tc * LDV + ci;
+    }
+
+    float2 rx[NXE], ry[NYE][2];
+    WgChunk cy, cx;                                         // the next chunk load_y / load_x fetch (they only ever step by one)
+    cy.k = k_beg; cy.cg = k_beg % cgs; cy.tr = (k_beg / cgs) % trs; cy.img = (k_beg / cgs) / trs;
+    cx = cy;
+    auto next_chunk = [&](WgChunk& c) {
+        ++c.k;
+        const int wc = c.cg + 1 == cgs;
+        c.cg = wc ? 0 : c.cg + 1;
+        const int wr = wc & (c.tr + 1 == trs);
+        c.tr = wr ? 0 : c.tr + wc;
+        c.img += wr;
+    };
+    auto load_y = [&]() {                                   // chunks past k_end load as zeros
+        const bool live = cy.k < k_end;
+        const unsigned ub = (unsigned)(cy.img * Cout) * plane + (unsigned)(2 * cy.tr * W + 2 * WCT * cy.cg);
+#pragma unroll
+        for (int r = 0; r < NYE; ++r)
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) {                // (a row the position row does not touch: out of range, reads 0;
+                // or-ed in, not selected: a select on a uniform condition comes back as a branch around the load)
+                const unsigned o = ((yoff[r] + ub + rr * W) * 4u) | ((live & (rr ? yrow1 : yrow0)) ? 0u : 0xFFFFFFF8u) | ykill[r];
+                ry[r][rr] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rY, o, 0, 0));
+            }
+        next_chunk(cy);
+    };
+    auto load_x = [&]() {
+        const int oy = 2 * cx.tr, ox = 2 * WCT * cx.cg;
+        const unsigned ub = (unsigned)(cx.img * Cin) * plane + (unsigned)((oy - 1) * W + ox);
+        const int m = ((unsigned)(oy - 1 + h0) < (unsigned)H ? 1 : 0) | ((unsigned)(oy - 1 + h1) < (unsigned)H ? 2 : 0) |
+                      (ox > 0 ? 4 : 0) | (ox + 2 * WCT < W ? 8 : 0) | (cx.k < k_end ? 32 : 0);
+#pragma unroll
+        for (int i = 0; i < NXE; ++i) {
+            const unsigned o = (m & xneed[i]) == xneed[i] ? (xoff[i] + ub) * 4u : 0xFFFFFFF8u;
+            rx[i] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rX, o, 0, 0));
+        }
+        next_chunk(cx);
+    };
+    auto store_x = [&](float* Xd) {
+#pragma unroll
+        for (int i = 0; i < NXE; ++i) { Xd[xl[i]] = rx[i].x; Xd[xl[i] + LDX] = rx[i].y; }
+    };
+    auto transform_q = [&](float* Qd) {                     // row g of Q = A d A^t, A = [[1,0],[1,1],[1,-1],[0,-1]]
+#pragma unroll
+        for (int r = 0; r < NYE; ++r) {
+            const int e = tid + 256 * r, co = e >> 3, tc = e & 7;
+            const float R0 = __builtin_fmaf(ys, ry[r][1].x, ry[r][0].x), R1 = __builtin_fmaf(ys, ry[r][1].y, ry[r][0].y);
+            float* q = &Qd[tc * LDQ + co];
+            q[0] = R0;
+            q[WCT * LDQ] = R0 + R1;
+            q[2 * WCT * LDQ] = R0 - R1;
+            q[3 * WCT * LDQ] = -R1;
+        }
+    };
+    auto transform_v = [&](const float* Xc, float* Vd) {    // row g of V = B^t d B for (ci, tile column)
+#pragma unroll
+        for (int r = 0; r < NYE; ++r) {
+            const float* px = &Xc[vx[r]];
+            float u[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) u[j] = __builtin_fmaf(vsb, px[(WXC + j) * LDX], vsa * px[j * LDX]);
+            float* pv = &Vd[vv[r]];
+            pv[0] = u[0] - u[2];
+            pv[WCT * LDV] = u[1] + u[2];
+            pv[2 * WCT * LDV] = u[2] - u[1];
+            pv[3 * WCT * LDV] = u[1] - u[3];
+        }
+    };
+    // the wave's operands of one chunk: lane (h, l31) holds the tiles 2 kk + h of co / ci a * 32 + l31
+    auto read_ops = [&](const float* Qc, const float* Vc, float (&av)[WCT / 2][3], float (&bv)[WCT / 2][3]) {
+#pragma unroll
+        for (int kk = 0; kk < WCT / 2; ++kk) {
+            const int row = wave * WCT + 2 * kk + h;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                av[kk][a] = FULL || a < na ? Qc[row * LDQ + a * 32 + l31] : 0.f;
+                bv[kk][a] = Vc[row * LDV + a * 32 + l31];
+            }
+        }
+    };
+
+    if (k_beg < k_end) {
+        load_y(); load_x();
+        store_x(Xs);
+        load_x();
+        __syncthreads();
+        transform_q(Qs); transform_v(Xs, Vs);
+        load_y();
+        store_x(Xs + WG_XSZ);
+        load_x();
+        __syncthreads();
+#if MOGAN_X6
+        // split-bf16 form: a chunk pair is one MFMA k-extent (8 k-values per lane = 4 of the even + 4 of the odd chunk); chunks
+        // past k_end are staged as zeros, so an unpaired last chunk is simply paired with zeros.  The odd iteration splits the
+        // three A fragments and the B fragments one at a time and issues the MFMAs of ci tiles 0 and 1; those of ci tile 2 wait
+        // in registers (fa, fb2) for the next even iteration, which has no operands of its own to multiply yet: with one wave
+        // per SIMD the transforms of BOTH iterations then have MFMAs to run beside.
+        X6Frag fa[3] = {}, fb2 = {};
+        float ave[WCT / 2][3], bve[WCT / 2][3];
+        auto split_b = [&](const float (&bv)[WCT / 2][3], int b) {
+            float b8[8];
+#pragma unroll
+            for (int kk = 0; kk < WCT / 2; ++kk) { b8[kk] = bve[kk][b]; b8[4 + kk] = bv[kk][b]; }
+            return x6_split8(b8);
+        };
+        auto mma_b = [&](const X6Frag& fb, int b) {
+#pragma unroll
+            for (int term = 0; term < 6; ++term)
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+                    if (FULL || a < na) acc[a][b] = x6_mfma(fa[a], fb, term, acc[a][b]);
+        };
+        for (int k = k_beg; k < k_end; k += 2) {
+#pragma unroll
+            for (int par = 0; par < 2; ++par) {
+                const int cur = par, nxt = cur ^ 1;
+                float av[WCT / 2][3], bv[WCT / 2][3];
+                read_ops(Qs + cur * WG_QSZ, Vs + cur * WG_VSZ, av, bv);
+                if (par == 0) {
+                    mma_b(fb2, 2);                                  // (of the pair before; zeros the first time)
+#pragma unroll
+                    for (int kk = 0; kk < WCT / 2; ++kk)
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) { ave[kk][a] = av[kk][a]; bve[kk][a] = bv[kk][a]; }
+                }
+                transform_q(Qs + nxt * WG_QSZ);                     // dY(k+par+1) (in registers since the last iteration)
+                load_y();                                           // dY(k+par+2)
+                if (par == 1) {
+#pragma unroll
+                    for (int a = 0; a < 3; ++a)
+                        if (FULL || a < na) {
+                            float a8[8];
+#pragma unroll
+                            for (int kk = 0; kk < WCT / 2; ++kk) { a8[kk] = ave[kk][a]; a8[4 + kk] = av[kk][a]; }
+                            fa[a] = x6_split8(a8);
+                        }
+                    mma_b(split_b(bv, 0), 0);
+                }
+                store_x(Xs + cur * WG_XSZ);                         // X(k+par+2)
+                load_x();                                           // X(k+par+3)
+                if (par == 1) mma_b(split_b(bv, 1), 1);
+                transform_v(Xs + nxt * WG_XSZ, Vs + nxt * WG_VSZ);  // X(k+par+1) -> V(k+par+1)
+                if (par == 1) fb2 = split_b(bv, 2);
+                __syncthreads();
+            }
+        }
+        mma_b(fb2, 2);
+#else
+        for (int k = k_beg; k < k_end; ++k) {
+            const int cur = (k - k_beg) & 1, nxt = cur ^ 1;
+            float av[WCT / 2][3], bv[WCT / 2][3];
+            read_ops(Qs + cur * WG_QSZ, Vs + cur * WG_VSZ, av, bv);
+            transform_q(Qs + nxt * WG_QSZ);                         // dY(k+1) (in registers since the last iteration)
+            load_y();                                               // dY(k+2)
+            store_x(Xs + cur * WG_XSZ);                             // X(k+2)
+            load_x();                                               // X(k+3)
+            transform_v(Xs + nxt * WG_XSZ, Vs + nxt * WG_VSZ);      // X(k+1) -> V(k+1)
+#pragma unroll
+            for (int kk = 0; kk < WCT / 2; ++kk)
+#pragma unroll
+                for (int b = 0; b < 3; ++b)
+#pragma unroll
+                    for (int a = 0; a < 3; ++a)
+                        if (FULL || a < na)
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk][a], bv[kk][b], acc[a][b], 0, 0, 0);
+            __syncthreads();
+        }
+#endif
+    }
+    // partial dU[sp][xi][co][ci]
+    float* out = part + ((size_t)sp * 16 + 4 * g + wave) * Cout * Cin;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, n = n0 + b * 32 + l31;
+                if (m < Cout) out[(size_t)m * Cin + n] = acc[a][b][r];
+            }
+}
+
+// The 96 co x 32 ci block for input-channel counts that are no multiple of 96 (committed text of rounds 2-6, unchanged): a block
+// owns all 16 positions (8 waves, wave w: xi = 2w, 2w+1; 2 x 3 accumulator tiles), so an input-channel tail costs a 32-wide block
+// and not a 96-wide one.  Measured alone at B = 16 (ms, this kernel / the one above): 64 -> 96 at 64x64 0.093 / 0.101, 64 -> 128 at
+// 64x64 0.114 / 0.158, 48 -> 96 at 128x128 0.216 / 0.308 (profiles/wino_wgrad_once_ab.json).
+namespace wg32 {
 constexpr int WCT = 8, WBN = 32, LDQ = BM + 4, WXR = 4, WXC = 2 * WCT + 2, LDX = 33;
 
-__global__ __launch_bounds__(512) void wino_wgrad_kernel(const float* __restrict__ dY, const float* __restrict__ X,
+__global__ __launch_bounds__(512) void wino_wgrad_ci32_kernel(const float* __restrict__ dY, const float* __restrict__ X,
                                                          float* __restrict__ part, int Cin, int H, int W, int Cout,
                                                          int nchunk, int cps, unsigned y_bytes, unsigned x_bytes) {
     constexpr int QSZ = 16 * WCT * LDQ, VSZ = 16 * WCT * WBN, XSZ = WXR * WXC * LDX;
@@ -804,6 +1079,7 @@ __global__ __launch_bounds__(512) void wino_wgrad_kernel(const float* __restrict
             }
     }
 }
+}  // namespace wg32
 
 // dW[co][ci] (+)= G^t (sum_sp dU[sp][.][co][ci]) G,  G^t = [[1,.5,.5,0],[0,.5,-.5,0],[0,.5,.5,1]]
 __global__ __launch_bounds__(64) void wino_wgrad_finish(const float* __restrict__ part, float* __restrict__ dw, int Cout,
@@ -924,13 +1200,18 @@ int mogan_wino_wgrad_try(const float* dy, const float* x, float* dw, const Mogan
     if ((((uintptr_t)dy) & 7) != 0) return 0;
     if ((long long)B * Cin * H * W >= (1ll << 30) || (long long)B * Cout * H * W >= (1ll << 30)) return 0;
     const int nchunk = B * (H / 2) * (W / (2 * WCT));
-    const int tiles_mn = ((Cout + BM - 1) / BM) * ((Cin + WBN - 1) / WBN);
-    // one 8-wave block per CU and ONE round of blocks: the K-split partials (16 x Cout x Cin floats per split) are what the
-    // finish pass has to read back (256 blocks: 156 / 137 TF direct-equivalent at 128x128 / 64x64; 512: 147 / 117).  In the train step
-    // this kernel runs on the weight-gradient side stream BESIDE the generator's data-gradient chain: with 256 persistent blocks it
-    // holds every CU for ~240 us and the chain's short kernels queue behind it; 192 blocks leave a quarter of the CUs to the chain:
-    // 405.0 / 406.6 vs 402.3 / 399.3 img/s (224: 404.4, 160: 403.6; tools/wino_wg_blocks_probe.sh) -- the default since round 3
-    constexpr int wg_blocks = 192;
+    // input channels in multiples of 96 (the generator's ResBlocks): the position-row block; any other count: the 96 x 32 block
+    const bool rows = Cin % WBN == 0;
+    const int cob = (Cout + BM - 1) / BM;
+    const int tiles_mn = rows ? cob * (Cin / WBN) * WNP : cob * ((Cin + wg32::WBN - 1) / wg32::WBN);
+    // ONE round of blocks, one block per CU: the K-split partials (16 x Cout x Cin floats per split) are what the finish pass
+    // has to read back.  In the train step this kernel runs on the weight-gradient side stream BESIDE the generator's data-gradient
+    // chain.  The 8-wave 96 x 32 block fills a CU's registers, and with 256 blocks the chain's short kernels queued behind it:
+    // 192 blocks, which leave a quarter of the CUs to the chain, measured 405.0 / 406.6 img/s against 402.3 / 399.3 (round 3).
+    // The 4-wave position-row block leaves a third of each SIMD's registers free; in the step 256 / 192 / 128 blocks measured
+    // 453.6 453.7 454.4 / 454.2 451.7 452.8 / 454.5 451.6 img/s, interleaved, the parent 447.4 446.8 448.7 -- no difference to
+    // tell, and alone 256 blocks use every CU (profiles/wino_wgrad_once_ab.json).  -DWGRAD_BLOCKS=n builds another count.
+    const int wg_blocks = rows ? WGRAD_BLOCKS : 192;
     int nsplit = wg_blocks / tiles_mn;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > nchunk / 8) nsplit = nchunk / 8 > 0 ? nchunk / 8 : 1;
@@ -939,9 +1220,29 @@ int mogan_wino_wgrad_try(const float* dy, const float* x, float* dw, const Mogan
     if ((size_t)nsplit * slab > ws_bytes) nsplit = (int)(ws_bytes / slab);
     const int cps = (nchunk + nsplit - 1) / nsplit;
     nsplit = (nchunk + cps - 1) / cps;
-    dim3 grid((unsigned)((Cin + WBN - 1) / WBN), (unsigned)((Cout + BM - 1) / BM), (unsigned)nsplit);
-    hipLaunchKernelGGL(wino_wgrad_kernel, grid, dim3(512), 0, st, dy, x, (float*)ws, Cin, H, W, Cout, nchunk, cps,
-                       (unsigned)(4ull * B * Cout * H * W), (unsigned)(4ull * B * Cin * H * W));
+    const unsigned yb = (unsigned)(4ull * B * Cout * H * W), xb = (unsigned)(4ull * B * Cin * H * W);
+    if (rows) {
+        // dynamic LDS beyond 64 KB needs the attribute, once per kernel
+        static bool attr = false;
+        if (!attr) {
+            if (hipFuncSetAttribute((const void*)wino_wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS) != hipSuccess ||
+                hipFuncSetAttribute((const void*)wino_wgrad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS) != hipSuccess)
+                return MOGAN_ERR_LAUNCH;
+            attr = true;
+        }
+        // grid: ci blocks x (co block, position row) x K splits -- the position rows of a co block are neighbours in the XCD order.
+        // Compiler's resource report (not measured): 189 VGPRs + 176 AGPRs with full co blocks, 1 wave per SIMD, no scratch.
+        dim3 grid((unsigned)(Cin / WBN), (unsigned)(cob * WNP), (unsigned)nsplit);
+        if (Cout % BM == 0)
+            hipLaunchKernelGGL(wino_wgrad_kernel<true>, grid, dim3(64 * WNP), WG_LDS, st, dy, x, (float*)ws, Cin, H, W, Cout, nchunk,
+                               cps, yb, xb);
+        else
+            hipLaunchKernelGGL(wino_wgrad_kernel<false>, grid, dim3(64 * WNP), WG_LDS, st, dy, x, (float*)ws, Cin, H, W, Cout, nchunk,
+                               cps, yb, xb);
+    } else {
+        dim3 grid((unsigned)((Cin + wg32::WBN - 1) / wg32::WBN), (unsigned)cob, (unsigned)nsplit);
+        hipLaunchKernelGGL(wg32::wino_wgrad_ci32_kernel, grid, dim3(512), 0, st, dy, x, (float*)ws, Cin, H, W, Cout, nchunk, cps, yb, xb);
+    }
     const long long n = (long long)Cout * Cin;
     if (wg_on != 2)     // (2 = timing aid: main kernel only)
     hipLaunchKernelGGL(wino_wgrad_finish, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const float*)ws, dw, Cout,
