@@ -1,0 +1,454 @@
+"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9f).
+
+`CheckpointEvaluation` is the base of `trainer.condGANTrainer` that holds every path which reads a finished checkpoint instead of
+training one: `sampling` / `sample` (images), `r_precision`, and `pool_codes` with the three scores `fid` / `kid` / `prdc` that share
+its pass.  It needs `self.device`, `self.data_loader`, `self.n_words` and `self.ixtoword` of the trainer and nothing of the train
+step.  What these paths have in common is written once here: the NET_G guard and the save-directory rule (`net_g_missing`,
+`eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
+(`generate_seeded`), and what the three scores do around their own device calls (`PooledCodes`, `trunk_note`)."""
+import json
+import os
+
+import numpy as np
+import torch
+
+from ..hip import ops
+from .miscc.config import cfg
+from .miscc.utils import mkdir_p, weights_init
+from .model import CNN_ENCODER, G_NET, RNN_ENCODER
+
+
+def draw_bbox_lines(data_img, boxes, imsize):
+    """trainer.py:556-566: white (value 1) one-pixel rectangles of the relative boxes (x, y, w, h) on every image of
+    the row; pixel coordinates are int(imsize * v) of each value SEPARATELY, w and h are capped at imsize - 1, the first
+    absent box (x <= -1) ends the loop."""
+    for idx in range(boxes.shape[0]):
+        x, y, w, h = tuple(int(imsize * float(v)) for v in boxes[idx])
+        w = imsize - 1 if w > imsize - 1 else w
+        h = imsize - 1 if h > imsize - 1 else h
+        if x <= -1:
+            break
+        data_img[:, :, y, x:x + w] = 1
+        data_img[:, :, y:y + h, x] = 1
+        data_img[:, :, y + h, x:x + w] = 1
+        data_img[:, :, y:y + h, x + w] = 1
+    return data_img
+
+
+def caption_sentence(cap, ixtoword):
+    """trainer.py:569-576: the words of a zero-terminated caption joined by blanks, non-ASCII characters dropped."""
+    words = []
+    for ix in cap:
+        if int(ix) == 0:
+            break
+        words.append(ixtoword[int(ix)].encode('ascii', 'ignore').decode('ascii'))
+    return " ".join(words)
+
+
+def net_g_missing(what='model NET_G'):
+    """The guard of every evaluation path: True, with the reference's message, where TRAIN.NET_G names no checkpoint
+    (`what` keeps the reference's wording of trainer.py:389 for sampling())."""
+    if cfg.TRAIN.NET_G == '':
+        print('Error: the path for %s is not found!' % what)
+        return True
+    return False
+
+
+def eval_save_dir(split_dir, sep='/'):
+    """<NET_G minus .pth>/<split> of the evaluation paths ('test' reads the 'valid' split), created; sample() joins the
+    two with '_' as the reference does (trainer.py:508)"""
+    if split_dir == 'test':
+        split_dir = 'valid'
+    save_dir = cfg.TRAIN.NET_G[:cfg.TRAIN.NET_G.rfind('.pth')] + sep + split_dir
+    mkdir_p(save_dir)
+    return save_dir
+
+
+def write_json(save_dir, name, out):
+    with open('%s/%s.json' % (save_dir, name), 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+
+
+def encode_text(text_encoder, captions, cap_lens):
+    """The text side of one batch (trainer.py:431-437): (words_embs, sent_emb, mask), both embeddings contiguous, the
+    mask of the padding words cut to the word count the encoder returned.  Call it under torch.no_grad()."""
+    hidden = text_encoder.init_hidden(captions.shape[0])
+    words_embs, sent_emb = text_encoder(captions, cap_lens.cpu(), hidden)
+    mask = (captions == 0)
+    if mask.size(1) > words_embs.size(2):
+        mask = mask[:, :words_embs.size(2)]
+    return words_embs.contiguous(), sent_emb.contiguous(), mask
+
+
+def generate_seeded(netG, gen, words_embs, sent_emb, mask, tmi, label_one_hot):
+    """One 256x256 image per caption from the seeded device generator `gen`: `noise` (B, Z_DIM) is drawn first, then the
+    conditioning noise `eps` (B, CONDITION_DIM) -- the order is a contract, r_precision and pool_codes see the same images
+    under the same seed."""
+    B = sent_emb.shape[0]
+    noise = torch.randn(B, cfg.GAN.Z_DIM, device=sent_emb.device, generator=gen)
+    eps = torch.randn(B, cfg.GAN.CONDITION_DIM, device=sent_emb.device, generator=gen)
+    fake_imgs, _, _, _ = netG(noise, sent_emb, words_embs, mask, tmi, label_one_hot, eps=eps)
+    return fake_imgs[-1]
+
+
+def trunk_note(what, figure, unit):
+    """the note of fid.json / kid.json / prdc.json: what the score is under an ImageNet trunk and under a random-init one"""
+    return ("%s of Inception pool codes under the trunk of NET_E's image encoder: %s under torchvision's "
+            "Inception-v3 if that trunk holds ImageNet weights (published figures mostly use the TF-ported network), %s "
+            "in random convolutional features -- comparable between checkpoints under this trunk only -- if it is random-init."
+            % (what, figure, unit))
+
+
+class PooledCodes:
+    """What fid(), kid() and prdc() do around their own device calls: the codes of one pass (pool_codes; or the `codes` a
+    caller hands over, checked against `seed`) cut to their `n` filled rows as `real` / `fake`, the save directory, the JSON
+    with the keys the three files share, and the return_codes result.  `want_real` is pool_codes' argument; where the
+    real side is wanted and handed-over codes hold none, that is a ValueError (`or_else` ends its message)."""
+
+    def __init__(self, trainer, who, split_dir, num_samples, seed, codes, want_real=True, or_else=""):
+        if codes is None:
+            codes = trainer.pool_codes(split_dir, num_samples, seed, want_real)
+        else:
+            if int(codes["seed"]) != int(seed):
+                raise ValueError("%s: the codes were taken under seed %d, not %d" % (who, codes["seed"], seed))
+            if callable(want_real):
+                want_real = want_real(codes["trunk_digest"], int(codes["fake"].shape[1]))
+            if not want_real:
+                codes = dict(codes, real=None)
+            elif codes["real"] is None:
+                raise ValueError("%s: the codes handed over hold no real side%s" % (who, or_else))
+        self.who, self.seed, self.n, self.digest = who, int(seed), codes["n"], codes["trunk_digest"]
+        self.real = None if codes["real"] is None else codes["real"][:self.n]
+        self.fake = codes["fake"][:self.n]
+        self.save_dir = eval_save_dir(split_dir)
+
+    def write(self, out, n_real, n_fake, note):
+        """adds the common keys to `out`, writes <save_dir>/<who>.json and returns `out`"""
+        out.update({"n_real": int(n_real), "n_fake": int(n_fake), "seed": self.seed, "NET_G": cfg.TRAIN.NET_G,
+                    "NET_E": cfg.TRAIN.NET_E, "trunk_digest": self.digest, "note": note})
+        write_json(self.save_dir, self.who, out)
+        return out
+
+    def result(self, out, return_codes):
+        if return_codes:
+            return out, {"real": None if self.real is None else self.real.cpu(), "fake": self.fake.cpu()}
+        return out
+
+
+class CheckpointEvaluation(object):
+    """The evaluation methods of condGANTrainer (reference trainer.py:387-579 and DESIGN.md sections 9c-9f)."""
+
+    def _load_eval_models(self):
+        """The two checkpoints of the evaluation paths (trainer.py:397-417, 483-505): EMA generator from
+        cfg.TRAIN.NET_G["netG"], DAMSM text encoder from cfg.TRAIN.NET_E, both in eval mode."""
+        netG = G_NET()
+        netG.apply(weights_init)
+        sd = torch.load(cfg.TRAIN.NET_G, map_location='cpu')
+        netG.load_state_dict(sd["netG"])
+        print('Load G from: ', cfg.TRAIN.NET_G)
+        netG = netG.to(self.device).eval()
+        text_encoder = RNN_ENCODER(self.n_words, nhidden=cfg.TEXT.EMBEDDING_DIM)
+        if cfg.TRAIN.NET_E != '':
+            text_encoder.load_state_dict(torch.load(cfg.TRAIN.NET_E, map_location='cpu'))
+            print('Load text encoder from:', cfg.TRAIN.NET_E)
+        return netG, text_encoder.to(self.device).eval()
+
+    def _load_image_encoder(self):
+        """The image encoder that TRAIN.NET_E's text encoder was trained with: the `image_encoder` twin of its path, by
+        build_models' rule and with its error.  The heads are TEXT.EMBEDDING_DIM wide as in training (outside training the
+        reference's constructor fixes them at 256, model.py:213, which is the same thing for the published pairs only)."""
+        nef = cfg.TEXT.EMBEDDING_DIM
+        image_encoder = CNN_ENCODER(nef, pretrained=False)
+        if image_encoder.nef != nef:
+            image_encoder.nef = nef
+            image_encoder.emb_features = type(image_encoder.emb_features)(768, nef, kernel_size=1, stride=1, padding=0, bias=False)
+            image_encoder.emb_cnn_code = type(image_encoder.emb_cnn_code)(2048, nef)
+            image_encoder.init_trainable_weights()
+        if cfg.TRAIN.NET_E != '':
+            img_path = cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder')
+            for path in (cfg.TRAIN.NET_E, img_path):
+                if not os.path.isfile(path):
+                    raise FileNotFoundError("DAMSM encoder checkpoint not found: %s (cwd %s)" % (path, os.getcwd()))
+            image_encoder.load_state_dict(torch.load(img_path, map_location='cpu'))
+            print('Load image encoder from:', img_path)
+        for p in image_encoder.parameters():
+            p.requires_grad = False
+        return image_encoder.to(self.device).eval()
+
+    def _load_seeded(self, seed):
+        """The networks of the seeded paths under torch.manual_seed(seed) (which fixes the random-init encoders of an empty
+        NET_E) and the device generator the noise comes from: (netG, text_encoder, image_encoder, generator)"""
+        torch.manual_seed(seed)
+        netG, text_encoder = self._load_eval_models()
+        image_encoder = self._load_image_encoder()
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(seed)
+        return netG, text_encoder, image_encoder, gen
+
+    def sampling(self, split_dir, num_samples=30000):
+        """trainer.py:387-470: load cfg.TRAIN.NET_G (EMA generator of a checkpoint) and cfg.TRAIN.NET_E (DAMSM text
+        encoder), generate one 256x256 image per caption of the data loader with netG.eval() and save it as
+        <NET_G minus .pth>/<split>/single/<key>_s<batch index>.png"""
+        from PIL import Image
+        from .datasets import prepare_data
+        if net_g_missing('morels'):
+            return None
+        netG, text_encoder = self._load_eval_models()
+        save_dir = eval_save_dir(split_dir)
+        written = []
+        for step, data in enumerate(self.data_loader, 0):
+            if step >= num_samples:
+                break
+            imgs, captions, cap_lens, class_ids, keys, (tm, tmi), label_one_hot = prepare_data(data, self.device)
+            B = captions.shape[0]
+            with torch.no_grad():
+                words_embs, sent_emb, mask = encode_text(text_encoder, captions, cap_lens)
+                noise = torch.randn(B, cfg.GAN.Z_DIM, device=self.device)
+                fake_imgs, _, _, _ = netG(noise, sent_emb, words_embs, mask, tmi, label_one_hot)
+            out = fake_imgs[-1].add(1.0).mul(127.5).clamp(0, 255).byte().permute(0, 2, 3, 1).cpu().numpy()
+            for j in range(B):
+                s_tmp = '%s/single/%s' % (save_dir, keys[j])
+                mkdir_p(s_tmp[:s_tmp.rfind('/')] if '/' in keys[j] else '%s/single' % save_dir)
+                fullpath = '%s_s%d.png' % (s_tmp, step)
+                Image.fromarray(out[j]).save(fullpath)
+                written.append(fullpath)
+        return written
+
+    def r_precision(self, split_dir, num_samples=30000, n_mismatched=99, folds=10, seed=100, real=False, return_codes=False):
+        """R-precision of the checkpoint TRAIN.NET_G under the DAMSM pair TRAIN.NET_E: one 256x256 image per
+        caption of the data loader (EMA generator, eval mode, seeded noise) -- or, with real=True, the real 256x256 image: the
+        ceiling the encoder pair allows --, its image code ranked against its own caption and `n_mismatched` captions of other
+        images of the split (hip/ops.retrieval_rank, one launch per batch; the ranks stay on the device until the end).
+        `seed` fixes the noise, the mismatched draws, the bank's long-caption subsets and, with an empty NET_E, the random-init
+        encoders.  A split with fewer than `n_mismatched` captions of other images is ranked against as many as it has.
+        Writes <NET_G minus .pth>/<split>/r_precision.json and returns its content; with return_codes also a dict of host
+        tensors: the image codes "code", "pos", "idx", the ranks "rank" and the "bank" the rows of idx point into."""
+        from .datasets import prepare_data
+        from .retrieval import SentenceBank, draw_mismatched, fold_stats
+        if net_g_missing():
+            return None
+        netG, text_encoder, image_encoder, gen = self._load_seeded(seed)
+        save_dir = eval_save_dir(split_dir)
+        bank = SentenceBank.from_dataset(text_encoder, self.data_loader.dataset, cfg.TEXT.WORDS_NUM, seed)
+        usable = len(bank) - int(np.bincount(bank.image_index).max())       # captions of other images, for the fullest image
+        if usable < 1:
+            raise ValueError("r_precision: the split holds no caption of another image to rank against")
+        if n_mismatched > usable:
+            print("R-precision: the split has %d captions of other images per query, not %d -- ranking against %d (a smaller "
+                  "candidate set gives a HIGHER figure; the JSON records it)" % (usable, n_mismatched, usable))
+            n_mismatched = usable
+        rng = np.random.RandomState(seed)
+        ranks, codes, poss, idxs, n = [], [], [], [], 0
+        for data in self.data_loader:
+            if n >= num_samples:
+                break
+            imgs, captions, cap_lens, class_ids, keys, (tm, tmi), label_one_hot = prepare_data(data, self.device)
+            with torch.no_grad():
+                words_embs, sent_emb, mask = encode_text(text_encoder, captions, cap_lens)
+                img = imgs[-1] if real else generate_seeded(netG, gen, words_embs, sent_emb, mask, tmi, label_one_hot)
+                code = image_encoder(img)[1]
+                idx = draw_mismatched(bank.image_index, bank.images_of(keys), n_mismatched, rng)
+                ranks.append(ops.retrieval_rank(code, sent_emb, bank.bank, idx))
+            if return_codes:
+                codes.append(code); poss.append(sent_emb); idxs.append(torch.from_numpy(idx))
+            n += captions.shape[0]
+        if not ranks:
+            raise ValueError("r_precision: the data loader gave no batch")
+        rank = torch.cat(ranks)[:num_samples].cpu()                      # the one read-back
+        out = fold_stats(rank.numpy(), folds)
+        out.update({"n_mismatched": int(n_mismatched), "seed": int(seed), "real": bool(real), "NET_G": cfg.TRAIN.NET_G,
+                    "NET_E": cfg.TRAIN.NET_E})
+        write_json(save_dir, "r_precision", out)
+        print("R-precision (%s images, %d queries, %d mismatched): %.4f, folds %.4f +- %.4f -> %s/r_precision.json"
+              % ("real" if real else "generated", out["n"], n_mismatched, out["r_precision"], out["mean"], out["std"], save_dir))
+        if return_codes:
+            k = rank.numel()
+            return out, {"code": torch.cat(codes)[:k].cpu(), "pos": torch.cat(poss)[:k].cpu(), "idx": torch.cat(idxs)[:k],
+                         "rank": rank, "bank": bank.bank.cpu()}
+        return out
+
+    def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True):
+        """The one pass over the data loader that fid() and kid() share: the real 256x256 image and one generated 256x256 image per
+        caption (EMA generator, eval mode, noise from the seeded device generator exactly as r_precision draws it) go through
+        CNN_ENCODER.pool_code; the codes stay on the device in two preallocated (num_samples, 2048) fp32 buffers.  `want_real`
+        False leaves the real images out of the trunk; it may also be a callable (trunk digest, code width) -> bool, asked once the
+        image encoder is loaded and before the pass (fid() decides there whether a statistics file replaces the real side).
+        `split_dir` names the split the data loader was built for; the pass itself reads the loader only.
+        Returns a dict: "real" (None where not wanted) and "fake", the device buffers, of which the first "n" rows are filled;
+        "trunk_digest"; the "seed" the pass ran under.  None, with fid()'s message, where TRAIN.NET_G is empty."""
+        from .datasets import prepare_data
+        from .fid import trunk_digest
+        if net_g_missing():
+            return None
+        netG, text_encoder, image_encoder, gen = self._load_seeded(seed)
+        D = int(image_encoder.emb_cnn_code.weight.shape[1])                 # 2048: the pooled code's width
+        digest = trunk_digest(image_encoder)
+        if callable(want_real):
+            want_real = want_real(digest, D)
+        rows = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        fake_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device)
+        real_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device) if want_real else None
+        n = 0
+        for data in self.data_loader:
+            if n >= rows:
+                break
+            imgs, captions, cap_lens, class_ids, keys, (tm, tmi), label_one_hot = prepare_data(data, self.device)
+            take = min(captions.shape[0], rows - n)
+            with torch.no_grad():
+                words_embs, sent_emb, mask = encode_text(text_encoder, captions, cap_lens)
+                fake = generate_seeded(netG, gen, words_embs, sent_emb, mask, tmi, label_one_hot)
+                fake_codes[n:n + take] = image_encoder.pool_code(fake)[:take]
+                if real_codes is not None:
+                    real_codes[n:n + take] = image_encoder.pool_code(imgs[-1])[:take]
+            n += take
+        return {"real": real_codes, "fake": fake_codes, "n": n, "trunk_digest": digest, "seed": int(seed)}
+
+    def fid(self, split_dir, num_samples=30000, seed=100, stats_path=None, return_codes=False, codes=None):
+        """Frechet distance between real and generated images of the checkpoint TRAIN.NET_G in the Inception pool codes of
+        TRAIN.NET_E's image encoder: the codes of ONE pass over the data loader (pool_codes; or the `codes`
+        a caller hands over from a pass of its own, which kid() can share) stay on the device, their
+        fp64 mean and covariance come from hip/ops.feature_moments after the loop and the distance from fid.frechet_distance on
+        the host.  With `stats_path` the real side is loaded from that file when it exists and was taken under the same trunk
+        (the real images then skip the trunk), and computed and saved there otherwise.  With a trunk that holds torchvision's
+        ImageNet weights the figure is FID under torchvision's Inception-v3; with a random-init trunk it is a Frechet distance in
+        random convolutional features, comparable between checkpoints under the same trunk only.
+        Writes <NET_G minus .pth>/<split>/fid.json and returns its content; with return_codes also a dict of the two code matrices
+        on the host, "real" (None where the real side was loaded) and "fake"."""
+        from .fid import FeatureStats, frechet_distance
+        if net_g_missing():
+            return None
+        loaded = []
+
+        def want_real(digest, D):
+            if stats_path is not None and os.path.isfile(stats_path):
+                loaded.append(FeatureStats.load(stats_path, digest, D))     # ValueError for another trunk's file
+                print('Load real-image statistics from: %s (%d images)' % (stats_path, loaded[0].n))
+            return not loaded
+        c = PooledCodes(self, "fid", split_dir, num_samples, seed, codes, want_real, " and there is no statistics file")
+        n, D = c.n, int(c.fake.shape[1])
+        if n < 2:
+            raise ValueError("fid: the data loader gave %d images; a covariance needs two at least" % n)
+        fake_stats = FeatureStats(*[t.cpu() for t in ops.feature_moments(c.fake)], n, c.digest)
+        if loaded:
+            real_stats = loaded[0]
+        else:
+            real_stats = FeatureStats(*[t.cpu() for t in ops.feature_moments(c.real)], n, c.digest)
+            if stats_path is not None:
+                real_stats.save(stats_path)
+                print('Save real-image statistics to: %s' % stats_path)
+        dist, terms = frechet_distance(real_stats.mean, real_stats.cov, fake_stats.mean, fake_stats.cov)
+        few = min(real_stats.n, fake_stats.n)
+        note = trunk_note("Frechet distance", "FID", "a distance")
+        if few < D:
+            note += (" n = %d < %d features: the covariances are rank-deficient, so the figure is biased and only comparable "
+                     "at equal n." % (few, D))
+            print("FID: %d images for %d features -- the covariances are rank-deficient, the figure is biased and only comparable "
+                  "at equal n (the JSON records it)" % (few, D))
+        out = c.write(dict(terms, fid=dist), real_stats.n, fake_stats.n, note)
+        print("FID (%d real, %d generated images): %.4f = |dmu|^2 %.4f + Tr S_real %.4f + Tr S_fake %.4f - 2 x %.4f -> %s/fid.json"
+              % (out["n_real"], out["n_fake"], dist, terms["mean_sq"], terms["tr_s1"], terms["tr_s2"], terms["tr_sqrt"], c.save_dir))
+        return c.result(out, return_codes)
+
+    def kid(self, split_dir, num_samples=30000, seed=100, subsets=100, subset_size=1000, codes=None, return_codes=False):
+        """Kernel Inception distance between real and generated images of the checkpoint TRAIN.NET_G in the Inception pool codes
+        of TRAIN.NET_E's image encoder: the unbiased estimate of the squared maximum mean discrepancy under
+        k(a, b) = (<a, b> / D + 1)^3, averaged over `subsets` random subset pairs of `subset_size` codes each (kid.draw_subsets
+        under `seed`; the size is lowered to the number of images where there are fewer).  The codes are those of fid() -- ONE
+        pass over the data loader (pool_codes), or the `codes` a caller hands over from a pass of its own -- and stay on the device;
+        the three sums per subset pair come from hip/ops.poly_mmd_sums in one call, the figure from kid.kid_from_sums on the host.
+        Unlike the Frechet distance the estimator has no bias that depends on n; it may be negative.  The real images always go
+        through the trunk.  Writes <NET_G minus .pth>/<split>/kid.json and returns its content; with return_codes also a dict of
+        the two code matrices on the host, "real" and "fake"."""
+        from . import kid as KID
+        if net_g_missing():
+            return None
+        c = PooledCodes(self, "kid", split_dir, num_samples, seed, codes)
+        n, D = c.n, int(c.fake.shape[1])
+        s = KID.subset_size(n, n, subset_size)
+        ix, iy = KID.draw_subsets(n, n, subsets, s, seed)
+        gamma = 1.0 / D
+        sums = ops.poly_mmd_sums(c.real, c.fake, ix, iy, gamma=gamma, coef0=KID.COEF0).cpu().numpy()   # the one read-back
+        mean, std, _ = KID.kid_from_sums(sums, s)
+        note = trunk_note("Kernel Inception distance (unbiased MMD^2 under the cubic polynomial kernel, mean over subset pairs)",
+                          "KID", "a distance")
+        if s < int(subset_size):
+            note += (" subset_size lowered from %d to %d: there are only %d images per side." % (subset_size, s, n))
+            print("KID: %d images per side -- subsets of %d codes instead of %d (the JSON records it)" % (n, s, subset_size))
+        out = c.write({"kid": mean, "kid_std": std, "subsets": int(subsets), "subset_size": int(s), "gamma": gamma,
+                       "coef0": float(KID.COEF0), "degree": int(KID.DEGREE)}, n, n, note)
+        print("KID (%d real, %d generated images; %d subset pairs of %d): %.6f +- %.6f -> %s/kid.json"
+              % (n, n, out["subsets"], s, mean, std, c.save_dir))
+        return c.result(out, return_codes)
+
+    def prdc(self, split_dir, num_samples=30000, seed=100, k_pr=3, k_dc=5, codes=None, return_codes=False):
+        """Improved precision / recall (k_pr nearest neighbours) and density / coverage (k_dc) between real and generated images of
+        the checkpoint TRAIN.NET_G in the Inception pool codes of TRAIN.NET_E's image encoder (attngan/prdc.py
+        has the definitions): where the Frechet distance and KID give one number, these tell a generator whose images are sharp but
+        alike (precision high, recall low) from one whose images are varied but poor.  The codes are those of fid() -- ONE pass over
+        the data loader (pool_codes), or the `codes` a caller hands over from a pass of its own -- and stay on the device: two
+        calls of hip/ops.knn_sqdist give every code's radii inside its own set, three of hip/ops.ball_counts the memberships
+        between the sets, and the counts are read back once; the k's are lowered to n - 1 where there are fewer images.  All four
+        figures depend on n.  The real images always go through the trunk.  Writes <NET_G minus .pth>/<split>/prdc.json and
+        returns its content; with return_codes also a dict of the two code matrices on the host, "real" and "fake"."""
+        from . import prdc as PRDC
+        if net_g_missing():
+            return None
+        c = PooledCodes(self, "prdc", split_dir, num_samples, seed, codes)
+        n, real_codes, fake_codes = c.n, c.real, c.fake
+        if n < 2:
+            raise ValueError("prdc: the data loader gave %d images; a nearest neighbour needs two at least" % n)
+        kp, kd = PRDC.neighbours(n, n, k_pr, k_dc)
+        real_r2 = ops.knn_sqdist(real_codes, max(kp, kd))                                  # every real code's radii, both k's
+        fake_r2 = ops.knn_sqdist(fake_codes, kp)
+        fake_in_real = ops.ball_counts(fake_codes, real_codes, real_r2[:, [kp - 1, kd - 1]].contiguous(), "support")
+        real_in_fake = ops.ball_counts(real_codes, fake_codes, fake_r2[:, kp - 1].contiguous(), "support")
+        real_own = ops.ball_counts(real_codes, fake_codes, real_r2[:, kd - 1].contiguous(), "query")
+        counts = torch.cat([fake_in_real, real_in_fake, real_own], dim=1).cpu().numpy()      # (n, 4): the one read-back
+        scores = PRDC.scores_from_counts(counts[:, 0:2], counts[:, 2], counts[:, 3], kd)
+        note = trunk_note("Improved precision / recall (k_pr nearest neighbours) and density / coverage (k_dc)",
+                          "the published scores", "scores")
+        note += " All four figures depend on the number of images and are comparable at equal n only."
+        for name, asked, k in (("k_pr", k_pr, kp), ("k_dc", k_dc, kd)):
+            if k < int(asked):
+                note += (" %s lowered from %d to %d: there are only %d images per side." % (name, asked, k, n))
+                print("PRDC: %d images per side -- %s = %d instead of %d (the JSON records it)" % (n, name, k, asked))
+        out = c.write(dict(scores, k_pr=int(kp), k_dc=int(kd)), n, n, note)
+        print("PRDC (%d real, %d generated images; k = %d / %d): precision %.4f recall %.4f density %.4f coverage %.4f -> %s/prdc.json"
+              % (n, n, kp, kd, out["precision"], out["recall"], out["density"], out["coverage"], c.save_dir))
+        return c.result(out, return_codes)
+
+    def sample(self, split_dir, num_samples=25, draw_bbox=False):
+        """trainer.py:474-579 (what main.py:158 runs for B_VALIDATION): for the first `num_samples` batches of an
+        eval-mode loader take the FIRST sample of the sorted batch, generate nine 256x256 images for its caption /
+        boxes / labels from nine noise vectors with netG.eval(), and save one row [real | 9 fakes] (boxes drawn as white
+        lines when draw_bbox) as <NET_G minus .pth>_<split>/<caption>_<step>.png."""
+        from .datasets import prepare_data
+        from ..stackgan.logging_utils import save_image
+        if net_g_missing():
+            return None
+        netG, text_encoder = self._load_eval_models()
+        save_dir = eval_save_dir(split_dir, sep='_')
+        imsize, nrep = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1), 9
+        written, step = [], 0
+        for step, data in enumerate(self.data_loader, 0):
+            if step >= num_samples:
+                break
+            imgs, captions, cap_lens, class_ids, keys, (tm, tmi), label_one_hot, bbox = \
+                prepare_data(data, self.device, eval=True)
+            with torch.no_grad():
+                def row0(t):                                  # the first sample of the batch, nine times
+                    return t[0:1].repeat(nrep, *[1] * (t.dim() - 1)).contiguous()
+                words_embs, sent_emb, mask = (row0(t) for t in encode_text(text_encoder, captions, cap_lens))
+                noise = torch.randn(nrep, cfg.GAN.Z_DIM, device=self.device)
+                fake_imgs, _, _, _ = netG(noise, sent_emb, words_embs, mask, row0(tmi), row0(label_one_hot))
+            data_img = torch.zeros(1 + nrep, 3, imsize, imsize)
+            data_img[0] = imgs[-1][0].cpu()
+            data_img[1:] = fake_imgs[-1].float().cpu()
+            if draw_bbox:
+                draw_bbox_lines(data_img, np.asarray(bbox[0]), imsize)
+            sentence = caption_sentence(captions[0].cpu().numpy(), self.ixtoword)
+            fullpath = '{}/{}_{}.png'.format(save_dir, sentence, step)
+            save_image(data_img, fullpath, nrow=1 + nrep, normalize=True)
+            written.append(fullpath)
+        print("Saved {} files to {}".format(len(written), save_dir))
+        return written

@@ -192,6 +192,39 @@ def test_sample_rows_from_a_checkpoint_via_main(tmp_path):
         assert white[0].sum() >= 50 and all((white[0] & w).sum() >= 0.9 * white[0].sum() for w in white[1:])
 
 
+def test_sample_rows_directly(tmp_path):
+    """condGANTrainer.sample() on the tiny evaluation set-up (tests/eval_setup.py), without main.py: the files it returns, their
+    names and directory, one row of 1 + 9 images each, the boxes drawn on request only, and the same bytes under the same seed."""
+    from PIL import Image
+    from eval_setup import tiny_checkpoint, trainer
+    from mogan_amd.attngan.datasets import prepare_data
+    from mogan_amd.attngan.evaluate import caption_sentence
+    cfg, ev, ckpt = tiny_checkpoint(tmp_path)
+    try:
+        algo = trainer(tmp_path, length=8, eval=True)
+
+        def run(draw_bbox):
+            torch.manual_seed(5)
+            files = algo.sample("test", num_samples=2, draw_bbox=draw_bbox)
+            return files, [open(f, "rb").read() for f in files]
+        files, boxed = run(True)
+        assert len(files) == 2 and all(os.path.isfile(f) for f in files)
+        for step, (f, data) in enumerate(zip(files, algo.data_loader)):
+            captions = prepare_data(data, "cuda", eval=True)[1]
+            sentence = caption_sentence(captions[0].cpu().numpy(), algo.ixtoword)
+            assert sentence and os.path.basename(f) == "%s_%d.png" % (sentence, step)
+            assert os.path.dirname(f) == ckpt[:-4] + "_valid"
+            width, height = Image.open(f).size
+            pad = (height - 256) // 2                              # one row: 256 pixels and the grid's padding above and below
+            assert pad >= 0 and height == 256 + 2 * pad and width == 10 * (256 + pad) + pad
+        again, boxed_again = run(True)
+        assert again == files and boxed_again == boxed
+        plain_files, plain = run(False)
+        assert plain_files == files and all(a != b for a, b in zip(plain, boxed))
+    finally:
+        cfg.TRAIN.NET_G, cfg.TRAIN.FLAG = '', True
+
+
 def test_bench_two_ranks_control_flow():
     """`python bench.py --gpus 2 ... --full` as ONE plain command: bench.py re-executes itself under torch.distributed.run (2 ranks,
     the way the driver launches N>1 and what train.sh:25-29 hands to data_parallel in the reference) -- on this 1-GPU box

@@ -15,6 +15,7 @@ import torch
 
 import kid_cases as K
 import memguard as MG
+from eval_setup import tiny_checkpoint as _tiny_checkpoint, trainer as _trainer
 from helpers import load_pkg
 
 load_pkg()
@@ -155,36 +156,8 @@ def test_op_matches_the_entry_point_and_raises():
 
 
 # ------------------------------------------------------------------------------------------------- 3: end to end
-TINY = ("CONFIG_NAME: 'tiny'\nDATASET_NAME: 'coco'\nWORKERS: 0\nRNN_TYPE: 'LSTM'\nTREE: {BRANCH_NUM: 3, BASE_SIZE: 64}\n"
-        "GAN: {DF_DIM: 8, GF_DIM: 8, Z_DIM: 100, R_NUM: 1}\n"
-        "TEXT: {EMBEDDING_DIM: 32, CAPTIONS_PER_IMAGE: 5, WORDS_NUM: 6}\n")
 FIELDS = {"kid", "kid_std", "subsets", "subset_size", "n_real", "n_fake", "seed", "gamma", "coef0", "degree", "NET_G", "NET_E",
           "trunk_digest", "note"}
-
-
-def _tiny_checkpoint(tmp_path):
-    """the set-up of tests/test_fid_gpu.py's end-to-end tests: the evaluation yml of the existing evaluation tests' widths and a
-    checkpoint of a random-init generator at those widths"""
-    from mogan_amd.attngan import model
-    from mogan_amd.attngan.miscc.config import cfg, cfg_from_file
-    from mogan_amd.attngan.miscc.utils import weights_init
-    ckpt = str(tmp_path / "netG_tiny.pth")
-    ev = tmp_path / "eval.yml"
-    ev.write_text(TINY + "TRAIN: {FLAG: False, BATCH_SIZE: 4, NET_G: '%s', NET_E: ''}\n" % ckpt)
-    cfg_from_file(str(ev))
-    torch.manual_seed(21)
-    netG = model.G_NET()
-    netG.apply(weights_init)
-    torch.save({"netG": netG.state_dict()}, ckpt)
-    return cfg, ev, ckpt
-
-
-def _trainer(tmp_path):
-    from mogan_amd.attngan.datasets import SyntheticTextDataset
-    from mogan_amd.attngan.trainer import condGANTrainer
-    ds = SyntheticTextDataset(length=12, n_words=100, seed=7)
-    dl = torch.utils.data.DataLoader(ds, batch_size=4, drop_last=True, shuffle=False)
-    return condGANTrainer(str(tmp_path), dl, 100, ds.ixtoword, resume=False)
 
 
 def _check_json(out, ckpt, seed, subsets, s, lowered):

@@ -40,7 +40,7 @@ def test_sample_row_helpers():
     first absent box; the caption is the words up to the first 0 joined by blanks with non-ASCII characters dropped."""
     import numpy as np
     import torch
-    from mogan_amd.attngan.trainer import caption_sentence, draw_bbox_lines
+    from mogan_amd.attngan.evaluate import caption_sentence, draw_bbox_lines
     img = torch.zeros(3, 2, 256, 256)
     boxes = np.array([[0.25, 0.5, 0.125, 0.25], [0.0, 0.0, 1.2, 0.999], [-1, -1, -1, -1], [0.5, 0.5, 0.1, 0.1]], dtype=np.float32)
     draw_bbox_lines(img, boxes, 256)

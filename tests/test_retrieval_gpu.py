@@ -11,6 +11,7 @@ import torch
 
 import memguard as MG
 import retrieval_cases as K
+from eval_setup import tiny_checkpoint as _tiny_checkpoint, trainer as _trainer
 from helpers import load_pkg
 
 load_pkg()
@@ -246,35 +247,10 @@ def test_sentence_bank_against_the_stock_modules():
 
 
 # ------------------------------------------------------------------------------------------------- 6: end to end
-TINY = ("CONFIG_NAME: 'tiny'\nDATASET_NAME: 'coco'\nWORKERS: 0\nRNN_TYPE: 'LSTM'\nTREE: {BRANCH_NUM: 3, BASE_SIZE: 64}\n"
-        "GAN: {DF_DIM: 8, GF_DIM: 8, Z_DIM: 100, R_NUM: 1}\n"
-        "TEXT: {EMBEDDING_DIM: 32, CAPTIONS_PER_IMAGE: 5, WORDS_NUM: 6}\n")
-
-
-def _tiny_checkpoint(tmp_path):
-    """the evaluation yml of the existing evaluation tests' widths and a checkpoint of a random-init generator at those widths"""
-    from mogan_amd.attngan import model
-    from mogan_amd.attngan.miscc.config import cfg, cfg_from_file
-    from mogan_amd.attngan.miscc.utils import weights_init
-    ckpt = str(tmp_path / "netG_tiny.pth")
-    ev = tmp_path / "eval.yml"
-    ev.write_text(TINY + "TRAIN: {FLAG: False, BATCH_SIZE: 4, NET_G: '%s', NET_E: ''}\n" % ckpt)
-    cfg_from_file(str(ev))
-    torch.manual_seed(21)
-    netG = model.G_NET()
-    netG.apply(weights_init)
-    torch.save({"netG": netG.state_dict()}, ckpt)
-    return cfg, ev, ckpt
-
-
 def test_r_precision_end_to_end(tmp_path):
-    from mogan_amd.attngan.datasets import SyntheticTextDataset
-    from mogan_amd.attngan.trainer import condGANTrainer
     cfg, ev, ckpt = _tiny_checkpoint(tmp_path)
     try:
-        ds = SyntheticTextDataset(length=12, n_words=100, seed=7)
-        dl = torch.utils.data.DataLoader(ds, batch_size=4, drop_last=True, shuffle=False)
-        algo = condGANTrainer(str(tmp_path), dl, 100, ds.ixtoword, resume=False)
+        algo = _trainer(tmp_path)
         out, t = algo.r_precision("test", n_mismatched=5, seed=100, return_codes=True)
         path = os.path.join(ckpt[:-4], "valid", "r_precision.json")
         assert os.path.isfile(path) and json.load(open(path)) == out
@@ -325,17 +301,13 @@ def test_main_r_precision_on_synthetic(tmp_path):
 def test_r_precision_needs_the_encoder_pair(tmp_path):
     """TRAIN.NET_E names a text encoder whose image_encoder twin is missing: FileNotFoundError, as build_models raises"""
     from mogan_amd.attngan import model
-    from mogan_amd.attngan.datasets import SyntheticTextDataset
-    from mogan_amd.attngan.trainer import condGANTrainer
     cfg, ev, ckpt = _tiny_checkpoint(tmp_path)
     try:
         te = str(tmp_path / "text_encoder0.pth")
         torch.save(model.RNN_ENCODER(100, nhidden=32).state_dict(), te)
         cfg.TRAIN.NET_E = te
-        ds = SyntheticTextDataset(length=4, n_words=100)
-        dl = torch.utils.data.DataLoader(ds, batch_size=4, drop_last=True, shuffle=False)
         with pytest.raises(FileNotFoundError):
-            condGANTrainer(str(tmp_path), dl, 100, ds.ixtoword, resume=False).r_precision("test", n_mismatched=2)
+            _trainer(tmp_path, length=4, seed=0).r_precision("test", n_mismatched=2)
     finally:
         cfg.TRAIN.NET_G, cfg.TRAIN.NET_E, cfg.TRAIN.FLAG = '', '', True
 
