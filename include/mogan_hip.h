@@ -729,7 +729,7 @@ int mogan_retrieval_rank(const float* code, const float* pos, const float* bank,
 
 /* fp64 moments of a set of feature codes: what the Frechet distance is computed from (the reference has no code for it --
  * DESIGN.md section 9d; csrc/mogan_stats.hip).  x is fp32 (N, D), dense, widened exactly; mean (D) and cov (D, D) are fp64 -- with
- * the sums of mogan_poly3_mmd_f64 and the radii of mogan_knn_sqdist_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
+ * the sums of mogan_poly3_mmd_f64, the radii of mogan_knn_sqdist_f64 and the moments and sums of mogan_swd_* below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
  * workgroup to workgroup: every sum over n runs in one fixed order, so the same inputs give the same bits on every call.
  *   mean[j]   = (sum_n (double)x[n][j]) / N
  *   cov[i][j] = (sum_n (x[n][i] - mean[i]) (x[n][j] - mean[j])) / (N - 1)       (numpy.cov(x, rowvar=False))
@@ -790,6 +790,44 @@ int mogan_knn_sqdist_f64(const float* x, long long N, int D, int K, double* out,
 size_t mogan_ball_count_ws_bytes(long long M, long long N, int R);
 int mogan_ball_count_f64(const float* q, long long M, const float* p, long long N, int D, const double* r2, int R, int side,
                          int32_t* count, void* ws, size_t ws_bytes, hipStream_t stream);
+
+/* The sliced Wasserstein distance of Karras et al. 2018 between real and generated images (DESIGN.md section 9g;
+ * csrc/mogan_swd.hip; the reference has no code for it): Laplacian pyramid, 7 x 7 descriptors, their moments, their projections
+ * and the sum of |a - b| per direction; the sort in between is the caller's.  All images and descriptors are fp32 and dense.  No
+ * atomics, every sum runs in one fixed order: the same inputs give the same bits on every call.
+ *   w = (1, 4, 6, 4, 1) / 16; mirrored index m(i, n) = -i for i < 0, 2 n - 2 - i for i >= n (the edge sample is not repeated).
+ * mogan_pyr_down: x (NC, H, W) -> out (NC, H / 2, W / 2), out[oy][ox] = sum_{dy, dx = -2..2} w[dy] w[dx] x[m(2 oy + dy, H)][m(2 ox + dx, W)].
+ * mogan_lap_residual: out = x - pyr_up(down) in one launch, x and out (NC, H, W), down (NC, H / 2, W / 2); pyr_up is the same
+ *   filter times 4 over the zero-inserted image z (z[2 y][2 x] = down[y][x]) under the same mirror rule on z's indices -- a
+ *   mirrored index on an odd row or column contributes zero.  out may alias neither x nor down.
+ *   Both: H and W even and >= 4 (they need not be equal), NC >= 1, NC H W <= 2^31 - 1.
+ * mogan_swd_gather: level (N, C, H, W); centres (R, 3) int32 = (image, cy, cx) per descriptor; writes rows [row0, row0 + R) of
+ *   desc (rows_total, 49 C), a row = the 7 x 7 neighbourhood of (cy, cx) over all channels in (channel, y, x) order.  A copy.  The
+ *   caller keeps cy in [3, H - 3) and cx in [3, W - 3); what lies outside is clamped into the level (image to [0, N)).
+ *   1 <= C <= 4, H and W >= 7, N C H W <= 2^31 - 1, R >= 1, row0 >= 0, row0 + R <= rows_total <= 2^31 - 1.
+ * mogan_swd_moments_f64: desc (rows, 49 C) -> moments (C, 2) fp64 = (mean, population standard deviation) per channel over all rows
+ *   and the 49 positions of that channel; two passes (sum x; sum (x - mean)^2) over P = min(ceil(rows / 64), 2048) contiguous
+ *   shares of the rows, the shares added in share order.  A constant channel has a standard deviation of exactly 0.  The workspace
+ *   is required, 8-byte aligned: mogan_swd_moments_ws_bytes(rows, C) = 8 P C (0 for arguments the call rejects); MOGAN_ERR_WS where
+ *   ws is NULL, misaligned or shorter, nothing launched.
+ * mogan_swd_project: desc (rows, K = 49 C), moments (C, 2) fp64, dirs (K, D) -> out (D, rows):
+ *   out[d][r] = sum_k z[r][k] dirs[k][d], z = (float)(((double)desc[r][k] - mean_c) / std_c), the product on the matrix pipe
+ *   (csrc/mogan_mma.h), every 16 values of k into an fp32 accumulator of their own, the groups added in fp64 in index order and
+ *   rounded to fp32 once; a result's bits depend on its row and direction only.
+ *   1 <= D <= 1024.
+ * mogan_swd_absdiff_f64: a, b (D, rows) -> out (D) fp64, out[d] = sum_r |(double)a[d][r] - (double)b[d][r]|.  1 <= D <= 1024.
+ * MOGAN_ERR_SHAPE before any HIP call (and before the workspace is looked at): a NULL pointer (ws apart), any dimension outside the
+ * ranges above, rows < 1 or > 2^31 - 1, C outside 1..4. */
+int mogan_pyr_down(const float* x, long long NC, int H, int W, float* out, hipStream_t stream);
+int mogan_lap_residual(const float* x, const float* down, long long NC, int H, int W, float* out, hipStream_t stream);
+int mogan_swd_gather(const float* level, int N, int C, int H, int W, const int32_t* centres, long long R, float* desc,
+                     long long row0, long long rows_total, hipStream_t stream);
+size_t mogan_swd_moments_ws_bytes(long long rows, int C);
+int mogan_swd_moments_f64(const float* desc, long long rows, int C, double* moments, void* ws, size_t ws_bytes,
+                          hipStream_t stream);
+int mogan_swd_project(const float* desc, long long rows, int C, const double* moments, const float* dirs, int D, float* out,
+                      hipStream_t stream);
+int mogan_swd_absdiff_f64(const float* a, const float* b, long long rows, int D, double* out, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,10 @@
-"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9f).
+"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9g).
 
 `CheckpointEvaluation` is the base of `trainer.condGANTrainer` that holds every path which reads a finished checkpoint instead of
 training one: `sampling` / `sample` (images), `r_precision`, and `pool_codes` with the three scores `fid` / `kid` / `prdc` that share
-its pass.  It needs `self.device`, `self.data_loader`, `self.n_words` and `self.ixtoword` of the trainer and nothing of the train
-step.  What these paths have in common is written once here: the NET_G guard and the save-directory rule (`net_g_missing`,
-`eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
+its pass and `swd`, which takes the pass's images instead of their codes.  It needs `self.device`, `self.data_loader`,
+`self.n_words` and `self.ixtoword` of the trainer and nothing of the train step.  What these paths have in common is written
+once here: the NET_G guard and the save-directory rule (`net_g_missing`, `eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
 (`generate_seeded`), and what the three scores do around their own device calls (`PooledCodes`, `trunk_note`)."""
 import json
 import os
@@ -153,10 +153,10 @@ class CheckpointEvaluation(object):
             print('Load text encoder from:', cfg.TRAIN.NET_E)
         return netG, text_encoder.to(self.device).eval()
 
-    def _load_image_encoder(self):
-        """The image encoder that TRAIN.NET_E's text encoder was trained with: the `image_encoder` twin of its path, by
-        build_models' rule and with its error.  The heads are TEXT.EMBEDDING_DIM wide as in training (outside training the
-        reference's constructor fixes them at 256, model.py:213, which is the same thing for the published pairs only)."""
+    def _new_image_encoder(self):
+        """A random-init image encoder on the host, heads TEXT.EMBEDDING_DIM wide as in training (outside training the reference's
+        constructor fixes them at 256, model.py:213, which is the same thing for the published pairs only).  Its construction
+        draws from torch's global generator: the state it leaves behind is the one every seeded pass shuffles its loader under."""
         nef = cfg.TEXT.EMBEDDING_DIM
         image_encoder = CNN_ENCODER(nef, pretrained=False)
         if image_encoder.nef != nef:
@@ -164,6 +164,12 @@ class CheckpointEvaluation(object):
             image_encoder.emb_features = type(image_encoder.emb_features)(768, nef, kernel_size=1, stride=1, padding=0, bias=False)
             image_encoder.emb_cnn_code = type(image_encoder.emb_cnn_code)(2048, nef)
             image_encoder.init_trainable_weights()
+        return image_encoder
+
+    def _load_image_encoder(self):
+        """The image encoder that TRAIN.NET_E's text encoder was trained with: the `image_encoder` twin of its path, by
+        build_models' rule and with its error, frozen, on the device, in eval mode."""
+        image_encoder = self._new_image_encoder()
         if cfg.TRAIN.NET_E != '':
             img_path = cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder')
             for path in (cfg.TRAIN.NET_E, img_path):
@@ -175,12 +181,19 @@ class CheckpointEvaluation(object):
             p.requires_grad = False
         return image_encoder.to(self.device).eval()
 
-    def _load_seeded(self, seed):
+    def _load_seeded(self, seed, trunk=True):
         """The networks of the seeded paths under torch.manual_seed(seed) (which fixes the random-init encoders of an empty
-        NET_E) and the device generator the noise comes from: (netG, text_encoder, image_encoder, generator)"""
+        NET_E) and the device generator the noise comes from: (netG, text_encoder, image_encoder, generator).  trunk=False: no
+        image encoder (None) -- no checkpoint of it is read, nothing of it reaches the device or runs; its random initialisation
+        alone is still drawn on the host and dropped, because a shuffling loader takes its order from the global generator's state
+        after it: a pass without the trunk sees the batches, and so the generated images, of a pass with it."""
         torch.manual_seed(seed)
         netG, text_encoder = self._load_eval_models()
-        image_encoder = self._load_image_encoder()
+        if trunk:
+            image_encoder = self._load_image_encoder()
+        else:
+            image_encoder = None
+            self._new_image_encoder()
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
         return netG, text_encoder, image_encoder, gen
@@ -267,27 +280,33 @@ class CheckpointEvaluation(object):
                          "rank": rank, "bank": bank.bank.cpu()}
         return out
 
-    def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True):
-        """The one pass over the data loader that fid() and kid() share: the real 256x256 image and one generated 256x256 image per
+    def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True, image_sink=None, trunk=True):
+        """The one pass over the data loader that the scores share: the real 256x256 image and one generated 256x256 image per
         caption (EMA generator, eval mode, noise from the seeded device generator exactly as r_precision draws it) go through
         CNN_ENCODER.pool_code; the codes stay on the device in two preallocated (num_samples, 2048) fp32 buffers.  `want_real`
         False leaves the real images out of the trunk; it may also be a callable (trunk digest, code width) -> bool, asked once the
         image encoder is loaded and before the pass (fid() decides there whether a statistics file replaces the real side).
         `split_dir` names the split the data loader was built for; the pass itself reads the loader only.
         Returns a dict: "real" (None where not wanted) and "fake", the device buffers, of which the first "n" rows are filled;
-        "trunk_digest"; the "seed" the pass ran under.  None, with fid()'s message, where TRAIN.NET_G is empty."""
+        "trunk_digest"; the "seed" the pass ran under.  None, with fid()'s message, where TRAIN.NET_G is empty.
+        `image_sink`, where given, is called once per batch with (real, fake, take): the real and the generated 256x256 images of
+        the batch on the device and the number of leading images that count (swd() gathers its descriptors there).  trunk=False
+        leaves the image encoder out altogether -- not loaded, not run; "real", "fake" and "trunk_digest" are then None -- and the
+        images, their order and "n" are those of a pass with it."""
         from .datasets import prepare_data
         from .fid import trunk_digest
         if net_g_missing():
             return None
-        netG, text_encoder, image_encoder, gen = self._load_seeded(seed)
-        D = int(image_encoder.emb_cnn_code.weight.shape[1])                 # 2048: the pooled code's width
-        digest = trunk_digest(image_encoder)
-        if callable(want_real):
-            want_real = want_real(digest, D)
+        netG, text_encoder, image_encoder, gen = self._load_seeded(seed, trunk)
         rows = max(1, min(int(num_samples), len(self.data_loader.dataset)))
-        fake_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device)
-        real_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device) if want_real else None
+        digest = fake_codes = real_codes = None
+        if trunk:
+            D = int(image_encoder.emb_cnn_code.weight.shape[1])             # 2048: the pooled code's width
+            digest = trunk_digest(image_encoder)
+            if callable(want_real):
+                want_real = want_real(digest, D)
+            fake_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device)
+            real_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device) if want_real else None
         n = 0
         for data in self.data_loader:
             if n >= rows:
@@ -297,9 +316,12 @@ class CheckpointEvaluation(object):
             with torch.no_grad():
                 words_embs, sent_emb, mask = encode_text(text_encoder, captions, cap_lens)
                 fake = generate_seeded(netG, gen, words_embs, sent_emb, mask, tmi, label_one_hot)
-                fake_codes[n:n + take] = image_encoder.pool_code(fake)[:take]
-                if real_codes is not None:
-                    real_codes[n:n + take] = image_encoder.pool_code(imgs[-1])[:take]
+                if trunk:
+                    fake_codes[n:n + take] = image_encoder.pool_code(fake)[:take]
+                    if real_codes is not None:
+                        real_codes[n:n + take] = image_encoder.pool_code(imgs[-1])[:take]
+                if image_sink is not None:
+                    image_sink(imgs[-1], fake, take)
             n += take
         return {"real": real_codes, "fake": fake_codes, "n": n, "trunk_digest": digest, "seed": int(seed)}
 
@@ -416,6 +438,58 @@ class CheckpointEvaluation(object):
         print("PRDC (%d real, %d generated images; k = %d / %d): precision %.4f recall %.4f density %.4f coverage %.4f -> %s/prdc.json"
               % (n, n, kp, kd, out["precision"], out["recall"], out["density"], out["coverage"], c.save_dir))
         return c.result(out, return_codes)
+
+    def swd_images(self, num_samples=30000, seed=100, patches=128, dirs=128, repeats=4, min_res=16):
+        """The accumulator swd() fills: attngan/swd.SlicedWasserstein for the tree's final resolution and as many images as the
+        pass will see, with `sink`, the (real, fake, take) callable pool_codes' image_sink wants.  A caller that shares one pass
+        between swd() and the trunk's scores makes it first and hands it to both (main.py)."""
+        from .swd import SlicedWasserstein
+        size = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1)
+        images = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        acc = SlicedWasserstein(size, 3, images * int(patches), patches, dirs, repeats, min_res, seed, self.device)
+        print("SWD: %.2f GB of descriptors on the device (%d levels x 2 sides x %d rows x %d values, fp32)"
+              % (acc.bytes / 1e9, len(acc.sizes), acc.rows, acc.desc["real"][0].shape[1]))
+
+        def sink(real, fake, take):
+            acc.add(real[:take].float().contiguous(), fake[:take].float().contiguous())
+        acc.sink = sink
+        return acc
+
+    def swd(self, split_dir, num_samples=30000, seed=100, patches=128, dirs=128, repeats=4, min_res=16, images=None):
+        """Sliced Wasserstein distance (Karras et al. 2018; attngan/swd.py has the definition and the draw
+        order) between the real 256x256 images and one generated image per caption of the checkpoint TRAIN.NET_G -- exactly the
+        images pool_codes and r_precision see under `seed` -- at every level of a Laplacian pyramid from 256 down to `min_res`.
+        The score reads the images themselves: it needs no image encoder, and pool_codes runs without one (trunk=False) unless
+        the caller shares a pass: `images` is then the accumulator of swd_images() whose sink that pass has fed.  Pyramid,
+        descriptors, moments, projections and the reduction run in hip/ops; the sort is torch.sort.  Writes
+        <NET_G minus .pth>/<split>/swd.json and returns its content."""
+        if net_g_missing():
+            return None
+        if images is None:
+            images = self.swd_images(num_samples, seed, patches, dirs, repeats, min_res)
+            self.pool_codes(split_dir, num_samples, seed, want_real=False, image_sink=images.sink, trunk=False)
+        elif ((images.seed, images.patches, images.dirs, images.repeats, images.sizes[-1])
+              != (int(seed), int(patches), int(dirs), int(repeats), int(min_res))):
+            raise ValueError("swd: the images handed over were gathered under other parameters (seed, patches, dirs, repeats, "
+                             "min_res) = %s" % ((images.seed, images.patches, images.dirs, images.repeats, images.sizes[-1]),))
+        if images.n < 1:
+            raise ValueError("swd: the data loader gave no batch")
+        res = images.result()
+        n = images.n // images.patches
+        out = {"swd": res["swd"], "levels": res["levels"], "per_level": res["per_level"], "patches": images.patches,
+               "dirs": images.dirs, "repeats": images.repeats, "n_real": n, "n_fake": n, "seed": int(seed),
+               "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E,
+               "note": "Sliced Wasserstein distance x 1000 between Laplacian-pyramid descriptors (7x7 neighbourhoods) of the real "
+                       "and the generated images, per level and averaged: trunk-free -- no image encoder is involved, the figure "
+                       "does not depend on any encoder weights.  It depends on the number of descriptors per image (patches = "
+                       "%d), on dirs, repeats and the seed, and is comparable under equal settings only.  The images enter as "
+                       "fp32 in [-1, 1], not quantised to 8 bits as in Karras et al.'s code." % images.patches}
+        save_dir = eval_save_dir(split_dir)
+        write_json(save_dir, "swd", out)
+        print("SWD (%d real, %d generated images; %d patches, %d directions, %d repeats): %.4f = mean of %s at levels %s -> %s/swd.json"
+              % (n, n, images.patches, images.dirs, images.repeats, out["swd"], ["%.4f" % v for v in out["per_level"]],
+                 out["levels"], save_dir))
+        return out
 
     def sample(self, split_dir, num_samples=25, draw_bbox=False):
         """trainer.py:474-579 (what main.py:158 runs for B_VALIDATION): for the first `num_samples` batches of an

@@ -71,7 +71,19 @@ def parse_args(argv=None):
                              'any of --fid --kid --prdc together take one pass; not together with --sampling or --r_precision')
     parser.add_argument('--prdc_k_pr', type=int, default=3, metavar='K', help='with --prdc: neighbours of precision / recall (1..8)')
     parser.add_argument('--prdc_k_dc', type=int, default=5, metavar='K', help='with --prdc: neighbours of density / coverage (1..8)')
+    parser.add_argument('--swd', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): sliced Wasserstein distance between Laplacian-pyramid descriptors of the '
+                             'real and the generated images themselves (condGANTrainer.swd: no image encoder involved, one figure per '
+                             'pyramid level) -> <NET_G minus .pth>/<split>/swd.json; with any of --fid --kid --prdc all take one pass; '
+                             'not together with --sampling or --r_precision')
+    parser.add_argument('--swd_patches', type=int, default=128, metavar='N', help='with --swd: 7x7 descriptors per image and level')
+    parser.add_argument('--swd_dirs', type=int, default=128, metavar='N', help='with --swd: random directions per repeat (1..1024)')
+    parser.add_argument('--swd_repeats', type=int, default=4, metavar='N', help='with --swd: repeats of the random projection')
+    parser.add_argument('--swd_min_res', type=int, default=16, metavar='S',
+                        help='with --swd: the coarsest pyramid level (256 / S must be a power of two)')
     args = parser.parse_args(argv)
+    if args.swd and (args.sampling or args.r_precision):
+        parser.error('--swd cannot be combined with --sampling or --r_precision')
     if args.fid and (args.sampling or args.r_precision):
         parser.error('--fid cannot be combined with --sampling or --r_precision')
     if args.kid and (args.sampling or args.r_precision):
@@ -129,7 +141,7 @@ def main(argv=None):
         output_dir = args.resume
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
-    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc or args.swd)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -152,9 +164,15 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
-    elif args.fid + args.kid + args.prdc > 1:
-        codes = algo.pool_codes(split_dir, seed=args.manualSeed)                    # one pass over the loader and the trunk for all
+    elif args.fid + args.kid + args.prdc + args.swd > 1:
+        swd_kw = dict(seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
+                      min_res=args.swd_min_res)
+        images = algo.swd_images(**swd_kw) if args.swd and cfg.TRAIN.NET_G != '' else None
+        # one pass over the loader and the trunk for all; --swd takes the pass's images where the others take their codes
+        codes = algo.pool_codes(split_dir, seed=args.manualSeed, image_sink=None if images is None else images.sink)
         if codes is not None:
+            if images is not None:
+                algo.swd(split_dir, images=images, **swd_kw)
             if args.fid:
                 algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats, codes=codes)
             if args.kid:
@@ -167,6 +185,9 @@ def main(argv=None):
         algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size)
     elif args.prdc:
         algo.prdc(split_dir, seed=args.manualSeed, k_pr=args.prdc_k_pr, k_dc=args.prdc_k_dc)
+    elif args.swd:
+        algo.swd(split_dir, seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
+                 min_res=args.swd_min_res)
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:

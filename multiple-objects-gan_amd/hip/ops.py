@@ -1899,6 +1899,150 @@ def ball_counts(q, p, r2, side="support"):
     return count
 
 
+def _dense_f32(who, name, t, ndim):
+    """the contract of the sliced-Wasserstein ops for an fp32 tensor: dtype, rank, contiguity (nothing is converted)"""
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise ValueError("%s: fp32 expected, %s is %s" % (who, name, getattr(t, "dtype", type(t))))
+    if t.dim() != ndim or min(t.shape) < 1:
+        raise ValueError("%s: %s must have %d non-empty dimensions, got %s" % (who, name, ndim, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: contiguous tensors expected (%s has strides %s)" % (who, name, tuple(t.stride())))
+    return t.detach()
+
+
+def _plane(who, x):
+    x = _dense_f32(who, "x", x, 3)
+    NC, H, W = x.shape
+    if H < 4 or W < 4 or H % 2 or W % 2 or x.numel() > 2 ** 31 - 1:
+        raise ValueError("%s: x (N C, H, W) with even H, W >= 4 and fewer than 2^31 elements expected, got %s" % (who, tuple(x.shape)))
+    return x, NC, H, W
+
+
+def pyr_down(x):
+    """One step down the Gaussian pyramid of DESIGN.md section 9g (mogan_pyr_down): fp32 x (N C, H, W) -> (N C, H / 2, W / 2) under
+    the 5 x 5 filter (1, 4, 6, 4, 1)^2 / 256 with mirrored indices (the edge sample not repeated).  H and W even and >= 4.  No
+    gradient.  Nothing is converted or copied for the caller: a wrong dtype, rank, contiguity or size is a ValueError."""
+    x, NC, H, W = _plane("pyr_down", x)
+    px = ptr(x)
+    out = torch.empty((NC, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    call("mogan_pyr_down", px, NC, H, W, ptr(out), stream_ptr())
+    return out
+
+
+def lap_residual(x, down):
+    """One level of the Laplacian pyramid in one launch (mogan_lap_residual): x - pyr_up(down) for fp32 x (N C, H, W) and
+    down (N C, H / 2, W / 2); pyr_up is pyr_down's filter times 4 over the zero-inserted image, which is never formed.  No gradient.
+    Nothing is converted or copied for the caller: a wrong dtype, rank, contiguity, device or size is a ValueError."""
+    x, NC, H, W = _plane("lap_residual", x)
+    down = _dense_f32("lap_residual", "down", down, 3)
+    if tuple(down.shape) != (NC, H // 2, W // 2):
+        raise ValueError("lap_residual: down must be %s for x %s, got %s" % ((NC, H // 2, W // 2), tuple(x.shape), tuple(down.shape)))
+    if down.device != x.device:
+        raise ValueError("lap_residual: x and down must be on one device (%s, %s)" % (x.device, down.device))
+    px, pd = ptr(x), ptr(down)
+    out = torch.empty_like(x)
+    call("mogan_lap_residual", px, pd, NC, H, W, ptr(out), stream_ptr())
+    return out
+
+
+def swd_gather(level, centres, desc, row0):
+    """Writes rows [row0, row0 + R) of the descriptor buffer desc (rows_total, 49 C) fp32: row r = the 7 x 7 neighbourhood of
+    (cy, cx) in image `image` of the fp32 level (N, C, H, W), all channels, in (channel, y, x) order (mogan_swd_gather; a copy).
+    centres (R, 3) = (image, cy, cx) per row: a host array (numpy integers), checked here -- image in [0, N), cy in [3, H - 3),
+    cx in [3, W - 3), else a ValueError -- and uploaded; or an int32 device tensor, which the kernel clamps into the level.  C in 1..4,
+    H and W >= 7.  Returns desc.  No gradient; nothing is converted or copied for the caller."""
+    import numpy as np
+    level = _dense_f32("swd_gather", "level", level, 4)
+    given, desc = desc, _dense_f32("swd_gather", "desc", desc, 2)
+    N, C, H, W = level.shape
+    if C > 4 or H < 7 or W < 7 or level.numel() > 2 ** 31 - 1:
+        raise ValueError("swd_gather: level (N, 1..4, >= 7, >= 7) with fewer than 2^31 elements expected, got %s" % (tuple(level.shape),))
+    if desc.shape[1] != 49 * C or desc.shape[0] > 2 ** 31 - 1:
+        raise ValueError("swd_gather: desc must be (rows, %d) for %d channels, got %s" % (49 * C, C, tuple(desc.shape)))
+    if desc.device != level.device:
+        raise ValueError("swd_gather: level and desc must be on one device (%s, %s)" % (level.device, desc.device))
+    if isinstance(centres, np.ndarray):
+        if centres.ndim != 2 or centres.shape[1] != 3 or centres.shape[0] < 1 or not np.issubdtype(centres.dtype, np.integer):
+            raise ValueError("swd_gather: centres must be an integer (R, 3) table, got %s %s" % (centres.dtype, centres.shape))
+        lo, hi = centres.min(axis=0), centres.max(axis=0)
+        if lo[0] < 0 or hi[0] >= N or lo[1] < 3 or hi[1] >= H - 3 or lo[2] < 3 or hi[2] >= W - 3:
+            raise ValueError("swd_gather: centres outside image [0, %d), cy [3, %d), cx [3, %d): min %s, max %s"
+                             % (N, H - 3, W - 3, lo.tolist(), hi.tolist()))
+    host = centres if isinstance(centres, np.ndarray) else None
+    if host is None and (not torch.is_tensor(centres) or centres.dtype != torch.int32 or centres.dim() != 2 or centres.shape[1] != 3
+                         or centres.shape[0] < 1 or not centres.is_contiguous()):
+        raise ValueError("swd_gather: centres must be contiguous int32 (R, 3), got %s %s"
+                         % (getattr(centres, "dtype", type(centres)), tuple(getattr(centres, "shape", ()))))
+    if host is None and centres.device != level.device:
+        raise ValueError("swd_gather: centres must be on the level's device (%s, %s)" % (centres.device, level.device))
+    R, row0 = int(centres.shape[0]), int(row0)
+    if row0 < 0 or row0 + R > desc.shape[0]:
+        raise ValueError("swd_gather: rows [%d, %d) do not fit a buffer of %d rows" % (row0, row0 + R, desc.shape[0]))
+    if host is not None:
+        ptr(level)                                           # (a host tensor raises here, before anything is uploaded)
+        centres = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(level.device)
+    call("mogan_swd_gather", ptr(level), N, C, H, W, ptr(centres), R, ptr(desc), row0, desc.shape[0], stream_ptr())
+    return given
+
+
+def _descriptors(who, desc):
+    desc = _dense_f32(who, "desc", desc, 2)
+    rows, K = desc.shape
+    if K % 49 or K // 49 > 4 or rows > 2 ** 31 - 1:
+        raise ValueError("%s: descriptors (rows, 49 C) with C in 1..4 expected, got %s" % (who, tuple(desc.shape)))
+    return desc, rows, K // 49
+
+
+def swd_moments(desc):
+    """(C, 2) fp64 on the device: mean and population standard deviation per channel of fp32 descriptors (rows, 49 C), over all rows
+    and the 49 positions of the channel (mogan_swd_moments_f64: two passes, fp64 sums in a fixed order).  A constant channel has a
+    standard deviation of exactly 0.  No gradient; nothing is converted or copied for the caller."""
+    desc, rows, C = _descriptors("swd_moments", desc)
+    pd = ptr(desc)
+    ws, ws_bytes, own = _scratch(desc.device, int(lib.load().mogan_swd_moments_ws_bytes(rows, C)))
+    mom = torch.empty((C, 2), dtype=torch.float64, device=desc.device)
+    call("mogan_swd_moments_f64", pd, rows, C, ptr(mom), ws, ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(desc.device))
+    return mom
+
+
+def swd_project(desc, moments, dirs):
+    """Projections (D, rows) fp32 of the standardised descriptors onto the directions: desc (rows, K = 49 C) fp32, moments (C, 2)
+    fp64 (swd_moments), dirs (K, D) fp32, 1 <= D <= 1024 (mogan_swd_project: every value standardised in fp64 and rounded once, the
+    product on the matrix pipe; a projection's bits depend on its row and direction only).  A direction's projections are
+    contiguous.  No gradient; nothing is converted or copied for the caller."""
+    desc, rows, C = _descriptors("swd_project", desc)
+    dirs = _dense_f32("swd_project", "dirs", dirs, 2)
+    if not torch.is_tensor(moments) or moments.dtype != torch.float64 or tuple(moments.shape) != (C, 2) or not moments.is_contiguous():
+        raise ValueError("swd_project: contiguous fp64 moments (%d, 2) expected, got %s %s"
+                         % (C, getattr(moments, "dtype", type(moments)), tuple(getattr(moments, "shape", ()))))
+    if dirs.shape[0] != 49 * C or dirs.shape[1] > 1024:
+        raise ValueError("swd_project: dirs (%d, 1..1024) expected, got %s" % (49 * C, tuple(dirs.shape)))
+    if not (moments.device == dirs.device == desc.device):
+        raise ValueError("swd_project: desc, moments and dirs must be on one device")
+    D = int(dirs.shape[1])
+    pd, pm, pv = ptr(desc), ptr(moments.detach()), ptr(dirs)
+    out = torch.empty((D, rows), dtype=torch.float32, device=desc.device)
+    call("mogan_swd_project", pd, rows, C, pm, pv, D, ptr(out), stream_ptr())
+    return out
+
+
+def swd_absdiff(a, b):
+    """(D,) fp64 on the device: sum over r of |a[d, r] - b[d, r]| for two fp32 (D, rows) matrices, D <= 1024, in fp64 and a fixed
+    order (mogan_swd_absdiff_f64).  No gradient; nothing is converted or copied for the caller."""
+    a = _dense_f32("swd_absdiff", "a", a, 2)
+    b = _dense_f32("swd_absdiff", "b", b, 2)
+    if a.shape != b.shape or a.shape[0] > 1024 or a.shape[1] > 2 ** 31 - 1:
+        raise ValueError("swd_absdiff: two (D <= 1024, rows) matrices of one shape expected, got %s, %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.device != b.device:
+        raise ValueError("swd_absdiff: a and b must be on one device (%s, %s)" % (a.device, b.device))
+    pa, pb = ptr(a), ptr(b)
+    out = torch.empty((a.shape[0],), dtype=torch.float64, device=a.device)
+    call("mogan_swd_absdiff_f64", pa, pb, a.shape[1], a.shape[0], ptr(out), stream_ptr())
+    return out
+
+
 class ScalarSumFn(torch.autograd.Function):
     """sum_k w_k * x_k over up to 8 zero-dim device scalars in ONE launch (forward) / one launch (backward): the loss sums
     of miscc/losses.py:169-174,203,221 and trainer.py:330 otherwise cost a chain of 0-dim aten kernels each way."""
