@@ -729,7 +729,7 @@ int mogan_retrieval_rank(const float* code, const float* pos, const float* bank,
 
 /* fp64 moments of a set of feature codes: what the Frechet distance is computed from (the reference has no code for it --
  * DESIGN.md section 9d; csrc/mogan_stats.hip).  x is fp32 (N, D), dense, widened exactly; mean (D) and cov (D, D) are fp64 -- with
- * the sums of mogan_poly3_mmd_f64, the radii of mogan_knn_sqdist_f64 and the moments and sums of mogan_swd_* below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
+ * the sums of mogan_poly3_mmd_f64, the radii of mogan_knn_sqdist_f64 , the moments and sums of mogan_swd_* and the terms of mogan_ssim_level_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
  * workgroup to workgroup: every sum over n runs in one fixed order, so the same inputs give the same bits on every call.
  *   mean[j]   = (sum_n (double)x[n][j]) / N
  *   cov[i][j] = (sum_n (x[n][i] - mean[i]) (x[n][j] - mean[j])) / (N - 1)       (numpy.cov(x, rowvar=False))
@@ -828,6 +828,37 @@ int mogan_swd_moments_f64(const float* desc, long long rows, int C, double* mome
 int mogan_swd_project(const float* desc, long long rows, int C, const double* moments, const float* dirs, int D, float* out,
                       hipStream_t stream);
 int mogan_swd_absdiff_f64(const float* a, const float* b, long long rows, int D, double* out, hipStream_t stream);
+
+/* One level of the multi-scale structural similarity of pairs of images (Wang et al. 2003, as Odena et al. 2017 use it for GAN
+ * diversity; csrc/mogan_ssim.hip; attngan/msssim.py has the whole definition; the reference has no code for
+ * it).  All images are fp32 and dense.  No atomics, every sum runs in one fixed order: the same inputs give the same bits on every
+ * call.
+ * mogan_avg_down2: x (NC, H, W) -> out (NC, H / 2, W / 2), the aligned 2 x 2 mean
+ *   out[y][x] = ((x[2y][2x] + x[2y][2x + 1]) + (x[2y + 1][2x] + x[2y + 1][2x + 1])) * 0.25f.
+ *   H and W even and >= 2 (they need not be equal), NC >= 1, NC H W <= 2^31 - 1.
+ * mogan_ssim_level_f64: a, b (P, C, S, S) = P pairs; win (n) the separable window, fp32, on the device; M = S - n + 1 valid
+ *   positions per axis.  Per channel, in fp32 without contraction, on the centred values d = 127.5f x, with G* the window applied
+ *   along x first and then along y, both sums from zero in index order:
+ *     m_a = G*d_a, m_b = G*d_b, s_aa = G*(d_a d_a) - m_a m_a, s_bb = G*(d_b d_b) - m_b m_b, s_ab = G*(d_a d_b) - m_a m_b,
+ *     mu_a = 127.5f + m_a, mu_b = 127.5f + m_b, C1 = 6.5025f, C2 = 58.5225f,
+ *     cs   = (2 s_ab + C2) / ((s_aa + s_bb) + C2)
+ *     l    = (2 (mu_a mu_b) + C1) / ((mu_a mu_a + mu_b mu_b) + C1)
+ *     ssim = l cs                                  (IEEE division)
+ *   so a pair of bit-identical images gives ssim = cs = 1.0f at every position, and exchanging a and b leaves every bit as it is.
+ *   terms (P, 2) fp64 = (mean ssim, mean cs) over the C M M values of a pair: a workgroup owns a 32 x 32 tile of positions of one
+ *   channel of one pair, stages the tile and its n - 1 halo of both images in LDS, filters along x into LDS and along y in
+ *   registers (the five filtered planes never reach memory), adds its values in fp64 in a fixed tree and leaves two doubles in the
+ *   workspace; a second launch of the same call adds a pair's C T T partials (T = ceil(M / 32)) in index order and divides by
+ *   C M M.  ssim_map and cs_map, (P, C, M, M) fp32, are written where they are not NULL.  The workspace is required, 8-byte
+ *   aligned: mogan_ssim_level_ws_bytes(P, C, S, n) = 16 P C T T (0 for arguments the call rejects); MOGAN_ERR_WS where ws is NULL,
+ *   misaligned or shorter, nothing launched.
+ *   P >= 1, 1 <= C <= 4, S >= 2, 1 <= n <= min(11, S), P C S S <= 2^31 - 1.
+ * MOGAN_ERR_SHAPE before any HIP call (and before the workspace is looked at): a NULL pointer (the maps and ws apart), any
+ * dimension outside the ranges above. */
+int mogan_avg_down2(const float* x, long long NC, int H, int W, float* out, hipStream_t stream);
+size_t mogan_ssim_level_ws_bytes(long long P, int C, int S, int n);
+int mogan_ssim_level_f64(const float* a, const float* b, long long P, int C, int S, const float* win, int n, double* terms,
+                         float* ssim_map, float* cs_map, void* ws, size_t ws_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,13 +1,14 @@
-"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9g).
+"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9h).
 
 `CheckpointEvaluation` is the base of `trainer.condGANTrainer` that holds every path which reads a finished checkpoint instead of
 training one: `sampling` / `sample` (images), `r_precision`, and `pool_codes` with the three scores `fid` / `kid` / `prdc` that share
-its pass and `swd`, which takes the pass's images instead of their codes.  It needs `self.device`, `self.data_loader`,
+its pass and `swd` and `msssim`, which take the pass's images instead of their codes.  It needs `self.device`, `self.data_loader`,
 `self.n_words` and `self.ixtoword` of the trainer and nothing of the train step.  What these paths have in common is written
 once here: the NET_G guard and the save-directory rule (`net_g_missing`, `eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
 (`generate_seeded`), and what the three scores do around their own device calls (`PooledCodes`, `trunk_note`)."""
 import json
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -280,7 +281,7 @@ class CheckpointEvaluation(object):
                          "rank": rank, "bank": bank.bank.cpu()}
         return out
 
-    def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True, image_sink=None, trunk=True):
+    def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True, image_sink=None, trunk=True, resample_sink=None):
         """The one pass over the data loader that the scores share: the real 256x256 image and one generated 256x256 image per
         caption (EMA generator, eval mode, noise from the seeded device generator exactly as r_precision draws it) go through
         CNN_ENCODER.pool_code; the codes stay on the device in two preallocated (num_samples, 2048) fp32 buffers.  `want_real`
@@ -292,7 +293,11 @@ class CheckpointEvaluation(object):
         `image_sink`, where given, is called once per batch with (real, fake, take): the real and the generated 256x256 images of
         the batch on the device and the number of leading images that count (swd() gathers its descriptors there).  trunk=False
         leaves the image encoder out altogether -- not loaded, not run; "real", "fake" and "trunk_digest" are then None -- and the
-        images, their order and "n" are those of a pass with it."""
+        images, their order and "n" are those of a pass with it.
+        `resample_sink`, where given, makes the pass generate a SECOND image per caption right after the batch's first one -- the
+        same text, boxes and labels, noise and then eps (generate_seeded's order) from a device generator of its own seeded
+        `seed` + 1 -- and is called with (fake, fake_again, take) (msssim() scores how much the noise changes there).  The first
+        generator's draws, and so the images every other score sees, are those of a pass without it."""
         from .datasets import prepare_data
         from .fid import trunk_digest
         if net_g_missing():
@@ -307,6 +312,10 @@ class CheckpointEvaluation(object):
                 want_real = want_real(digest, D)
             fake_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device)
             real_codes = torch.empty((rows, D), dtype=torch.float32, device=self.device) if want_real else None
+        gen_again = None
+        if resample_sink is not None:
+            gen_again = torch.Generator(device=self.device)
+            gen_again.manual_seed(int(seed) + 1)
         n = 0
         for data in self.data_loader:
             if n >= rows:
@@ -316,6 +325,8 @@ class CheckpointEvaluation(object):
             with torch.no_grad():
                 words_embs, sent_emb, mask = encode_text(text_encoder, captions, cap_lens)
                 fake = generate_seeded(netG, gen, words_embs, sent_emb, mask, tmi, label_one_hot)
+                if resample_sink is not None:
+                    resample_sink(fake, generate_seeded(netG, gen_again, words_embs, sent_emb, mask, tmi, label_one_hot), take)
                 if trunk:
                     fake_codes[n:n + take] = image_encoder.pool_code(fake)[:take]
                     if real_codes is not None:
@@ -489,6 +500,76 @@ class CheckpointEvaluation(object):
         print("SWD (%d real, %d generated images; %d patches, %d directions, %d repeats): %.4f = mean of %s at levels %s -> %s/swd.json"
               % (n, n, images.patches, images.dirs, images.repeats, out["swd"], ["%.4f" % v for v in out["per_level"]],
                  out["levels"], save_dir))
+        return out
+
+    def msssim_images(self, num_samples=30000, seed=100, scales=5, same_caption=True):
+        """The accumulator msssim() fills: one attngan/msssim.PairSimilarity per figure ("real", "generated" and, with
+        `same_caption`, "same_caption") for the tree's final resolution and as many pairs as the pass can give, with `sink`, the
+        (real, fake, take) callable of pool_codes' image_sink, and `resample_sink`, the (fake, fake_again, take) callable of its
+        resample_sink (None without `same_caption`).  Within a batch, of the `take` leading images, row j is paired with row
+        j + take // 2 for j < take // 2.  A caller that shares one pass between msssim() and other scores makes it first and
+        hands it to both (main.py)."""
+        from .msssim import PairSimilarity
+        size = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1)
+        images = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        acc = SimpleNamespace(seed=int(seed), scales=int(scales), same_caption=bool(same_caption))
+        acc.figures = {name: PairSimilarity(size, 3, max(1, images // 2), scales, self.device) for name in ("real", "generated")}
+        if same_caption:
+            acc.figures["same_caption"] = PairSimilarity(size, 3, images, scales, self.device)
+
+        def sink(real, fake, take):
+            half = take // 2
+            if half:
+                for name, t in (("real", real), ("generated", fake)):
+                    t = t[:2 * half].float()
+                    acc.figures[name].add(t[:half].contiguous(), t[half:].contiguous())
+
+        def resample_sink(fake, fake_again, take):
+            acc.figures["same_caption"].add(fake[:take].float().contiguous(), fake_again[:take].float().contiguous())
+        acc.sink, acc.resample_sink = sink, resample_sink if same_caption else None
+        return acc
+
+    def msssim(self, split_dir, num_samples=30000, seed=100, scales=5, same_caption=True, images=None):
+        """Multi-scale structural similarity between PAIRS of images (Wang et al. 2003 as Odena et al. 2017 use it; DESIGN.md section
+        9h; attngan/msssim.py has the definition), the trunk-free score for variation: "real", pairs of real 256x256 images -- the
+        data's own figure, the floor a generator should reach; "generated", the same pairs of the images pool_codes and
+        r_precision see under `seed` -- higher than "real" means less varied than the data; and, with `same_caption`,
+        "same_caption": every caption's image against a second image for the same text, boxes and labels under fresh z and
+        conditioning noise (pool_codes' resample_sink) -- a value near 1 means the generator ignores its noise, which no score
+        that draws one image per caption can see.  No image encoder is involved, and pool_codes runs without one (trunk=False)
+        unless the caller shares a pass: `images` is then the accumulator of msssim_images() whose sinks that pass has fed.
+        Every level's filtering and sums run in hip/ops.ssim_level; the terms are read back once per figure.  Writes
+        <NET_G minus .pth>/<split>/msssim.json and returns its content."""
+        if net_g_missing():
+            return None
+        if images is None:
+            images = self.msssim_images(num_samples, seed, scales, same_caption)
+            self.pool_codes(split_dir, num_samples, seed, want_real=False, image_sink=images.sink, trunk=False,
+                            resample_sink=images.resample_sink)
+        elif (images.seed, images.scales, images.same_caption) != (int(seed), int(scales), bool(same_caption)):
+            raise ValueError("msssim: the images handed over were scored under other parameters (seed, scales, same_caption) = %s"
+                             % ((images.seed, images.scales, images.same_caption),))
+        if any(f.n < 1 for f in images.figures.values()):
+            raise ValueError("msssim: the data loader gave no pair of images")
+        out = {}
+        for name, f in images.figures.items():
+            res = f.result()
+            out[name] = {"mean": res["mean"], "std": res["std"], "ssim": res["ssim"], "cs": res["cs"], "pairs": res["pairs"],
+                         "clamped": res["clamped"]}
+        out.update({"levels": list(images.figures["real"].sizes), "scales": images.scales, "seed": int(seed),
+                    "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E,
+                    "note": "Multi-scale structural similarity between pairs of images, mean and population standard deviation over "
+                            "the pairs, with the per-level means of ssim and cs: trunk-free -- no image encoder is involved.  "
+                            "HIGHER means LESS varied.  real / generated: within a batch row j against row j + take // 2; the "
+                            "batches are sorted by caption length, so a pair's captions are of similar length.  same_caption: "
+                            "two images for one caption, boxes and labels under independent noise; near 1 means the generator "
+                            "ignores its noise.  A pair with a negative level mean scores 0 and is counted as clamped.  The images "
+                            "enter as fp32 in [-1, 1], not quantised to 8 bits."})
+        save_dir = eval_save_dir(split_dir)
+        write_json(save_dir, "msssim", out)
+        print("MS-SSIM (%d scales; mean +- std over pairs): %s -> %s/msssim.json"
+              % (images.scales, ", ".join("%s %.4f +- %.4f (%d pairs)" % (k, out[k]["mean"], out[k]["std"], out[k]["pairs"])
+                                          for k in ("real", "generated", "same_caption") if k in out), save_dir))
         return out
 
     def sample(self, split_dir, num_samples=25, draw_bbox=False):

@@ -81,7 +81,17 @@ def parse_args(argv=None):
     parser.add_argument('--swd_repeats', type=int, default=4, metavar='N', help='with --swd: repeats of the random projection')
     parser.add_argument('--swd_min_res', type=int, default=16, metavar='S',
                         help='with --swd: the coarsest pyramid level (256 / S must be a power of two)')
+    parser.add_argument('--msssim', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): multi-scale structural similarity between pairs of real images, the same '
+                             'pairs of generated images, and two images per caption under independent noise (condGANTrainer.msssim: '
+                             'no image encoder involved; higher = less varied) -> <NET_G minus .pth>/<split>/msssim.json; with any of '
+                             '--fid --kid --prdc --swd all take one pass; not together with --sampling or --r_precision')
+    parser.add_argument('--msssim_scales', type=int, default=5, metavar='N', help='with --msssim: number of scales (1..5)')
+    parser.add_argument('--msssim_no_resample', action='store_true',
+                        help='with --msssim: leave the second image per caption, and so the same_caption figure, out')
     args = parser.parse_args(argv)
+    if args.msssim and (args.sampling or args.r_precision):
+        parser.error('--msssim cannot be combined with --sampling or --r_precision')
     if args.swd and (args.sampling or args.r_precision):
         parser.error('--swd cannot be combined with --sampling or --r_precision')
     if args.fid and (args.sampling or args.r_precision):
@@ -141,7 +151,8 @@ def main(argv=None):
         output_dir = args.resume
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
-    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc or args.swd)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc or args.swd
+                                 or args.msssim)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -164,15 +175,27 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
-    elif args.fid + args.kid + args.prdc + args.swd > 1:
+    elif args.fid + args.kid + args.prdc + args.swd + args.msssim > 1:
+        ms_kw = dict(seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
+        pairs = algo.msssim_images(**ms_kw) if args.msssim and cfg.TRAIN.NET_G != '' else None
         swd_kw = dict(seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
                       min_res=args.swd_min_res)
         images = algo.swd_images(**swd_kw) if args.swd and cfg.TRAIN.NET_G != '' else None
-        # one pass over the loader and the trunk for all; --swd takes the pass's images where the others take their codes
-        codes = algo.pool_codes(split_dir, seed=args.manualSeed, image_sink=None if images is None else images.sink)
+        # one pass over the loader and the trunk for all; --swd and --msssim take the pass's images where the others take their
+        # codes, and the trunk stays out where only those two are asked for
+        sinks = [acc.sink for acc in (images, pairs) if acc is not None]
+
+        def image_sink(real, fake, take):
+            for sink in sinks:
+                sink(real, fake, take)
+        codes = algo.pool_codes(split_dir, seed=args.manualSeed, image_sink=image_sink if sinks else None,
+                                trunk=bool(args.fid or args.kid or args.prdc),
+                                resample_sink=None if pairs is None else pairs.resample_sink)
         if codes is not None:
             if images is not None:
                 algo.swd(split_dir, images=images, **swd_kw)
+            if pairs is not None:
+                algo.msssim(split_dir, images=pairs, **ms_kw)
             if args.fid:
                 algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats, codes=codes)
             if args.kid:
@@ -188,6 +211,8 @@ def main(argv=None):
     elif args.swd:
         algo.swd(split_dir, seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
                  min_res=args.swd_min_res)
+    elif args.msssim:
+        algo.msssim(split_dir, seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:

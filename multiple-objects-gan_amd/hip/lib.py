@@ -156,6 +156,9 @@ SIGNATURES = {
     "mogan_swd_moments_f64": [P, L, I, P, P, Z, P],
     "mogan_swd_project": [P, L, I, P, P, I, P, P],
     "mogan_swd_absdiff_f64": [P, P, L, I, P, P],
+    "mogan_avg_down2": [P, L, I, I, P, P],
+    "mogan_ssim_level_ws_bytes": [L, I, I, I],
+    "mogan_ssim_level_f64": [P, P, L, I, I, P, I, P, P, P, P, Z, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }
@@ -185,7 +188,8 @@ class TailArgs(ctypes.Structure):               # MoganTailArgs
 
 _RESTYPE = {"mogan_bn_ws_bytes": Z, "mogan_upconv3x3_ws_bytes": Z, "mogan_pk_weight_bytes": Z, "mogan_pk_panel_bytes": Z,
             "mogan_wino_prep_bytes": Z, "mogan_conv_prep_bytes": Z, "mogan_poly3_mmd_ws_bytes": Z,
-            "mogan_knn_sqdist_ws_bytes": Z, "mogan_ball_count_ws_bytes": Z, "mogan_swd_moments_ws_bytes": Z}
+            "mogan_knn_sqdist_ws_bytes": Z, "mogan_ball_count_ws_bytes": Z, "mogan_swd_moments_ws_bytes": Z,
+            "mogan_ssim_level_ws_bytes": Z}
 _ERRORS = {-1: "MOGAN_ERR_SHAPE", -2: "MOGAN_ERR_LAUNCH", -3: "MOGAN_ERR_WS"}
 
 _lib = None

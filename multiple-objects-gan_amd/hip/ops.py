@@ -2043,6 +2043,51 @@ def swd_absdiff(a, b):
     return out
 
 
+def avg_down2(x):
+    """The aligned 2 x 2 mean of DESIGN.md section 9h (mogan_avg_down2): fp32 x (N C, H, W) -> (N C, H / 2, W / 2),
+    ((x00 + x01) + (x10 + x11)) / 4.  H and W even.  No gradient.  Nothing is converted or copied for the caller: a wrong dtype,
+    rank, contiguity or size is a ValueError."""
+    x = _dense_f32("avg_down2", "x", x, 3)
+    NC, H, W = x.shape
+    if H % 2 or W % 2 or x.numel() > 2 ** 31 - 1:
+        raise ValueError("avg_down2: x (N C, H, W) with even H, W and fewer than 2^31 elements expected, got %s" % (tuple(x.shape),))
+    px = ptr(x)
+    out = torch.empty((NC, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    call("mogan_avg_down2", px, NC, H, W, ptr(out), stream_ptr())
+    return out
+
+
+def ssim_level(a, b, window, maps=False):
+    """One scale of the structural similarity of P pairs of images (mogan_ssim_level_f64; attngan/msssim.py has the definition):
+    fp32 a, b (P, C, S, S) with C in 1..4 and the fp32 window (n,), n <= min(11, S), on their device -> terms (P, 2) fp64 on the
+    device, (mean ssim, mean cs) of every pair over its channels and its (S - n + 1)^2 valid positions; with maps=True
+    (terms, ssim_map, cs_map), the maps (P, C, S - n + 1, S - n + 1) fp32.  A bit copy gives 1.0 exactly, exchanging a and b gives
+    the same bits, and so does a second call.  No gradient.  Nothing is converted or copied for the caller: a wrong dtype, rank,
+    device, contiguity or size is a ValueError."""
+    a = _dense_f32("ssim_level", "a", a, 4)
+    b = _dense_f32("ssim_level", "b", b, 4)
+    window = _dense_f32("ssim_level", "window", window, 1)
+    P, C, S, n = a.shape[0], a.shape[1], a.shape[2], window.shape[0]
+    if a.shape != b.shape:
+        raise ValueError("ssim_level: a and b must have one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if C > 4 or S < 2 or a.shape[3] != S or a.numel() > 2 ** 31 - 1:
+        raise ValueError("ssim_level: pairs (P, 1..4, S, S) with S >= 2 and fewer than 2^31 elements expected, got %s" % (tuple(a.shape),))
+    if n > min(11, S):
+        raise ValueError("ssim_level: a window of at most min(11, S = %d) taps expected, got %d" % (S, n))
+    if not (a.device == b.device == window.device):
+        raise ValueError("ssim_level: a, b and the window must be on one device (%s, %s, %s)" % (a.device, b.device, window.device))
+    pa, pb, pw = ptr(a), ptr(b), ptr(window)
+    ws, ws_bytes, own = _scratch(a.device, int(lib.load().mogan_ssim_level_ws_bytes(P, C, S, n)))
+    terms = torch.empty((P, 2), dtype=torch.float64, device=a.device)
+    M = S - n + 1
+    ssim_map = torch.empty((P, C, M, M), dtype=torch.float32, device=a.device) if maps else None
+    cs_map = torch.empty((P, C, M, M), dtype=torch.float32, device=a.device) if maps else None
+    call("mogan_ssim_level_f64", pa, pb, P, C, S, pw, n, ptr(terms), ptr(ssim_map), ptr(cs_map), ws, ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(a.device))
+    return (terms, ssim_map, cs_map) if maps else terms
+
+
 class ScalarSumFn(torch.autograd.Function):
     """sum_k w_k * x_k over up to 8 zero-dim device scalars in ONE launch (forward) / one launch (backward): the loss sums
     of miscc/losses.py:169-174,203,221 and trainer.py:330 otherwise cost a chain of 0-dim aten kernels each way."""
