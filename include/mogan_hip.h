@@ -860,6 +860,28 @@ size_t mogan_ssim_level_ws_bytes(long long P, int C, int S, int n);
 int mogan_ssim_level_f64(const float* a, const float* b, long long P, int C, int S, const float* win, int n, double* terms,
                          float* ssim_map, float* cs_map, void* ws, size_t ws_bytes, hipStream_t stream);
 
+/* Crop, compaction and resize of a ragged list of boxes in one launch: what the object-level Frechet distance feeds the trunk
+ * (SceneFID, Sylvain et al. 2021; csrc/mogan_roi.hip; attngan/scenefid.py has the score's definition; the
+ * reference has no code for it).  x (B, C, H, W) fp32; boxes (R, 4) fp32, relative (x, y, w, h), the data set's convention;
+ * image_index (R) int32; y (R, C, OH, OW) fp32; all dense and on the device.  ROI r is box r of image image_index[r].
+ * Per axis (x shown; y alike with H, OH, box[1], box[3]), fp32 with ONE rounding per operation in this order, never contracted:
+ *     p0 = box.x * W                 pl = box.w * W                 scale = pl / OW
+ *     src(j) = p0 + (((float)j + 0.5f) * scale - 0.5f)     then clamped to [0, W - 1]
+ *     i0 = floor(src)    i1 = min(i0 + 1, W - 1)    l = src - (float)i0
+ *   y[r][c][oy][ox] = (1 - ly) * ((1 - lx) * x[y0][x0] + lx * x[y0][x1]) + ly * ((1 - lx) * x[y1][x0] + lx * x[y1][x1])
+ * on channel c of image image_index[r] (the blend may be contracted; this build does not).  The clamp repeats the edge pixel: what
+ * a box reaches past the image, and the half pixel around a box at the edge, is the edge's value, not zero.  The full box
+ * (0, 0, 1, 1) is bilinear interpolation with align_corners = False.
+ * Safe by construction: a ROI with w <= 0 or h <= 0 (the data set's absent object is (-1, -1, -1, -1)), with a box value that is
+ * not finite, or with image_index outside [0, B) reads nothing of x and gets zeros in its whole (C, OH, OW) slab; every other ROI's
+ * taps are clamped into the image.  Every element of y is written on every call, nothing outside y is written, and the same
+ * inputs give the same bits on every call.  One thread per output pixel, looping over the channels; no LDS, no atomics, no
+ * workspace.
+ * MOGAN_ERR_SHAPE before any HIP call: a NULL pointer; B, H, W, OH or OW < 1; C < 1 or C > 4; R < 0; any of B C H W, H W or
+ * R C OH OW above 2^31 - 1.  R = 0 returns 0 without a launch. */
+int mogan_roi_resize(const float* x, int B, int C, int H, int W, const float* boxes, const int* image_index, long long R,
+                     float* y, int OH, int OW, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

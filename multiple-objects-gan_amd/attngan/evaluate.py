@@ -1,8 +1,9 @@
-"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9h).
+"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9i).
 
 `CheckpointEvaluation` is the base of `trainer.condGANTrainer` that holds every path which reads a finished checkpoint instead of
 training one: `sampling` / `sample` (images), `r_precision`, and `pool_codes` with the three scores `fid` / `kid` / `prdc` that share
-its pass and `swd` and `msssim`, which take the pass's images instead of their codes.  It needs `self.device`, `self.data_loader`,
+its pass, `swd` and `msssim`, which take the pass's images instead of their codes, and `scene_fid`, which takes the images and
+their boxes and runs the trunk on the objects.  It needs `self.device`, `self.data_loader`,
 `self.n_words` and `self.ixtoword` of the trainer and nothing of the train step.  What these paths have in common is written
 once here: the NET_G guard and the save-directory rule (`net_g_missing`, `eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
 (`generate_seeded`), and what the three scores do around their own device calls (`PooledCodes`, `trunk_note`)."""
@@ -281,7 +282,8 @@ class CheckpointEvaluation(object):
                          "rank": rank, "bank": bank.bank.cpu()}
         return out
 
-    def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True, image_sink=None, trunk=True, resample_sink=None):
+    def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True, image_sink=None, trunk=True, resample_sink=None,
+                   object_sink=None):
         """The one pass over the data loader that the scores share: the real 256x256 image and one generated 256x256 image per
         caption (EMA generator, eval mode, noise from the seeded device generator exactly as r_precision draws it) go through
         CNN_ENCODER.pool_code; the codes stay on the device in two preallocated (num_samples, 2048) fp32 buffers.  `want_real`
@@ -297,9 +299,15 @@ class CheckpointEvaluation(object):
         `resample_sink`, where given, makes the pass generate a SECOND image per caption right after the batch's first one -- the
         same text, boxes and labels, noise and then eps (generate_seeded's order) from a device generator of its own seeded
         `seed` + 1 -- and is called with (fake, fake_again, take) (msssim() scores how much the noise changes there).  The first
-        generator's draws, and so the images every other score sees, are those of a pass without it."""
+        generator's draws, and so the images every other score sees, are those of a pass without it.
+        `object_sink`, where given, is called once per batch with (real, fake, tm, take, image_encoder): the images as for
+        `image_sink`, the batch's box matrices `tm` (B, 3, 2, 3) on the device and the pass's image encoder (scene_fid() cuts the
+        objects out there and runs the trunk on them).  It needs the trunk: ValueError with trunk=False.  It draws nothing, so
+        every other score's images and codes are those of a pass without it."""
         from .datasets import prepare_data
         from .fid import trunk_digest
+        if object_sink is not None and not trunk:
+            raise ValueError("pool_codes: an object_sink needs the image encoder, trunk=False leaves it out")
         if net_g_missing():
             return None
         netG, text_encoder, image_encoder, gen = self._load_seeded(seed, trunk)
@@ -333,6 +341,8 @@ class CheckpointEvaluation(object):
                         real_codes[n:n + take] = image_encoder.pool_code(imgs[-1])[:take]
                 if image_sink is not None:
                     image_sink(imgs[-1], fake, take)
+                if object_sink is not None:
+                    object_sink(imgs[-1], fake, tm, take, image_encoder)
             n += take
         return {"real": real_codes, "fake": fake_codes, "n": n, "trunk_digest": digest, "seed": int(seed)}
 
@@ -570,6 +580,67 @@ class CheckpointEvaluation(object):
         print("MS-SSIM (%d scales; mean +- std over pairs): %s -> %s/msssim.json"
               % (images.scales, ", ".join("%s %.4f +- %.4f (%d pairs)" % (k, out[k]["mean"], out[k]["std"], out[k]["pairs"])
                                           for k in ("real", "generated", "same_caption") if k in out), save_dir))
+        return out
+
+    def scene_fid_objects(self, num_samples=30000, seed=100, min_side=1):
+        """The accumulator scene_fid() fills: attngan/scenefid.ObjectCodes for the tree's final resolution, as many images as the
+        pass will see and the loader's batch size as the one batch shape the trunk runs at, with `sink`, the (real, fake, tm, take,
+        image_encoder) callable of pool_codes' object_sink.  A caller that shares one pass between scene_fid() and other scores
+        makes it first and hands it to both (main.py)."""
+        from .scenefid import ObjectCodes
+        size = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1)
+        images = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        return ObjectCodes(images, int(self.data_loader.batch_size), size, min_side, seed, self.device)
+
+    def scene_fid(self, split_dir, num_samples=30000, seed=100, min_side=1, objects=None, return_codes=False):
+        """Object-level Frechet distance (SceneFID, Sylvain et al. 2021; attngan/scenefid.py has the
+        definition) of the checkpoint TRAIN.NET_G: every object of the data -- a box with w, h > 0 whose shorter side is at least
+        `min_side` pixels -- is cut at its ground-truth box out of the real 256x256 image and out of the image generated for the same
+        caption, boxes and labels (exactly the images pool_codes and r_precision see under `seed`), resized to the trunk's 299x299
+        input in the same launch (hip/ops.roi_resize) and sent through CNN_ENCODER.pool_code of TRAIN.NET_E's image encoder; the
+        figure is fid()'s distance over the objects' codes (hip/ops.feature_moments, fid.frechet_distance).  It moves where the
+        whole-image scores cannot: when the generator paints a believable scene and nothing plausible at the boxes.  ONE pass over
+        the data loader (pool_codes), unless the caller shares one: `objects` is then the accumulator of scene_fid_objects() whose
+        sink that pass has fed.  Writes <NET_G minus .pth>/<split>/scene_fid.json and returns its content; with return_codes also a
+        dict of host tensors: the code matrices "real" and "fake" and the objects their rows stand for, "image" (in global image
+        order) and "box"."""
+        from .fid import frechet_distance, trunk_digest
+        if net_g_missing():
+            return None
+        if objects is None:
+            objects = self.scene_fid_objects(num_samples, seed, min_side)
+            self.pool_codes(split_dir, num_samples, seed, want_real=False, object_sink=objects.sink)
+        elif (objects.seed, objects.min_side) != (int(seed), float(min_side)):
+            raise ValueError("scene_fid: the objects handed over were gathered under other parameters (seed, min_side) = %s"
+                             % ((objects.seed, objects.min_side),))
+        real, fake = objects.finish()
+        n = objects.n
+        if n < 2:
+            raise ValueError("scene_fid: the data loader gave %d objects; a covariance needs two at least" % n)
+        D = int(real.shape[1])
+        digest = trunk_digest(objects.encoder)
+        stats = [[t.cpu() for t in ops.feature_moments(codes)] for codes in (real, fake)]
+        dist, terms = frechet_distance(stats[0][0], stats[0][1], stats[1][0], stats[1][1])
+        note = trunk_note("Object-level Frechet distance (SceneFID: every object cut at its box and resized to the trunk's input)",
+                          "SceneFID", "a distance")
+        note += (" The boxes are the data's on both sides: the real and the generated image of a caption are cut at the same "
+                 "ground-truth boxes; a box counts when its shorter side is at least min_side pixels.")
+        if n < D:
+            note += (" n = %d < %d features: the covariances are rank-deficient, so the figure is biased and only comparable "
+                     "at equal n." % (n, D))
+            print("SceneFID: %d objects for %d features -- the covariances are rank-deficient, the figure is biased and only "
+                  "comparable at equal n (the JSON records it)" % (n, D))
+        out = dict(terms, scene_fid=dist)
+        out.update({"n_objects": int(n), "n_images": int(objects.n_images), "min_side": objects.min_side, "seed": int(seed),
+                    "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E, "trunk_digest": digest, "note": note})
+        save_dir = eval_save_dir(split_dir)
+        write_json(save_dir, "scene_fid", out)
+        print("SceneFID (%d objects of %d images, real and generated): %.4f = |dmu|^2 %.4f + Tr S_real %.4f + Tr S_fake %.4f - 2 x %.4f "
+              "-> %s/scene_fid.json" % (n, objects.n_images, dist, terms["mean_sq"], terms["tr_s1"], terms["tr_s2"], terms["tr_sqrt"],
+                                        save_dir))
+        if return_codes:
+            image, box = objects.objects()
+            return out, {"real": real.cpu(), "fake": fake.cpu(), "image": image, "box": box}
         return out
 
     def sample(self, split_dir, num_samples=25, draw_bbox=False):

@@ -89,7 +89,16 @@ def parse_args(argv=None):
     parser.add_argument('--msssim_scales', type=int, default=5, metavar='N', help='with --msssim: number of scales (1..5)')
     parser.add_argument('--msssim_no_resample', action='store_true',
                         help='with --msssim: leave the second image per caption, and so the same_caption figure, out')
+    parser.add_argument('--scene_fid', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): object-level Frechet distance (SceneFID) -- every object of the data cut '
+                             'at its box out of the real and out of the generated image, resized to the trunk\'s input and scored as '
+                             '--fid scores whole images (condGANTrainer.scene_fid) -> <NET_G minus .pth>/<split>/scene_fid.json; with '
+                             'any of --fid --kid --prdc --swd --msssim all take one pass; not together with --sampling or --r_precision')
+    parser.add_argument('--scene_fid_min_side', type=float, default=1, metavar='PX',
+                        help='with --scene_fid: leave out boxes whose shorter side is below PX pixels of the 256x256 image')
     args = parser.parse_args(argv)
+    if args.scene_fid and (args.sampling or args.r_precision):
+        parser.error('--scene_fid cannot be combined with --sampling or --r_precision')
     if args.msssim and (args.sampling or args.r_precision):
         parser.error('--msssim cannot be combined with --sampling or --r_precision')
     if args.swd and (args.sampling or args.r_precision):
@@ -152,7 +161,7 @@ def main(argv=None):
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
     with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc or args.swd
-                                 or args.msssim)
+                                 or args.msssim or args.scene_fid)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -175,23 +184,30 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
-    elif args.fid + args.kid + args.prdc + args.swd + args.msssim > 1:
+    elif args.fid + args.kid + args.prdc + args.swd + args.msssim + args.scene_fid > 1:
+        sf_kw = dict(seed=args.manualSeed, min_side=args.scene_fid_min_side)
+        objects = algo.scene_fid_objects(**sf_kw) if args.scene_fid and cfg.TRAIN.NET_G != '' else None
         ms_kw = dict(seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
         pairs = algo.msssim_images(**ms_kw) if args.msssim and cfg.TRAIN.NET_G != '' else None
         swd_kw = dict(seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
                       min_res=args.swd_min_res)
         images = algo.swd_images(**swd_kw) if args.swd and cfg.TRAIN.NET_G != '' else None
         # one pass over the loader and the trunk for all; --swd and --msssim take the pass's images where the others take their
-        # codes, and the trunk stays out where only those two are asked for
+        # codes, and the trunk stays out where only those two are asked for; --scene_fid takes the images, their boxes and the
+        # trunk, and the real images' own codes stay out where none of --fid --kid --prdc wants them
         sinks = [acc.sink for acc in (images, pairs) if acc is not None]
 
         def image_sink(real, fake, take):
             for sink in sinks:
                 sink(real, fake, take)
-        codes = algo.pool_codes(split_dir, seed=args.manualSeed, image_sink=image_sink if sinks else None,
-                                trunk=bool(args.fid or args.kid or args.prdc),
-                                resample_sink=None if pairs is None else pairs.resample_sink)
+        whole = bool(args.fid or args.kid or args.prdc)
+        codes = algo.pool_codes(split_dir, seed=args.manualSeed, want_real=whole, image_sink=image_sink if sinks else None,
+                                trunk=whole or args.scene_fid,
+                                resample_sink=None if pairs is None else pairs.resample_sink,
+                                object_sink=None if objects is None else objects.sink)
         if codes is not None:
+            if objects is not None:
+                algo.scene_fid(split_dir, objects=objects, **sf_kw)
             if images is not None:
                 algo.swd(split_dir, images=images, **swd_kw)
             if pairs is not None:
@@ -211,6 +227,8 @@ def main(argv=None):
     elif args.swd:
         algo.swd(split_dir, seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
                  min_res=args.swd_min_res)
+    elif args.scene_fid:
+        algo.scene_fid(split_dir, seed=args.manualSeed, min_side=args.scene_fid_min_side)
     elif args.msssim:
         algo.msssim(split_dir, seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
     elif cfg.B_VALIDATION:

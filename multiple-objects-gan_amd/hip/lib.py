@@ -159,6 +159,7 @@ SIGNATURES = {
     "mogan_avg_down2": [P, L, I, I, P, P],
     "mogan_ssim_level_ws_bytes": [L, I, I, I],
     "mogan_ssim_level_f64": [P, P, L, I, I, P, I, P, P, P, P, Z, P],
+    "mogan_roi_resize": [P, I, I, I, I, P, P, L, P, I, I, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }

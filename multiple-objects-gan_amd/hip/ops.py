@@ -2088,6 +2088,55 @@ def ssim_level(a, b, window, maps=False):
     return (terms, ssim_map, cs_map) if maps else terms
 
 
+def roi_resize(x, boxes, image_index, OH, OW, out=None):
+    """Crop, compaction and edge-clamped bilinear resize of a ragged list of boxes in one launch (mogan_roi_resize; DESIGN.md section
+    9i): fp32 x (B, C, H, W) on the device with C in 1..4; boxes (R, 4) fp32, relative (x, y, w, h), and image_index (R) int32 or
+    int64 are HOST tensors -- checked here, then uploaded -- -> (R, C, OH, OW) fp32 on x's device, row r the box boxes[r] of image
+    image_index[r].  A box with w <= 0 or h <= 0 gives zeros.  `out`, where given, is a dense (R, C, OH, OW) fp32 tensor on x's device
+    (rows of a larger buffer, for one) and is returned.  R = 0 returns an empty tensor without a launch.  No gradient.  Nothing is
+    converted or copied for the caller: a wrong type, dtype, rank, stride or device, an index outside [0, B) and a box value that is
+    not finite are a ValueError."""
+    x = _dense_f32("roi_resize", "x", x, 4)
+    B, C, H, W = x.shape
+    OH, OW = int(OH), int(OW)
+    if C > 4 or x.numel() > 2 ** 31 - 1 or OH < 1 or OW < 1:
+        raise ValueError("roi_resize: x (B, 1..4, H, W) with fewer than 2^31 elements and OH, OW >= 1 expected, got %s -> (%d, %d)"
+                         % (tuple(x.shape), OH, OW))
+    for name, t, dtypes, ndim in (("boxes", boxes, (torch.float32,), 2), ("image_index", image_index, (torch.int32, torch.int64), 1)):
+        if not torch.is_tensor(t) or t.dtype not in dtypes or t.device.type != "cpu":
+            raise ValueError("roi_resize: %s must be a host tensor of %s, got %s %s" % (
+                name, " or ".join(str(d) for d in dtypes), getattr(t, "dtype", type(t)), getattr(t, "device", "")))
+        if t.dim() != ndim or not t.is_contiguous():
+            raise ValueError("roi_resize: %s must be a contiguous tensor of %d dimensions, got %s with strides %s"
+                             % (name, ndim, tuple(t.shape), tuple(t.stride())))
+    R = image_index.shape[0]
+    if tuple(boxes.shape) != (R, 4):
+        raise ValueError("roi_resize: boxes (R, 4) for image_index (R,) expected, got %s and %s" % (tuple(boxes.shape), (R,)))
+    if x.device.type == "meta":
+        raise ValueError("roi_resize: x is a meta tensor")
+    if R * C * OH * OW > 2 ** 31 - 1:
+        raise ValueError("roi_resize: (%d, %d, %d, %d) has 2^31 elements or more" % (R, C, OH, OW))
+    if R and (int(image_index.min()) < 0 or int(image_index.max()) >= B):
+        raise ValueError("roi_resize: image_index holds images outside [0, %d): min %d, max %d"
+                         % (B, int(image_index.min()), int(image_index.max())))
+    if not bool(torch.isfinite(boxes).all()):
+        raise ValueError("roi_resize: a box value is not finite")
+    if out is not None:
+        if (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (R, C, OH, OW) or not out.is_contiguous()
+                or out.device != x.device):
+            raise ValueError("roi_resize: out must be a dense fp32 %s tensor on %s, got %s %s on %s"
+                             % ((R, C, OH, OW), x.device, getattr(out, "dtype", type(out)), tuple(getattr(out, "shape", ())),
+                                getattr(out, "device", "")))
+    px = ptr(x)                                                # (a host tensor raises here, before anything is uploaded)
+    if out is None:
+        out = torch.empty((R, C, OH, OW), dtype=torch.float32, device=x.device)
+    if R:
+        # one upload for both: the boxes' bits and the index behind them, 20 bytes per object
+        both = torch.cat([boxes.view(torch.int32).view(-1), image_index.to(torch.int32)]).to(x.device)
+        call("mogan_roi_resize", px, B, C, H, W, ptr(both), ptr(both) + 16 * R, R, ptr(out), OH, OW, stream_ptr())
+    return out
+
+
 class ScalarSumFn(torch.autograd.Function):
     """sum_k w_k * x_k over up to 8 zero-dim device scalars in ONE launch (forward) / one launch (backward): the loss sums
     of miscc/losses.py:169-174,203,221 and trainer.py:330 otherwise cost a chain of 0-dim aten kernels each way."""
