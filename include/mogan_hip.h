@@ -729,7 +729,7 @@ int mogan_retrieval_rank(const float* code, const float* pos, const float* bank,
 
 /* fp64 moments of a set of feature codes: what the Frechet distance is computed from (the reference has no code for it --
  * DESIGN.md section 9d; csrc/mogan_stats.hip).  x is fp32 (N, D), dense, widened exactly; mean (D) and cov (D, D) are fp64 -- with
- * the sums of mogan_poly3_mmd_f64, the radii of mogan_knn_sqdist_f64 , the moments and sums of mogan_swd_* and the terms of mogan_ssim_level_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
+ * the sums of mogan_poly3_mmd_f64, the radii of mogan_knn_sqdist_f64, the distances of mogan_knn_cross_f64, the moments and sums of mogan_swd_* and the terms of mogan_ssim_level_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
  * workgroup to workgroup: every sum over n runs in one fixed order, so the same inputs give the same bits on every call.
  *   mean[j]   = (sum_n (double)x[n][j]) / N
  *   cov[i][j] = (sum_n (x[n][i] - mean[i]) (x[n][j] - mean[j])) / (N - 1)       (numpy.cov(x, rowvar=False))
@@ -790,6 +790,25 @@ int mogan_knn_sqdist_f64(const float* x, long long N, int D, int K, double* out,
 size_t mogan_ball_count_ws_bytes(long long M, long long N, int R);
 int mogan_ball_count_f64(const float* q, long long M, const float* p, long long N, int D, const double* r2, int R, int side,
                          int32_t* count, void* ws, size_t ws_bytes, hipStream_t stream);
+
+/* Nearest neighbours BETWEEN two sets, with their positions: what the memorisation figures of DESIGN.md section 9j are computed
+ * from (csrc/mogan_knn.hip; the reference has no code for it).  For every query row q_j of q (M, D), d2 (M, K) fp64 and idx (M, K)
+ * int32 hold the K smallest d2(q_j, p_i) over all rows i of p (N, D), ascending, and the positions i.  The distances are the ones
+ * above -- the same tile loop, the same row norms, the same one expression -- so their bits depend on the two rows only, a bit copy
+ * is at exactly 0, and they equal what mogan_knn_sqdist_f64 and mogan_ball_count_f64 form for the same two rows.  Where two
+ * distances are equal bit for bit the lower position comes first: the order is the lexicographic order of (d2, i), a total order,
+ * so the result does not depend on how the support tiles are split into shares.  1 <= K <= 8, N >= K.  A NaN distance (non-finite
+ * inputs) is never a neighbour; a query that has fewer than K others keeps d2 = +inf, idx = 2^31 - 1 in the slots left over.
+ * A workgroup owns a stripe of 64 queries and walks the support tiles of its share, `shares` = min(ceil(512 / Tr), Tc, 64) as above
+ * with Tr = ceil(M / 64), Tc = ceil(N / 64); one thread per query keeps the 8 first pairs in registers; a last launch of the same
+ * call merges the shares' lists per query under the same order.  No distance matrix is written, there are no atomics, and the same
+ * inputs give the same bits on every call.  The workspace is required, 8-byte aligned:
+ *   mogan_knn_cross_ws_bytes(M, N, K) = 8 (M + N + shares M K) + 4 shares M K rounded up to 8     (0 for arguments the call rejects)
+ * MOGAN_ERR_WS where ws is NULL, misaligned or shorter, nothing launched.  MOGAN_ERR_SHAPE before any HIP call (and before the
+ * workspace is looked at): a NULL q / p / d2 / idx, K < 1, K > 8, N < K, M < 1, M or N > 2^31 - 1, D < 1, D > 65536. */
+size_t mogan_knn_cross_ws_bytes(long long M, long long N, int K);
+int mogan_knn_cross_f64(const float* q, long long M, const float* p, long long N, int D, int K, double* d2, int32_t* idx, void* ws,
+                        size_t ws_bytes, hipStream_t stream);
 
 /* The sliced Wasserstein distance of Karras et al. 2018 between real and generated images (DESIGN.md section 9g;
  * csrc/mogan_swd.hip; the reference has no code for it): Laplacian pyramid, 7 x 7 descriptors, their moments, their projections

@@ -1,9 +1,9 @@
-"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9i).
+"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9j).
 
 `CheckpointEvaluation` is the base of `trainer.condGANTrainer` that holds every path which reads a finished checkpoint instead of
 training one: `sampling` / `sample` (images), `r_precision`, and `pool_codes` with the three scores `fid` / `kid` / `prdc` that share
 its pass, `swd` and `msssim`, which take the pass's images instead of their codes, and `scene_fid`, which takes the images and
-their boxes and runs the trunk on the objects.  It needs `self.device`, `self.data_loader`,
+their boxes and runs the trunk on the objects, and `memorisation`, which searches the pass's codes in a bank of the TRAIN split's.  It needs `self.device`, `self.data_loader`,
 `self.n_words` and `self.ixtoword` of the trainer and nothing of the train step.  What these paths have in common is written
 once here: the NET_G guard and the save-directory rule (`net_g_missing`, `eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
 (`generate_seeded`), and what the three scores do around their own device calls (`PooledCodes`, `trunk_note`)."""
@@ -137,8 +137,46 @@ class PooledCodes:
         return out
 
 
+THUMB = 64                   # side of the thumbnails of nn_grid.png
+BANK_SEED_STEP = 1           # a synthetic split's training bank: a second synthetic set, under the split's seed plus this
+
+
+class Thumbnails:
+    """u8 THUMB x THUMB thumbnails of a pass's generated images on the host, in the pass's order (12 KB per image): `sink` is the
+    (real, fake, take) callable of pool_codes' image_sink and halves the generated images with hip/ops.avg_down2 -- the aligned
+    2 x 2 mean, twice for 256 x 256 -- until they are THUMB wide.  memorisation() shows its most suspicious rows from it."""
+
+    def __init__(self):
+        self.rows = []
+
+    def sink(self, real, fake, take):
+        t = fake[:take].float().contiguous()
+        B, C, H, W = t.shape
+        t = t.view(B * C, H, W)
+        while t.shape[-1] > THUMB and t.shape[-1] % 2 == 0 and t.shape[-2] % 2 == 0:
+            t = ops.avg_down2(t)
+        self.rows.append(t.view(B, C, t.shape[-2], t.shape[-1]).add(1.0).mul(127.5).clamp(0, 255).byte().cpu())
+
+    def __len__(self):
+        return sum(int(r.shape[0]) for r in self.rows)
+
+    def images(self, rows):
+        """(len(rows), 3, h, w) u8, numpy"""
+        every = torch.cat(self.rows)
+        return every[torch.as_tensor(np.asarray(rows, dtype=np.int64))].numpy()
+
+
+def thumbnail_u8(img):
+    """a (3, H, W) image in [-1, 1] (host) as (3, h, w) u8 with h, w <= THUMB where H, W are THUMB times a power of two: the mean
+    over aligned squares"""
+    a = np.asarray(img, dtype=np.float32)
+    while a.shape[-1] > THUMB and a.shape[-1] % 2 == 0 and a.shape[-2] % 2 == 0:
+        a = ((a[:, 0::2, 0::2] + a[:, 0::2, 1::2]) + (a[:, 1::2, 0::2] + a[:, 1::2, 1::2])) / np.float32(4)
+    return np.clip((a + 1.0) * 127.5, 0, 255).astype(np.uint8)
+
+
 class CheckpointEvaluation(object):
-    """The evaluation methods of condGANTrainer (reference trainer.py:387-579 and DESIGN.md sections 9c-9f)."""
+    """The evaluation methods of condGANTrainer (reference trainer.py:387-579 and DESIGN.md sections 9c-9j)."""
 
     def _load_eval_models(self):
         """The two checkpoints of the evaluation paths (trainer.py:397-417, 483-505): EMA generator from
@@ -642,6 +680,176 @@ class CheckpointEvaluation(object):
             image, box = objects.objects()
             return out, {"real": real.cpu(), "fake": fake.cpu(), "image": image, "box": box}
         return out
+
+    def train_split(self):
+        """(dataset, name): the TRAIN split next to the data loader's evaluation split, what memorisation() searches -- for a
+        TextDataset the 'train' split of the same directories; for a SyntheticTextDataset a second synthetic set of the same
+        length and vocabulary under a seed of its own (the split's plus BANK_SEED_STEP), named 'synthetic-train'"""
+        from .datasets import SyntheticTextDataset, TextDataset
+        ds = self.data_loader.dataset
+        if isinstance(ds, SyntheticTextDataset):
+            return SyntheticTextDataset(ds.length, ds.n_words, seed=ds.seed + BANK_SEED_STEP), "synthetic-train"
+        if isinstance(ds, TextDataset):
+            return TextDataset(ds.data_dir, ds.img_dir, 'train', base_size=cfg.TREE.BASE_SIZE), "train"
+        raise ValueError("memorisation: no train split is known for a %s; hand a bank over" % type(ds).__name__)
+
+    @staticmethod
+    def dataset_key(dataset, position):
+        """the key of a dataset's sample without reading its image"""
+        names = getattr(dataset, "filenames", None)
+        return str(names[position]) if names is not None else 'synthetic_%06d' % position
+
+    def neighbour_bank(self, seed=100, bank_size=None, digest=None):
+        """fid.NeighbourBank of the train split (train_split): the pool codes of its first `bank_size` real images (all where
+        None), in dataset order, under the image encoder a pass under `seed` runs -- loaded as _load_seeded loads it, so a
+        random-init trunk of an empty NET_E is the pass's too; `digest`, where given, is checked against it.  No generator runs
+        and no caption is encoded.  The trunk sees the loader's batch size only: the last batch is filled up with zeros.  The
+        global generators' states are put back, so a pass that follows shuffles and crops as it would have without this call."""
+        from .fid import NeighbourBank, trunk_digest
+        dataset, name = self.train_split()
+        rows = len(dataset) if bank_size is None else max(1, min(int(bank_size), len(dataset)))
+        states = torch.get_rng_state(), np.random.get_state()
+        try:
+            image_encoder = self._load_seeded(seed)[2]
+            own = trunk_digest(image_encoder)
+            if digest is not None and own != digest:
+                raise ValueError("memorisation: the bank's trunk (digest %s...) is not the pass's (%s...)" % (own[:12], digest[:12]))
+            chunk = int(self.data_loader.batch_size)
+            loader = torch.utils.data.DataLoader(torch.utils.data.Subset(dataset, range(rows)), batch_size=chunk, shuffle=False,
+                                                 num_workers=int(self.data_loader.num_workers))
+            D = int(image_encoder.emb_cnn_code.weight.shape[1])
+            codes = torch.empty((rows, D), dtype=torch.float32, device=self.device)
+            n = 0
+            for batch in loader:
+                img = batch[0][-1].to(self.device)
+                take = int(img.shape[0])
+                if take < chunk:
+                    img = torch.cat([img, img.new_zeros((chunk - take,) + tuple(img.shape[1:]))])
+                with torch.no_grad():
+                    codes[n:n + take] = image_encoder.pool_code(img)[:take]
+                n += take
+        finally:
+            torch.set_rng_state(states[0])
+            np.random.set_state(states[1])
+        return NeighbourBank(codes.cpu(), np.arange(rows), own, name)
+
+    def memorisation(self, split_dir, num_samples=30000, seed=100, bank_path=None, bank_size=None, k=5, show=16, codes=None,
+                     bank=None, return_codes=False):
+        """Is the checkpoint TRAIN.NET_G reproducing its TRAINING images?  (attngan/memorisation.py has the
+        definitions.)  Every other score compares the generated images with the evaluation split's or with each other, and a
+        generator that has memorised the training set scores well on all of them.  Here the Inception pool codes of TRAIN.NET_E's
+        image encoder are searched in a bank T of the TRAIN split's real images: `authenticity`, the share of generated images that
+        are not closer to their nearest training image than that image's own nearest training neighbour, next to the same share of
+        the evaluation split's real images (`authenticity_heldout`, the data's own value); `copying`, the Mann-Whitney statistic of
+        the generated images' nearest-bank distances against the held-out real images' (0.5: as far from the training set as
+        unseen real images; towards 1: closer); and the `show` most suspicious generated images with their `k` nearest training
+        images, listed in the JSON and drawn as nn_grid.png, rows of [generated | its k nearest training images] at 64 x 64.
+        The generated and the held-out codes are those of fid() -- ONE pass over the data loader (pool_codes, whose image_sink
+        keeps the thumbnails), or the `codes` a caller hands over from a pass of its own (with a Thumbnails under "thumbnails" where
+        the grid is wanted).  The bank: `bank`, a fid.NeighbourBank, where given; else `bank_path` when that file exists and was
+        taken under the same trunk (ValueError for another trunk's); else neighbour_bank(), saved to `bank_path` where given.
+        `bank_size` cuts it to its first rows.  On the device: hip/ops.knn_sqdist(T, 1), hip/ops.knn_cross(F, T, k),
+        hip/ops.knn_cross(H, T, 1), one read-back; k is lowered to the bank's size where that is smaller.  All figures depend on the
+        bank's size.  Writes <NET_G minus .pth>/<split>/memorisation.json (and nn_grid.png) and returns the JSON's content; with
+        return_codes also a dict of host tensors: the code matrices "real", "fake" and "bank"."""
+        from . import memorisation as MEM
+        from .fid import NeighbourBank
+        if net_g_missing():
+            return None
+        k, show = int(k), int(show)
+        if k < 1 or k > 8 or show < 0:
+            raise ValueError("memorisation: 1 <= k <= 8 and show >= 0 expected, got k = %d, show = %d" % (k, show))
+        if codes is None:
+            thumbs = Thumbnails() if show > 0 else None
+            codes = self.pool_codes(split_dir, num_samples, seed, image_sink=None if thumbs is None else thumbs.sink)
+            codes = dict(codes, thumbnails=thumbs)
+        c = PooledCodes(self, "memorisation", split_dir, num_samples, seed, codes)
+        thumbs = codes.get("thumbnails") if show > 0 else None
+        n, D = c.n, int(c.fake.shape[1])
+        if n < 1:
+            raise ValueError("memorisation: the data loader gave no batch")
+        if bank is None:
+            if bank_path is not None and os.path.isfile(bank_path):
+                bank = NeighbourBank.load(bank_path, c.digest, D)             # ValueError for another trunk's file
+                print('Load the training bank from: %s (%d images of split %s)' % (bank_path, len(bank), bank.split))
+            else:
+                bank = self.neighbour_bank(seed, bank_size, c.digest)
+                if bank_path is not None:
+                    bank.save(bank_path)
+                    print('Save the training bank to: %s' % bank_path)
+        elif bank.trunk_digest != c.digest or bank.codes.shape[1] != D:
+            raise ValueError("memorisation: the bank handed over was computed under another Inception trunk (digest %s..., the "
+                             "codes' is %s...) or at another width" % (bank.trunk_digest[:12], str(c.digest)[:12]))
+        bank_codes, positions = bank.codes, bank.positions
+        if bank_size is not None and len(bank) > int(bank_size):
+            bank_codes, positions = bank_codes[:max(1, int(bank_size))], positions[:max(1, int(bank_size))]
+        n_bank = int(bank_codes.shape[0])
+        if n_bank < 2:
+            raise ValueError("memorisation: a bank of %d image has no nearest other image; two at least" % n_bank)
+        kk = min(k, n_bank)
+        T = torch.tensor(bank_codes).to(self.device)
+        nn_bank = ops.knn_sqdist(T, 1)                                      # every training image's own nearest training neighbour
+        d2_f, idx_f = ops.knn_cross(c.fake.contiguous(), T, kk)
+        d2_h, idx_h = ops.knn_cross(c.real.contiguous(), T, 1)
+        back = torch.cat([t.double().flatten() for t in (d2_f, idx_f, d2_h, idx_h, nn_bank)]).cpu().numpy()    # the one read-back
+        cut = np.cumsum([0, n * kk, n * kk, n, n, n_bank])
+        d2_f, idx_f, d2_h, idx_h, nn_bank = (back[cut[i]:cut[i + 1]] for i in range(5))
+        d2_f, idx_f = d2_f.reshape(n, kk), idx_f.reshape(n, kk).astype(np.int64)
+        idx_h = idx_h.astype(np.int64)
+        out = MEM.scores(d2_f[:, 0], idx_f[:, 0], d2_h, idx_h, nn_bank)
+        rows, ratio = MEM.most_suspicious(d2_f[:, 0], idx_f[:, 0], nn_bank, show)
+        bank_dataset = None
+        suspicious = []
+        for r, x in zip(rows.tolist(), ratio.tolist()):
+            at = positions[idx_f[r]].tolist()
+            entry = {"row": r, "ratio": x, "d2": d2_f[r].tolist(), "nn_bank_d2": float(nn_bank[idx_f[r, 0]]),
+                     "bank_rows": idx_f[r].tolist(), "bank_positions": at}
+            if bank.split in ("train", "synthetic-train"):
+                if bank_dataset is None:
+                    bank_dataset = self.train_split()[0]
+                entry["bank_keys"] = [self.dataset_key(bank_dataset, p) for p in at]
+            suspicious.append(entry)
+        grid = None
+        if thumbs is not None and len(rows) and bank_dataset is not None and len(thumbs) >= n:
+            grid = self._nn_grid(c.save_dir, thumbs.images(rows), [e["bank_positions"] for e in suspicious], bank_dataset)
+        note = trunk_note("Nearest training neighbours (authenticity: the share of generated images not closer to their nearest "
+                          "training image than that image's own nearest training neighbour, authenticity_heldout: the same share "
+                          "of the evaluation split's real images; copying: the Mann-Whitney statistic of the generated images' "
+                          "distances to the training set against the held-out real images', 0.5 = as far as unseen real images, "
+                          "towards 1 = closer)", "the papers' figures", "figures")
+        note += " Every figure depends on n_bank: comparable at equal bank only."
+        if bank.split == "synthetic-train":
+            note += " Synthetic data: the bank is a second synthetic set with a seed of its own, not a split of real images."
+        if kk < k:
+            note += " k lowered from %d to %d: the bank holds only %d images." % (k, kk, n_bank)
+            print("Memorisation: a bank of %d images -- k = %d instead of %d (the JSON records it)" % (n_bank, kk, k))
+        out.update({"n_bank": n_bank, "k": int(kk), "bank_path": bank_path, "bank_split": bank.split, "show": len(suspicious),
+                    "most_suspicious": suspicious, "grid": grid})
+        out = c.write(out, n, n, note)
+        print("Memorisation (%d generated, %d held-out real images against %d training images; k = %d): authenticity %.4f "
+              "(held-out %.4f) copying %.4f -> %s/memorisation.json%s"
+              % (n, n, n_bank, kk, out["authenticity"], out["authenticity_heldout"], out["copying"], c.save_dir,
+                 "" if grid is None else " and %s" % grid))
+        if return_codes:
+            out, both = c.result(out, True)
+            return out, dict(both, bank=torch.tensor(bank_codes))
+        return out
+
+    @staticmethod
+    def _nn_grid(save_dir, generated, bank_positions, bank_dataset):
+        """nn_grid.png: one row per entry, [generated | the training images at its bank positions], THUMB x THUMB each; the
+        training images are re-read from the bank's dataset by position.  Returns the file's name."""
+        from PIL import Image
+        k = max(len(p) for p in bank_positions)
+        h, w = generated.shape[-2], generated.shape[-1]
+        sheet = np.zeros((len(bank_positions) * h, (1 + k) * w, 3), dtype=np.uint8)
+        for r, at in enumerate(bank_positions):
+            sheet[r * h:(r + 1) * h, 0:w] = generated[r].transpose(1, 2, 0)
+            for j, p in enumerate(at):
+                tile = thumbnail_u8(bank_dataset[int(p)][0][-1].numpy())
+                sheet[r * h:r * h + tile.shape[1], (1 + j) * w:(1 + j) * w + tile.shape[2]] = tile.transpose(1, 2, 0)
+        Image.fromarray(sheet).save('%s/nn_grid.png' % save_dir)
+        return "nn_grid.png"
 
     def sample(self, split_dir, num_samples=25, draw_bbox=False):
         """trainer.py:474-579 (what main.py:158 runs for B_VALIDATION): for the first `num_samples` batches of an

@@ -8,7 +8,8 @@ hip/ops.feature_moments -- and compared as Gaussians:
 
   * `frechet_distance`  the distance and its four terms, in fp64 on the host, from two symmetric eigen-decompositions;
   * `trunk_digest`      which trunk weights produced a set of codes;
-  * `FeatureStats`      mean, covariance, count and digest of one set, saved as an .npz and refused for another trunk.
+  * `FeatureStats`      mean, covariance, count and digest of one set, saved as an .npz and refused for another trunk;
+  * `NeighbourBank`     the codes themselves of a split's real images, with their dataset positions, saved and refused likewise.
 Nothing in this module's logic needs a GPU.
 """
 import hashlib
@@ -85,3 +86,43 @@ class FeatureStats:
         if mean.shape != (D,) or cov.shape != (D, D):
             raise ValueError("%s holds statistics of %s features, this encoder has %d" % (path, mean.shape, D))
         return cls(mean, cov, n, digest)
+
+
+class NeighbourBank:
+    """fp32 pool codes (n, D) of a split's real images under the trunk `trunk_digest`, with the dataset positions (n,) their rows
+    stand for and the split's name: what the memorisation figures search for nearest neighbours (host
+    arrays)"""
+
+    def __init__(self, codes, positions, trunk_digest, split):
+        if torch.is_tensor(codes):
+            codes = codes.detach().cpu().numpy()
+        self.codes = np.ascontiguousarray(codes)
+        self.positions = np.ascontiguousarray(np.asarray(positions), dtype=np.int64)
+        self.trunk_digest, self.split = str(trunk_digest), str(split)
+        if self.codes.dtype != np.float32 or self.codes.ndim != 2 or self.codes.shape[0] < 1 or self.codes.shape[1] < 1:
+            raise ValueError("NeighbourBank: fp32 codes (n, D) expected, got %s %s" % (self.codes.dtype, self.codes.shape))
+        if self.positions.shape != (self.codes.shape[0],):
+            raise ValueError("NeighbourBank: one dataset position per code expected, got %s for %d codes"
+                             % (self.positions.shape, self.codes.shape[0]))
+
+    def __len__(self):
+        return int(self.codes.shape[0])
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, codes=self.codes, positions=self.positions, trunk_digest=np.str_(self.trunk_digest),
+                     split=np.str_(self.split))
+
+    @classmethod
+    def load(cls, path, trunk_digest, D):
+        """the bank of `path`; ValueError where it was taken under another trunk or at another feature width"""
+        with np.load(path, allow_pickle=False) as z:
+            codes, positions, digest, split = z["codes"], z["positions"], str(z["trunk_digest"]), str(z["split"])
+        if codes.dtype != np.float32:
+            raise ValueError("%s: fp32 codes expected, found %s" % (path, codes.dtype))
+        if digest != str(trunk_digest):
+            raise ValueError("%s was computed under another Inception trunk (digest %s..., this encoder's is %s...): codes of "
+                             "different trunks cannot be compared" % (path, digest[:12], str(trunk_digest)[:12]))
+        if codes.ndim != 2 or codes.shape[1] != D:
+            raise ValueError("%s holds codes of shape %s, this encoder has %d features" % (path, codes.shape, D))
+        return cls(codes, positions, digest, split)

@@ -96,7 +96,28 @@ def parse_args(argv=None):
                              'any of --fid --kid --prdc --swd --msssim all take one pass; not together with --sampling or --r_precision')
     parser.add_argument('--scene_fid_min_side', type=float, default=1, metavar='PX',
                         help='with --scene_fid: leave out boxes whose shorter side is below PX pixels of the 256x256 image')
+    parser.add_argument('--memorisation', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): is the generator reproducing its TRAINING images?  The pool codes of the '
+                             'generated and of the split\'s real images against their nearest neighbours in a bank of the train '
+                             'split\'s real images (condGANTrainer.memorisation: authenticity, its held-out value, copying, and the '
+                             'most suspicious images next to their nearest training images) -> <NET_G minus .pth>/<split>/'
+                             'memorisation.json and nn_grid.png; with any of --fid --kid --prdc --swd --msssim --scene_fid all take '
+                             'one pass; not together with --sampling or --r_precision')
+    parser.add_argument('--nn_bank', type=str, default=None, metavar='PATH',
+                        help='with --memorisation: the training bank as an .npz -- loaded when it exists and was taken under the same '
+                             'trunk, computed and saved there otherwise')
+    parser.add_argument('--nn_bank_size', type=int, default=None, metavar='N',
+                        help='with --memorisation: the first N training images only (every figure depends on the bank\'s size)')
+    parser.add_argument('--nn_k', type=int, default=5, metavar='K', help='with --memorisation: training neighbours listed and drawn per image (1..8)')
+    parser.add_argument('--nn_show', type=int, default=16, metavar='M',
+                        help='with --memorisation: the M most suspicious generated images are listed and drawn (0: no nn_grid.png)')
     args = parser.parse_args(argv)
+    if args.memorisation and (args.sampling or args.r_precision):
+        parser.error('--memorisation cannot be combined with --sampling or --r_precision')
+    if not 1 <= args.nn_k <= 8:
+        parser.error('--nn_k must be in 1..8')
+    if args.nn_show < 0 or (args.nn_bank_size is not None and args.nn_bank_size < 2):
+        parser.error('--nn_show must not be negative and --nn_bank_size must be 2 at least')
     if args.scene_fid and (args.sampling or args.r_precision):
         parser.error('--scene_fid cannot be combined with --sampling or --r_precision')
     if args.msssim and (args.sampling or args.r_precision):
@@ -161,7 +182,7 @@ def main(argv=None):
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
     with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc or args.swd
-                                 or args.msssim or args.scene_fid)
+                                 or args.msssim or args.scene_fid or args.memorisation)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -184,7 +205,10 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
-    elif args.fid + args.kid + args.prdc + args.swd + args.msssim + args.scene_fid > 1:
+    elif args.fid + args.kid + args.prdc + args.swd + args.msssim + args.scene_fid + args.memorisation > 1:
+        from .evaluate import Thumbnails
+        mem_kw = dict(seed=args.manualSeed, bank_path=args.nn_bank, bank_size=args.nn_bank_size, k=args.nn_k, show=args.nn_show)
+        thumbs = Thumbnails() if args.memorisation and args.nn_show > 0 and cfg.TRAIN.NET_G != '' else None
         sf_kw = dict(seed=args.manualSeed, min_side=args.scene_fid_min_side)
         objects = algo.scene_fid_objects(**sf_kw) if args.scene_fid and cfg.TRAIN.NET_G != '' else None
         ms_kw = dict(seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
@@ -194,13 +218,14 @@ def main(argv=None):
         images = algo.swd_images(**swd_kw) if args.swd and cfg.TRAIN.NET_G != '' else None
         # one pass over the loader and the trunk for all; --swd and --msssim take the pass's images where the others take their
         # codes, and the trunk stays out where only those two are asked for; --scene_fid takes the images, their boxes and the
-        # trunk, and the real images' own codes stay out where none of --fid --kid --prdc wants them
-        sinks = [acc.sink for acc in (images, pairs) if acc is not None]
+        # trunk, and the real images' own codes stay out where none of --fid --kid --prdc --memorisation wants them; --memorisation
+        # takes the codes and, for its grid, thumbnails of the generated images
+        sinks = [acc.sink for acc in (images, pairs, thumbs) if acc is not None]
 
         def image_sink(real, fake, take):
             for sink in sinks:
                 sink(real, fake, take)
-        whole = bool(args.fid or args.kid or args.prdc)
+        whole = bool(args.fid or args.kid or args.prdc or args.memorisation)
         codes = algo.pool_codes(split_dir, seed=args.manualSeed, want_real=whole, image_sink=image_sink if sinks else None,
                                 trunk=whole or args.scene_fid,
                                 resample_sink=None if pairs is None else pairs.resample_sink,
@@ -218,6 +243,8 @@ def main(argv=None):
                 algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size, codes=codes)
             if args.prdc:
                 algo.prdc(split_dir, seed=args.manualSeed, k_pr=args.prdc_k_pr, k_dc=args.prdc_k_dc, codes=codes)
+            if args.memorisation:                                    # last: its grid re-reads training images
+                algo.memorisation(split_dir, codes=dict(codes, thumbnails=thumbs), **mem_kw)
     elif args.fid:
         algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats)
     elif args.kid:
@@ -229,6 +256,9 @@ def main(argv=None):
                  min_res=args.swd_min_res)
     elif args.scene_fid:
         algo.scene_fid(split_dir, seed=args.manualSeed, min_side=args.scene_fid_min_side)
+    elif args.memorisation:
+        algo.memorisation(split_dir, seed=args.manualSeed, bank_path=args.nn_bank, bank_size=args.nn_bank_size, k=args.nn_k,
+                          show=args.nn_show)
     elif args.msssim:
         algo.msssim(split_dir, seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
     elif cfg.B_VALIDATION:

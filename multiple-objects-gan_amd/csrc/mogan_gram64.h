@@ -1,6 +1,6 @@
 // mogan_gram64.h -- one 64 x 64 tile of an fp64 Gram matrix on v_mfma_f64_16x16x4_f64, written once (internal, like mogan_mma.h
 // and mogan_bn.h) for the evaluation kernels: cov_f64_kernel (mogan_stats.hip), poly3_mmd_kernel (mogan_mmd.hip), row_norm_kernel,
-// knn_kernel and ball_kernel (mogan_knn.hip).  They differ in where their two 64-wide panels come from and in what they do with
+// knn_kernel, cross_kernel and ball_kernel (mogan_knn.hip).  They differ in where their two 64-wide panels come from and in what they do with
 // the tile; the loop between is gram64_tile and nothing else.  DESIGN.md section 9d.
 //
 // acc[i][j] = sum_k a[k][i] b[k][j] for a 4-wave block.  Per chunk of KC = 32 values of k the block stages its two panels in LDS

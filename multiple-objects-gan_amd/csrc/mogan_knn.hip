@@ -26,6 +26,11 @@
 // ball_kernel: a block owns a 64-query stripe and walks the support tiles of its share; a lane counts d2 <= r2 for its 8 rows x
 // R radii in registers over all its tiles, the 16 lanes of a row meet by a fixed butterfly, the two waves of a row in LDS, the
 // shares in ball_finish_kernel in share order (integers: any fixed order gives the same result).
+//
+// cross_kernel: knn_kernel between two sets and with the positions -- a block owns a 64-query stripe and
+// walks the support tiles of its share; the selecting thread keeps the 8 first (d2, i) pairs in registers under the lexicographic
+// order `before` (by distance, equal bits by position), which is a total order on the pairs of a row: the K first of a set of
+// pairs do not depend on how it was partitioned, so cross_merge_kernel merges the shares' lists under the same order.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "mogan_gram64.h"
@@ -172,6 +177,117 @@ __global__ __launch_bounds__(NT) void knn_merge_kernel(const double* __restrict_
 #pragma unroll
     for (int t = 0; t < K_MAX; ++t)
         if (t < K) o[t] = best[t];
+}
+
+// (v, i) comes before (w, j) in a neighbour list: by distance, equal bits by position
+__device__ __forceinline__ bool before(double v, int32_t i, double w, int32_t j) { return v < w || (v == w && i < j); }
+
+// (v, i) into the list of the 8 first pairs under `before` (the caller has seen it before the 8th)
+__device__ __forceinline__ void insert8(double (&best)[K_MAX], int32_t (&at)[K_MAX], double v, int32_t i) {
+    best[K_MAX - 1] = v;
+    at[K_MAX - 1] = i;
+#pragma unroll
+    for (int t = K_MAX - 1; t > 0; --t) {
+        const bool up = before(best[t], at[t], best[t - 1], at[t - 1]);
+        const double lo = up ? best[t] : best[t - 1], hi = up ? best[t - 1] : best[t];
+        const int32_t li = up ? at[t] : at[t - 1], hi_i = up ? at[t - 1] : at[t];
+        best[t - 1] = lo; best[t] = hi;
+        at[t - 1] = li; at[t] = hi_i;
+    }
+}
+
+// an empty slot: after every pair a set can hold (positions end at 2^31 - 2), so a share of fewer than K columns merges as it is
+constexpr int32_t NO_ROW = 2147483647;
+
+template <bool VEC>
+__global__ __launch_bounds__(NT) void cross_kernel(const float* __restrict__ q, long long M, const float* __restrict__ p, long long N,
+                                                   int D, int K, const double* __restrict__ nq, const double* __restrict__ np,
+                                                   double* __restrict__ part, int32_t* __restrict__ part_at) {
+    __shared__ GramLds sm;
+    const int tid = threadIdx.x;
+    const GramLane ln;
+    const long long r0 = (long long)blockIdx.x * CT;
+    const long long T = tiles_of(N);
+    const long long t_lo = T * blockIdx.y / gridDim.y, t_hi = T * (blockIdx.y + 1) / gridDim.y;
+    double na[8];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long long row = ln.row(r0, m, j);
+            na[m * 4 + j] = row < M ? nq[row] : 0.0;
+        }
+    double best[K_MAX];
+    int32_t at[K_MAX];
+#pragma unroll
+    for (int t = 0; t < K_MAX; ++t) {
+        best[t] = INFINITY;
+        at[t] = NO_ROW;
+    }
+    double* dist = &sm[0][0][0];
+    const long long own = r0 + tid;                                    // the query of the selecting thread (tid < 64)
+    f64x4 acc[2][2];
+    for (long long bt = t_lo; bt < t_hi; ++bt) {
+        const long long c0 = bt * CT;
+        gram_tile<VEC>(q, M, r0, p, N, c0, D, false, sm, acc);
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const int cl = ln.col(0, n);
+            const double nb = c0 + cl < N ? np[c0 + cl] : 0.0;
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dist[ln.row(0, m, j) * LDD + cl] = sqdist(na[m * 4 + j], nb, acc[m][n][j]);
+        }
+        __syncthreads();
+        if (tid < CT) {
+            const long long lim = N - c0 < CT ? N - c0 : CT;
+            for (int c = 0; c < (int)lim; ++c) {
+                const double v = dist[tid * LDD + c];
+                const int32_t i = (int32_t)(c0 + c);
+                if (before(v, i, best[K_MAX - 1], at[K_MAX - 1])) insert8(best, at, v, i);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < CT && own < M) {
+        const size_t o = ((size_t)blockIdx.y * (size_t)M + (size_t)own) * K;
+#pragma unroll
+        for (int t = 0; t < K_MAX; ++t)
+            if (t < K) {
+                part[o + t] = best[t];
+                part_at[o + t] = at[t];
+            }
+    }
+}
+
+__global__ __launch_bounds__(NT) void cross_merge_kernel(const double* __restrict__ part, const int32_t* __restrict__ part_at,
+                                                         long long M, int K, int shares, double* __restrict__ d2,
+                                                         int32_t* __restrict__ idx) {
+    const long long row = (long long)blockIdx.x * NT + threadIdx.x;
+    if (row >= M) return;
+    double best[K_MAX];
+    int32_t at[K_MAX];
+#pragma unroll
+    for (int t = 0; t < K_MAX; ++t) {
+        best[t] = INFINITY;
+        at[t] = NO_ROW;
+    }
+    for (int s = 0; s < shares; ++s) {
+        const size_t o = ((size_t)s * (size_t)M + (size_t)row) * K;
+        for (int t = 0; t < K; ++t) {
+            const double v = part[o + t];
+            const int32_t i = part_at[o + t];
+            if (before(v, i, best[K_MAX - 1], at[K_MAX - 1])) insert8(best, at, v, i);
+        }
+    }
+    const size_t o = (size_t)row * K;
+#pragma unroll
+    for (int t = 0; t < K_MAX; ++t)
+        if (t < K) {
+            d2[o + t] = best[t];
+            idx[o + t] = at[t];
+        }
 }
 
 // SIDE 0: the radius belongs to the support point (r2 (N, R), by column); SIDE 1: to the query (r2 (M, R), by row)
@@ -337,6 +453,38 @@ int mogan_ball_count_f64(const float* q, long long M, const float* p, long long 
     const long long MR = M * R;
     hipLaunchKernelGGL(ball_finish_kernel, dim3((unsigned)((MR + NT - 1) / NT)), dim3(NT), 0, stream, (const int32_t*)part, MR,
                        shares, count);
+    return ok_launch();
+}
+
+size_t mogan_knn_cross_ws_bytes(long long M, long long N, int K) {
+    if (K < 1 || K > K_MAX || M < 1 || N < (long long)K || M > N_MAX || N > N_MAX) return 0;
+    const size_t lists = (size_t)shares_of(M, N) * (size_t)M * (size_t)K;
+    return ((size_t)M + (size_t)N + lists) * sizeof(double) + up8(lists * sizeof(int32_t));
+}
+
+int mogan_knn_cross_f64(const float* q, long long M, const float* p, long long N, int D, int K, double* d2, int32_t* idx, void* ws,
+                        size_t ws_bytes, hipStream_t stream) {
+    if (!q || !p || !d2 || !idx || K < 1 || K > K_MAX || M < 1 || N < (long long)K || M > N_MAX || N > N_MAX || D < 1 || D > D_MAX)
+        return MOGAN_ERR_SHAPE;
+    if (!ws || ((uintptr_t)ws & 7) != 0 || ws_bytes < mogan_knn_cross_ws_bytes(M, N, K)) return MOGAN_ERR_WS;
+    const bool vec = D % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)p & 15) == 0;
+    const int shares = shares_of(M, N);
+    double* nq = (double*)ws;
+    double* np = nq + M;
+    double* part = np + N;
+    int32_t* part_at = (int32_t*)(part + (size_t)shares * (size_t)M * (size_t)K);
+    if (launch_norms(q, M, D, nq, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
+    if (launch_norms(p, N, D, np, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
+    const dim3 grid((unsigned)tiles_of(M), shares);
+    if (vec)
+        hipLaunchKernelGGL(cross_kernel<true>, grid, dim3(NT), 0, stream, q, M, p, N, D, K, (const double*)nq, (const double*)np,
+                           part, part_at);
+    else
+        hipLaunchKernelGGL(cross_kernel<false>, grid, dim3(NT), 0, stream, q, M, p, N, D, K, (const double*)nq, (const double*)np,
+                           part, part_at);
+    if (ok_launch() != 0) return MOGAN_ERR_LAUNCH;
+    hipLaunchKernelGGL(cross_merge_kernel, dim3((unsigned)((M + NT - 1) / NT)), dim3(NT), 0, stream, (const double*)part,
+                       (const int32_t*)part_at, M, K, shares, d2, idx);
     return ok_launch();
 }
 

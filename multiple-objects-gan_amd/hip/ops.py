@@ -1867,6 +1867,28 @@ def knn_sqdist(x, K):
     return out
 
 
+def knn_cross(q, p, K):
+    """For every row of fp32 queries q (M, D) its K nearest rows of fp32 codes p (N, D): (d2 (M, K) fp64, idx (M, K) int32) on the
+    device, ascending by squared Euclidean distance, equal bits by position -- the lexicographic order of (d2, i)
+    (mogan_knn_cross_f64; the distances are knn_sqdist's and ball_counts', bit for bit).  1 <= K <= min(8, N).  No gradient.
+    Nothing is converted or copied for the caller: a wrong dtype or rank, a width mismatch, a non-contiguous input, another device,
+    a K out of range are a ValueError."""
+    _codes("knn_cross", (("q", q), ("p", p)))
+    K = int(K)
+    M, N, D = q.shape[0], p.shape[0], q.shape[1]
+    if K < 1 or K > 8 or K > N:
+        raise ValueError("knn_cross: 1 <= K <= min(8, N) expected, got K = %d for %d rows of p" % (K, N))
+    q, p = q.detach(), p.detach()
+    pq, pp = ptr(q), ptr(p)
+    ws, ws_bytes, own = _scratch(q.device, int(lib.load().mogan_knn_cross_ws_bytes(M, N, K)))
+    d2 = torch.empty((M, K), dtype=torch.float64, device=q.device)
+    idx = torch.empty((M, K), dtype=torch.int32, device=q.device)
+    call("mogan_knn_cross_f64", pq, M, pp, N, D, K, ptr(d2), ptr(idx), ws, ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(q.device))
+    return d2, idx
+
+
 def ball_counts(q, p, r2, side="support"):
     """count (M, R) int32 on the device, count[j, c] = #{ i : d2(q_j, p_i) <= r2[., c] } for fp32 queries q (M, D), fp32 support
     points p (N, D) and fp64 squared radii r2 (mogan_ball_count_f64; the distances are knn_sqdist's, bit for bit).  side
