@@ -729,7 +729,7 @@ int mogan_retrieval_rank(const float* code, const float* pos, const float* bank,
 
 /* fp64 moments of a set of feature codes: what the Frechet distance is computed from (the reference has no code for it --
  * DESIGN.md section 9d; csrc/mogan_stats.hip).  x is fp32 (N, D), dense, widened exactly; mean (D) and cov (D, D) are fp64 -- with
- * the sums of mogan_poly3_mmd_f64, the radii of mogan_knn_sqdist_f64, the distances of mogan_knn_cross_f64, the moments and sums of mogan_swd_* and the terms of mogan_ssim_level_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
+ * the sums of mogan_poly3_mmd_f64, the radii of mogan_knn_sqdist_f64, the distances of mogan_knn_cross_f64, the moments and sums of mogan_swd_*, the terms of mogan_ssim_level_f64 and the twiddle table and sums of mogan_radial_power_f64 below the only fp64 tensors of this ABI.  No workspace, no atomics, nothing handed from
  * workgroup to workgroup: every sum over n runs in one fixed order, so the same inputs give the same bits on every call.
  *   mean[j]   = (sum_n (double)x[n][j]) / N
  *   cov[i][j] = (sum_n (x[n][i] - mean[i]) (x[n][j] - mean[j])) / (N - 1)       (numpy.cov(x, rowvar=False))
@@ -900,6 +900,34 @@ int mogan_ssim_level_f64(const float* a, const float* b, long long P, int C, int
  * R C OH OW above 2^31 - 1.  R = 0 returns 0 without a launch. */
 int mogan_roi_resize(const float* x, int B, int C, int H, int W, const float* boxes, const int* image_index, long long R,
                      float* y, int OH, int OW, hipStream_t stream);
+
+/* Radial power spectrum of a batch of images: what the spectral-artefact score is computed from (the azimuthally averaged power
+ * spectrum of Durall et al. 2020, Dzanic et al. 2020, Schwarz et al. 2021; csrc/mogan_spectrum.hip;
+ * attngan/spectrum.py has the whole definition; the reference has no code for it).  x (B, C, S, S) fp32, dense; weight (C) and
+ * window (S, or NULL for all ones) fp32; twiddle S / 2 pairs (cos, -sin)(2 pi k / S) fp64, built by the host and 16-byte aligned --
+ * the device calls no trigonometric function; bins (S, S / 2 + 1) int32 over the half plane v in [0, S / 2], an entry < 0 or
+ * >= n_bins leaves its frequency out; out (B, n_bins) fp64.  All on the device.  Per image b, everything after the loads in fp64:
+ *     y[i][j]   = (sum_c weight[c] x[b][c][i][j]) (window[i] window[j])               (c ascending)
+ *     F[u][v]   = sum_ij y[i][j] exp(-2 pi i (u i + v j) / S)                           (unnormalised)
+ *     out[b][k] = sum over (u, v) of the half plane with bins[u][v] = k of m(v) |F[u][v]|^2,    m = 1 for v in {0, S / 2}, else 2
+ *   (the Hermitian symmetry of a real plane: the sum over the full plane of a table that is symmetric under (u, v) -> (-u, -v)).
+ *   Three launches per round of at most 64 images: radix-2 transforms of the rows in LDS, the half spectrum to the workspace with
+ *   its columns contiguous; transforms of a group of columns in LDS, one thread per bin adding the group's members in (column, u)
+ *   order, n_bins partial sums per group to the workspace; a last sum over the groups in index order.  No atomics, no 2-D power
+ *   plane in memory, and every workgroup works on ONE image:
+ *     (a) the same inputs give the same bits on every call;
+ *     (b) row b of out depends on image b only -- the same bits at B = 1 and at any position of any batch;
+ *     (c) an all-zero image gives exactly 0.0 in every bin.
+ *   Every element of out is written (0.0 for a bin without members).  The workspace is required, 16-byte aligned:
+ *   mogan_radial_power_ws_bytes(B, S) = min(B, 64) ((S / 2 + 1) S 16 + G 2048), G = ceil((S / 2 + 1) / min(S / 2 + 1, 2048 / S))
+ *   column groups (0 for arguments the call rejects): it does not grow with B past 64 images.  MOGAN_ERR_WS where ws is NULL,
+ *   misaligned or shorter, nothing launched.
+ *   B >= 1, 1 <= C <= 4, S a power of two in [8, 256], 1 <= n_bins <= 256, B C S S <= 2^31 - 1.
+ * MOGAN_ERR_SHAPE before any HIP call (and before the workspace is looked at): a NULL pointer (window and ws apart), a misaligned
+ * twiddle or out, any dimension outside the ranges above. */
+size_t mogan_radial_power_ws_bytes(int B, int S);
+int mogan_radial_power_f64(const float* x, int B, int C, int S, const float* weight, const float* window, const double* twiddle,
+                           const int* bins, int n_bins, double* out, void* ws, size_t ws_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,8 @@
-"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9j).
+"""coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9k).
 
 `CheckpointEvaluation` is the base of `trainer.condGANTrainer` that holds every path which reads a finished checkpoint instead of
 training one: `sampling` / `sample` (images), `r_precision`, and `pool_codes` with the three scores `fid` / `kid` / `prdc` that share
-its pass, `swd` and `msssim`, which take the pass's images instead of their codes, and `scene_fid`, which takes the images and
+its pass, `swd`, `msssim` and `spectrum`, which take the pass's images instead of their codes, and `scene_fid`, which takes the images and
 their boxes and runs the trunk on the objects, and `memorisation`, which searches the pass's codes in a bank of the TRAIN split's.  It needs `self.device`, `self.data_loader`,
 `self.n_words` and `self.ixtoword` of the trainer and nothing of the train step.  What these paths have in common is written
 once here: the NET_G guard and the save-directory rule (`net_g_missing`, `eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
@@ -618,6 +618,58 @@ class CheckpointEvaluation(object):
         print("MS-SSIM (%d scales; mean +- std over pairs): %s -> %s/msssim.json"
               % (images.scales, ", ".join("%s %.4f +- %.4f (%d pairs)" % (k, out[k]["mean"], out[k]["std"], out[k]["pairs"])
                                           for k in ("real", "generated", "same_caption") if k in out), save_dir))
+        return out
+
+    def spectrum_images(self, num_samples=30000, seed=100, window="hann"):
+        """The accumulator spectrum() fills: attngan/spectrum.RadialSpectrum for the tree's final resolution and as many images as
+        the pass will see, whose `sink` is the (real, fake, take) callable pool_codes' image_sink wants.  A caller that shares one
+        pass between spectrum() and other scores makes it first and hands it to both (main.py)."""
+        from .spectrum import RadialSpectrum
+        size = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1)
+        images = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        return RadialSpectrum(size, 3, images, window, self.device, seed=seed)
+
+    def spectrum(self, split_dir, num_samples=30000, seed=100, window="hann", images=None):
+        """Radial power spectrum (the azimuthally averaged power spectrum of Durall et al. 2020, Dzanic et al. 2020, Schwarz et al.
+        2021; attngan/spectrum.py has the definition) of the real 256x256 images against one generated image per
+        caption of the checkpoint TRAIN.NET_G -- exactly the images pool_codes and r_precision see under `seed`: the one score that
+        looks at the images in the frequency domain, where the generator's nearest-neighbour upsamplings leave grids and
+        checkerboards of period 2, 4 and 8 that a random-init trunk can miss and SWD cannot place.  It reads the images
+        themselves: no image encoder is involved, and pool_codes runs without one (trunk=False) unless the caller shares a pass:
+        `images` is then the accumulator of spectrum_images() whose sink that pass has fed.  The transform and the sums per bin
+        run in hip/ops.radial_power, one call per side and batch, fp64; the per-image sums are read back once.  The score draws
+        nothing.  Writes <NET_G minus .pth>/<split>/spectrum.json and returns its content."""
+        from .spectrum import window_name
+        if net_g_missing():
+            return None
+        if images is None:
+            images = self.spectrum_images(num_samples, seed, window)
+            self.pool_codes(split_dir, num_samples, seed, want_real=False, image_sink=images.sink, trunk=False)
+        elif (images.seed, images.window) != (int(seed), window_name(window)):
+            raise ValueError("spectrum: the images handed over were scored under other parameters (seed, window) = %s"
+                             % ((images.seed, images.window),))
+        if images.n < 1:
+            raise ValueError("spectrum: the data loader gave no batch")
+        out = images.result()
+        n = out.pop("n")
+        out.update({"size": images.size, "window": images.window, "n_real": n, "n_fake": n, "seed": int(seed),
+                    "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E,
+                    "note": "Radial (azimuthally averaged) power spectrum of the luminance of the real and the generated images, in dB "
+                            "per bin of integer radius, with the log-spectral distance lsd_db, the ratio of the power above a "
+                            "quarter of the sampling frequency hf_db (positive: too much fine-scale power -- noise, grids; negative: "
+                            "blur), the spectral slopes and the bin of the largest excess with its period in pixels: trunk-free -- "
+                            "no image encoder is involved.  Every figure depends on the window (%s) and is comparable under the "
+                            "same window only.  The images enter as fp32 in [-1, 1], not quantised to 8 bits.  Bins beyond S / 2 "
+                            "cover partial rings only (the corners of the frequency square; the period-2 checkerboard is the last "
+                            "bin)." % images.window})
+        save_dir = eval_save_dir(split_dir)
+        write_json(save_dir, "spectrum", out)
+        def shown(v, form):                                     # a figure none of whose bins holds power is None
+            return "n/a" if v is None else form % v
+        print("Spectrum (%d real, %d generated images; window %s): LSD %.4f dB, HF %s dB, slopes %s / %s dB per decade, peak "
+              "%+.2f dB at bin %d (period %.2f px) -> %s/spectrum.json"
+              % (n, n, images.window, out["lsd_db"], shown(out["hf_db"], "%+.4f"), shown(out["slope_real"], "%.2f"),
+                 shown(out["slope_fake"], "%.2f"), out["peak"]["excess_db"], out["peak"]["bin"], out["peak"]["period"], save_dir))
         return out
 
     def scene_fid_objects(self, num_samples=30000, seed=100, min_side=1):

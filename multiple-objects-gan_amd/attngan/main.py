@@ -89,6 +89,14 @@ def parse_args(argv=None):
     parser.add_argument('--msssim_scales', type=int, default=5, metavar='N', help='with --msssim: number of scales (1..5)')
     parser.add_argument('--msssim_no_resample', action='store_true',
                         help='with --msssim: leave the second image per caption, and so the same_caption figure, out')
+    parser.add_argument('--spectrum', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): radial power spectrum of the real against the generated images '
+                             '(condGANTrainer.spectrum: no image encoder involved; the log-spectral distance, the high-frequency '
+                             'excess, the spectral slopes and the period of the largest excess -- the grids and checkerboards of the '
+                             'up-convolutions) -> <NET_G minus .pth>/<split>/spectrum.json; with any of --fid --kid --prdc --swd '
+                             '--msssim --scene_fid --memorisation all take one pass; not together with --sampling or --r_precision')
+    parser.add_argument('--spectrum_window', type=str, default='hann', choices=('hann', 'none'),
+                        help='with --spectrum: the window applied before the transform (every figure depends on it)')
     parser.add_argument('--scene_fid', action='store_true',
                         help='evaluation (TRAIN.FLAG False): object-level Frechet distance (SceneFID) -- every object of the data cut '
                              'at its box out of the real and out of the generated image, resized to the trunk\'s input and scored as '
@@ -118,6 +126,8 @@ def parse_args(argv=None):
         parser.error('--nn_k must be in 1..8')
     if args.nn_show < 0 or (args.nn_bank_size is not None and args.nn_bank_size < 2):
         parser.error('--nn_show must not be negative and --nn_bank_size must be 2 at least')
+    if args.spectrum and (args.sampling or args.r_precision):
+        parser.error('--spectrum cannot be combined with --sampling or --r_precision')
     if args.scene_fid and (args.sampling or args.r_precision):
         parser.error('--scene_fid cannot be combined with --sampling or --r_precision')
     if args.msssim and (args.sampling or args.r_precision):
@@ -182,7 +192,7 @@ def main(argv=None):
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
     with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc or args.swd
-                                 or args.msssim or args.scene_fid or args.memorisation)
+                                 or args.msssim or args.spectrum or args.scene_fid or args.memorisation)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -205,7 +215,7 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
-    elif args.fid + args.kid + args.prdc + args.swd + args.msssim + args.scene_fid + args.memorisation > 1:
+    elif args.fid + args.kid + args.prdc + args.swd + args.msssim + args.spectrum + args.scene_fid + args.memorisation > 1:
         from .evaluate import Thumbnails
         mem_kw = dict(seed=args.manualSeed, bank_path=args.nn_bank, bank_size=args.nn_bank_size, k=args.nn_k, show=args.nn_show)
         thumbs = Thumbnails() if args.memorisation and args.nn_show > 0 and cfg.TRAIN.NET_G != '' else None
@@ -216,11 +226,13 @@ def main(argv=None):
         swd_kw = dict(seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
                       min_res=args.swd_min_res)
         images = algo.swd_images(**swd_kw) if args.swd and cfg.TRAIN.NET_G != '' else None
-        # one pass over the loader and the trunk for all; --swd and --msssim take the pass's images where the others take their
-        # codes, and the trunk stays out where only those two are asked for; --scene_fid takes the images, their boxes and the
+        sp_kw = dict(seed=args.manualSeed, window=args.spectrum_window)
+        spectra = algo.spectrum_images(**sp_kw) if args.spectrum and cfg.TRAIN.NET_G != '' else None
+        # one pass over the loader and the trunk for all; --swd, --msssim and --spectrum take the pass's images where the others take
+        # their codes, and the trunk stays out where only those three are asked for; --scene_fid takes the images, their boxes and the
         # trunk, and the real images' own codes stay out where none of --fid --kid --prdc --memorisation wants them; --memorisation
         # takes the codes and, for its grid, thumbnails of the generated images
-        sinks = [acc.sink for acc in (images, pairs, thumbs) if acc is not None]
+        sinks = [acc.sink for acc in (images, pairs, spectra, thumbs) if acc is not None]
 
         def image_sink(real, fake, take):
             for sink in sinks:
@@ -237,6 +249,8 @@ def main(argv=None):
                 algo.swd(split_dir, images=images, **swd_kw)
             if pairs is not None:
                 algo.msssim(split_dir, images=pairs, **ms_kw)
+            if spectra is not None:
+                algo.spectrum(split_dir, images=spectra, **sp_kw)
             if args.fid:
                 algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats, codes=codes)
             if args.kid:
@@ -261,6 +275,8 @@ def main(argv=None):
                           show=args.nn_show)
     elif args.msssim:
         algo.msssim(split_dir, seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
+    elif args.spectrum:
+        algo.spectrum(split_dir, seed=args.manualSeed, window=args.spectrum_window)
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:

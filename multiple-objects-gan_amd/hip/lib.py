@@ -162,6 +162,8 @@ SIGNATURES = {
     "mogan_ssim_level_ws_bytes": [L, I, I, I],
     "mogan_ssim_level_f64": [P, P, L, I, I, P, I, P, P, P, P, Z, P],
     "mogan_roi_resize": [P, I, I, I, I, P, P, L, P, I, I, P],
+    "mogan_radial_power_ws_bytes": [I, I],
+    "mogan_radial_power_f64": [P, I, I, I, P, P, P, P, I, P, P, Z, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }
@@ -192,7 +194,7 @@ class TailArgs(ctypes.Structure):               # MoganTailArgs
 _RESTYPE = {"mogan_bn_ws_bytes": Z, "mogan_upconv3x3_ws_bytes": Z, "mogan_pk_weight_bytes": Z, "mogan_pk_panel_bytes": Z,
             "mogan_wino_prep_bytes": Z, "mogan_conv_prep_bytes": Z, "mogan_poly3_mmd_ws_bytes": Z,
             "mogan_knn_sqdist_ws_bytes": Z, "mogan_ball_count_ws_bytes": Z, "mogan_swd_moments_ws_bytes": Z,
-            "mogan_ssim_level_ws_bytes": Z, "mogan_knn_cross_ws_bytes": Z}
+            "mogan_ssim_level_ws_bytes": Z, "mogan_knn_cross_ws_bytes": Z, "mogan_radial_power_ws_bytes": Z}
 _ERRORS = {-1: "MOGAN_ERR_SHAPE", -2: "MOGAN_ERR_LAUNCH", -3: "MOGAN_ERR_WS"}
 
 _lib = None

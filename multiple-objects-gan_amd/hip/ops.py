@@ -2159,6 +2159,66 @@ def roi_resize(x, boxes, image_index, OH, OW, out=None):
     return out
 
 
+_twiddles = {}
+
+
+def twiddle_table(S):
+    """The S / 2 pairs (cos, -sin)(2 pi k / S) of mogan_radial_power_f64 as a (S / 2, 2) fp64 numpy array: numpy's cos and sin of
+    the fp64 angle 2 pi k / S.  The device takes them as they are, so a CPU oracle can start from the same constants."""
+    import numpy as np
+    ang = 2.0 * np.pi * np.arange(int(S) // 2, dtype=np.float64) / float(S)
+    return np.ascontiguousarray(np.stack([np.cos(ang), -np.sin(ang)], axis=1))
+
+
+def radial_power(x, weight, window, bins, n_bins, out=None):
+    """Per image the sums of |F|^2 over the bins of a table (mogan_radial_power_f64; attngan/spectrum.py has the definition): fp32 x
+    (B, C, S, S) with C in 1..4 and S a power of two in [8, 256], fp32 weight (C,), fp32 window (S,) or None (all ones), int32 bins
+    (S, S / 2 + 1) over the half plane v in [0, S / 2] (an entry < 0 or >= n_bins leaves its frequency out), all on x's device ->
+    (B, n_bins) fp64 on the device, out[b, k] = sum over the table's members of bin k of m(v) |F_b[u, v]|^2, F the unnormalised DFT of
+    (sum_c weight[c] x[b, c]) window[i] window[j], m = 1 for v in {0, S / 2} and 2 otherwise.  fp64 after the loads; the same bits on
+    every call, a row's bits depend on its image only, a zero image gives exactly 0.0.  `out`, where given, is a dense (B, n_bins)
+    fp64 tensor on x's device (rows of a larger buffer, for one) and is returned.  The twiddle table is built once per (S, device).
+    No gradient.  Nothing is converted or copied for the caller: a wrong dtype, rank, device, contiguity or size is a ValueError."""
+    x = _dense_f32("radial_power", "x", x, 4)
+    weight = _dense_f32("radial_power", "weight", weight, 1)
+    if window is not None:
+        window = _dense_f32("radial_power", "window", window, 1)
+    B, C, S, n_bins = x.shape[0], x.shape[1], x.shape[2], int(n_bins)
+    if C > 4 or x.shape[3] != S or S < 8 or S > 256 or S & (S - 1) or x.numel() > 2 ** 31 - 1:
+        raise ValueError("radial_power: x (B, 1..4, S, S) with S a power of two in [8, 256] and fewer than 2^31 elements expected, "
+                         "got %s" % (tuple(x.shape),))
+    if weight.shape[0] != C:
+        raise ValueError("radial_power: one weight per channel expected, got %d for %d channels" % (weight.shape[0], C))
+    if window is not None and window.shape[0] != S:
+        raise ValueError("radial_power: a window of S = %d values expected, got %d" % (S, window.shape[0]))
+    if (not torch.is_tensor(bins) or bins.dtype != torch.int32 or tuple(bins.shape) != (S, S // 2 + 1) or not bins.is_contiguous()):
+        raise ValueError("radial_power: bins must be a contiguous int32 (%d, %d) table, got %s %s"
+                         % (S, S // 2 + 1, getattr(bins, "dtype", type(bins)), tuple(getattr(bins, "shape", ()))))
+    if not 1 <= n_bins <= 256:
+        raise ValueError("radial_power: 1 <= n_bins <= 256 expected, got %d" % n_bins)
+    for name, t in (("weight", weight), ("window", window), ("bins", bins), ("out", out if torch.is_tensor(out) else None)):
+        if t is not None and t.device != x.device:
+            raise ValueError("radial_power: x and %s must be on one device (%s, %s)" % (name, x.device, t.device))
+    if x.device.type == "meta":
+        raise ValueError("radial_power: x is a meta tensor")
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != (B, n_bins) or not out.is_contiguous():
+            raise ValueError("radial_power: out must be a dense fp64 %s tensor, got %s %s"
+                             % ((B, n_bins), getattr(out, "dtype", type(out)), tuple(getattr(out, "shape", ()))))
+    px, pw, pn, pb = ptr(x), ptr(weight), ptr(window), ptr(bins.detach())      # (a host tensor raises here, before any upload)
+    key = (S, x.device)
+    tw = _twiddles.get(key)
+    if tw is None:
+        tw = _twiddles[key] = torch.from_numpy(twiddle_table(S)).to(x.device)
+    ws, ws_bytes, own = _scratch(x.device, int(lib.load().mogan_radial_power_ws_bytes(B, S)))
+    if out is None:
+        out = torch.empty((B, n_bins), dtype=torch.float64, device=x.device)
+    call("mogan_radial_power_f64", px, B, C, S, pw, pn, ptr(tw), pb, n_bins, ptr(out), ws, ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(x.device))
+    return out
+
+
 class ScalarSumFn(torch.autograd.Function):
     """sum_k w_k * x_k over up to 8 zero-dim device scalars in ONE launch (forward) / one launch (backward): the loss sums
     of miscc/losses.py:169-174,203,221 and trainer.py:330 otherwise cost a chain of 0-dim aten kernels each way."""
