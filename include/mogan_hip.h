@@ -273,7 +273,15 @@ int mogan_conv2d_wgrad_pk(const float* dy, const float* x, float* dw, int B, int
  *             miscc/losses.py:136-174 --: ONE convolution over all B images (the weights stream once), batch statistics per
  *             group (stats = mean[groups][Cout] | invstd[groups][Cout]), running statistics updated group after group in that
  *             order, d gamma / d beta = the groups' sums.  B / groups * OH*OW <= 2048.
- * Same arithmetic as mogan_bn_stats / mogan_bn_act_fwd / mogan_bn_act_bwd (fp64 sums). */
+ * Same arithmetic as mogan_bn_stats / mogan_bn_act_fwd / mogan_bn_act_bwd (fp64 sums).
+ * Nullable: x or xpanel (not both), rmean, rvar, zpanel (forward); dgamma, dbeta, dx -- and with dx NULL also wpk_dgrad and ws
+ * (backward).  Every rejection precedes the first launch, so a declined call has written nothing: MOGAN_ERR_SHAPE for B <= 0,
+ * groups outside 1..2, B % groups, Cin % 32, Cout % 32, stride <= 0, an empty output map, B / groups * OH*OW > 2048 / groups, an
+ * activation other than NONE / RELU / LRELU, KH*KW > 25, a NULL required pointer (forward: wpk, gamma, beta, y, stats, z, and x
+ * with xpanel; backward: dz, y, stats, gamma, beta, dy) and, where dx is wanted, KH, KW, Hs or Ws no multiple of the stride or
+ * Cin <= 0; MOGAN_ERR_WS for a workspace that is NULL or does not hold the panel that has to be packed (forward without xpanel:
+ * B*Hs*Ws*Cin*6 bytes, backward with dx: B*OH*OW*Cout*6, each rounded up to 256) and, with dx, a NULL wpk_dgrad.  Behind the
+ * panel the forward keeps its K-split slabs (4*B*Cout*OH*OW bytes each); room for fewer than two only disables the split. */
 size_t mogan_pk_panel_bytes(int B, int C, int HW);
 int mogan_deep_block_eligible(int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW, int stride, int ph, int pw, int act,
                               int groups);

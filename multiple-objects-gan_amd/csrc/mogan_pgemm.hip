@@ -912,6 +912,16 @@ static int pk_dgrad_from_panel(const void* panel, const void* wpk, float* dx, in
 }
 }  // namespace
 
+// what pk_fwd_from_panel (dgrad = 0) / pk_dgrad_from_panel (dgrad = 1) would decline, for callers that launch before them
+static bool deep_geom_ok(int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW, int stride, int OH, int OW, int dgrad) {
+    PkGeom g;
+    if (!pk_geom(Cout, Cin, KH, KW, stride, dgrad, g) || B <= 0 || Hs <= 0 || Ws <= 0 || OH <= 0 || OW <= 0) return false;
+    if (dgrad && (Hs % stride || Ws % stride)) return false;
+    const unsigned long long pbytes = dgrad ? (unsigned long long)B * OH * OW * Cout * 6 : (unsigned long long)B * Hs * Ws * Cin * 6;
+    const long long out = dgrad ? (long long)B * Cin * Hs * Ws : (long long)B * Cout * OH * OW;
+    return pbytes < (1ull << 32) && out < (1ll << 31);
+}
+
 extern "C" {
 
 int mogan_conv2d_fwd_pk(const float* x, const void* wpk, float* y, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW,
@@ -1067,13 +1077,17 @@ int mogan_deep_block_eligible(int B, int Cin, int Hs, int Ws, int Cout, int KH, 
 }
 
 // B = all images of the tensor; groups > 1: `groups` BatchNorm calls on consecutive B / groups images each (stats: [2][groups][Cout])
+// Both entry points answer every rejection -- dimensions, the panel formats' geometry (pk_geom: the forward's, and the data
+// gradient's where dx is wanted), required pointers, the workspace -- before their first launch: a declined call has written
+// nothing.  Nullable: x or xpanel (not both), rmean, rvar, zpanel; dgamma, dbeta, dx (and with dx NULL also wpk_dgrad and ws).
 int mogan_deep_conv_bn_act_fwd(const float* x, const void* xpanel, const void* wpk, const float* gamma, const float* beta,
                                float* rmean, float* rvar, float* y, float* stats, float* z, void* zpanel, int B, int Cin, int Hs,
                                int Ws, int Cout, int KH, int KW, int stride, int ph, int pw, float eps, float momentum, int act,
                                float slope, int groups, void* ws, size_t ws_bytes, hipStream_t stream) {
     if (B <= 0 || groups < 1 || B % groups || Cin <= 0 || Cin % 32 || Hs <= 0 || Ws <= 0 || stride <= 0) return MOGAN_ERR_SHAPE;
     const int OH = (Hs + 2 * ph - KH) / stride + 1, OW = (Ws + 2 * pw - KW) / stride + 1;
-    if (OH <= 0 || OW <= 0 || !tail_ok(B / groups, Cout, OH * OW, act, groups) || !gamma || !beta || !y || !stats || !z)
+    if (OH <= 0 || OW <= 0 || !tail_ok(B / groups, Cout, OH * OW, act, groups) || !gamma || !beta || !y || !stats || !z || !wpk ||
+        (!x && !xpanel) || !deep_geom_ok(B, Cin, Hs, Ws, Cout, KH, KW, stride, OH, OW, 0))
         return MOGAN_ERR_SHAPE;
     char* w0 = (char*)ws; size_t wn = ws_bytes;
     if (!xpanel) {                       // the producer of x handed over no panel: pack it here
@@ -1100,12 +1114,14 @@ int mogan_deep_conv_bn_act_bwd(const float* dz, const float* y, const float* sta
                                const void* wpk_dgrad, float* dy, float* dgamma, float* dbeta, int accumulate, float* dx, int B,
                                int Cin, int Hs, int Ws, int Cout, int KH, int KW, int stride, int ph, int pw, int act, float slope,
                                int groups, void* ws, size_t ws_bytes, hipStream_t stream) {
-    if (B <= 0 || stride <= 0 || groups < 1 || B % groups) return MOGAN_ERR_SHAPE;
+    if (B <= 0 || stride <= 0 || groups < 1 || B % groups || Cin % 32 || KH <= 0 || KW <= 0 || KH * KW > 25) return MOGAN_ERR_SHAPE;
     const int OH = (Hs + 2 * ph - KH) / stride + 1, OW = (Ws + 2 * pw - KW) / stride + 1;
     if (OH <= 0 || OW <= 0 || !tail_ok(B / groups, Cout, OH * OW, act, groups) || !dz || !y || !stats || !gamma || !beta || !dy)
         return MOGAN_ERR_SHAPE;
     const size_t pbytes = up256((size_t)B * OH * OW * Cout * 6);
     const bool want_dx = dx != nullptr;
+    // the data gradient's geometry BEFORE the tail kernel: that one writes dy and adds into dgamma / dbeta
+    if (want_dx && !deep_geom_ok(B, Cin, Hs, Ws, Cout, KH, KW, stride, OH, OW, 1)) return MOGAN_ERR_SHAPE;
     if (want_dx && (!ws || ws_bytes < pbytes || !wpk_dgrad)) return MOGAN_ERR_WS;
     TailBwdP t{};
     t.dz = dz; t.y = y; t.mean = stats; t.invstd = stats + (size_t)groups * Cout; t.gamma = gamma; t.beta = beta; t.dy = dy;

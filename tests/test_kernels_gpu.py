@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from conv_cases import CONV_CASES, PK_CASES, PK_WGRAD_CASES, UP_CASES
+from deep_cases import _panel_decode, _run_tail, _tail_member
 from helpers import ROOT, det_array, load_pkg, max_abs, rel_l2
 from oracle import attngan_oracle as O
 
@@ -1333,37 +1334,7 @@ def test_deep_blocks_hand_over_their_pixel_panel():
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Frozen trunk on pixel panels: mogan_pk_group (grouped packed-operand GEMM) + mogan_panel_tail_group, straight through the C ABI
-def _panel_decode(panel, Q, Cp):
-    """pixel panel bytes -> (Q, Cp) fp32: the three bf16 pieces of every value add up to it exactly (csrc/mogan_mma.h)"""
-    p = panel.view(torch.bfloat16).view(Q, Cp // 32, 3, 32).float()
-    return (p[:, :, 0] + p[:, :, 1] + p[:, :, 2]).reshape(Q, Cp)
-
-
-def _tail_member(B, n, H, W, srcs, dst=None, dst_bs=0, panel=None, Cp=0, c0=0, scale=None, shift=None, relu=0, box=0, add=None,
-                 add_bs=0, mask=None, mask_bs=0):
-    a = lib.TailArgs()
-    for j, (t, bs, slab, ns) in enumerate(srcs):
-        a.src[j], a.src_bs[j], a.src_slab[j], a.src_nsplit[j] = t, bs, slab, ns
-    a.nsrc, a.B, a.n, a.H, a.W, a.relu, a.box = len(srcs), B, n, H, W, relu, box
-    if dst is not None:
-        a.dst, a.dst_bs = dst, dst_bs
-    if panel is not None:
-        a.panel, a.CGp, a.cg0 = panel, Cp // 32, c0 // 32
-    if scale is not None:
-        a.scale, a.shift = scale, shift
-    if add is not None:
-        a.add, a.add_bs = add, add_bs
-    if mask is not None:
-        a.mask, a.mask_bs = mask, mask_bs
-    return a
-
-
-def _run_tail(members):
-    import ctypes
-    arr = (lib.TailArgs * len(members))(*members)
-    lib.call("mogan_panel_tail_group", len(members), ctypes.cast(arr, ctypes.c_void_p), lib.stream_ptr())
-
-
+# (the panel helpers live in tests/deep_cases.py, shared with tests/test_deep_entry_points_gpu.py)
 PANEL_CONVS = [  # Cin, c0 (slice offset in a wider panel), Cp_total, H, W, Cout, KH, KW, stride, ph, pw
     (48, 32, 128, 9, 11, 64, 5, 5, 1, 2, 2), (64, 0, 64, 17, 17, 40, 1, 7, 1, 0, 3), (96, 64, 192, 17, 17, 96, 7, 1, 1, 3, 0),
     (160, 0, 160, 8, 8, 200, 3, 3, 1, 1, 1), (288, 0, 288, 13, 13, 72, 3, 3, 2, 0, 0), (192, 0, 224, 8, 8, 136, 1, 1, 1, 0, 0)]
