@@ -243,6 +243,18 @@ int mogan_pk_weight_pack(const float* w, void* wpk, int Cout, int Cin, int KH, i
 /* both copies from one read of w (Cin % 32 == 0 and Cout % 32 == 0): what the owner of the weight calls after its optimizer step */
 int mogan_pk_weight_pack_both(const float* w, void* wpk_fwd, void* wpk_dgrad, int Cout, int Cin, int KH, int KW, int stride, int ph,
                               int pw, hipStream_t stream);
+/* the optimizer step of ONE such weight and both copies in one pass: p, m, v (and ema, nullable) are updated exactly as
+ * mogan_adam_step updates them (same arithmetic, csrc/mogan_adam.h), both panels are written from the new p exactly as
+ * mogan_pk_weight_pack_both writes them, and g is cleared behind its read when zero_g != 0 (left as it is otherwise).
+ * p / g / m / v / ema: (Cout, Cin, KH, KW) dense, 16-byte aligned.  dev_state != NULL: step size and bias correction are read
+ * from it as mogan_adam_prep left them (lr and step are ignored; the count is NOT advanced here: one mogan_adam_prep per bucket
+ * step, in front of all its launches); NULL: from lr and the 1-based step.  MOGAN_ERR_SHAPE before any launch: a NULL or
+ * misaligned pointer, step < 1 without dev_state, a geometry mogan_pk_weight_bytes declines in either direction,
+ * Cin % 32 != 0, Cout % 32 != 0, KH * KW not in {16, 9, 1}. */
+int mogan_pk_adam_pack_both(float* p, float* g, float* m, float* v, float* ema, void* wpk_fwd, void* wpk_dgrad, int Cout, int Cin,
+                            int KH, int KW, int stride, int ph, int pw, float lr, float beta1, float beta2, float eps, int step,
+                            const float* dev_state, int eps_mode, float grad_scale, float ema_decay, int zero_g,
+                            hipStream_t stream);
 int mogan_conv2d_fwd_pk(const float* x, const void* wpk, float* y, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW,
                         int stride, int ph, int pw, void* ws, size_t ws_bytes, hipStream_t stream);
 int mogan_conv2d_dgrad_pk(const float* dy, const void* wpk, float* dx, int B, int Cin, int Hs, int Ws, int Cout, int KH, int KW,
@@ -638,6 +650,13 @@ int mogan_feed_resample(const uint8_t* in, uint8_t* tmp, float* out, const int32
 int mogan_adam_step(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr, float beta1,
                     float beta2, float eps, int step, float* dev_state, int eps_mode, float grad_scale,
                     float ema_decay, hipStream_t stream);
+/* The same step in two parts, for a bucket that is updated by several launches (its deep convolution weights by
+ * mogan_pk_adam_pack_both, the ranges between them here): mogan_adam_prep advances the device-resident count once and leaves
+ * step size and bias correction in dev_state; mogan_adam_apply is mogan_adam_step's element pass over one range, reading them.
+ * MOGAN_ERR_SHAPE before any launch: a NULL dev_state; for mogan_adam_apply also what mogan_adam_step rejects. */
+int mogan_adam_prep(float* dev_state, float lr, float beta1, float beta2, int eps_mode, hipStream_t stream);
+int mogan_adam_apply(float* p, const float* g, float* m, float* v, float* ema, long long n, float beta1, float beta2, float eps,
+                     const float* dev_state, int eps_mode, float grad_scale, float ema_decay, hipStream_t stream);
 
 /* ---- text encoder (round 6, third session; csrc/mogan_rnn.hip): nn.Embedding + one-layer bidirectional nn.LSTM over packed
  * captions in eval mode, without gradients -- RNN_ENCODER.forward, code/coco/attngan/model.py:183-204 (pack_padded_sequence,

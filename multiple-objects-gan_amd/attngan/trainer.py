@@ -69,6 +69,12 @@ class FlatAdam:
         # that qualify, re-packed here after every change of the bucket
         self._pk_cell = [0]
         self.packs = [ops.attach_packs(p, self._pk_cell) for p in self.params if p.dim() == 4] if dev.type == "cuda" else []
+        self._pk_range = {id(p._mogan_pk): (o, p.numel()) for p, o in zip(self.params, offs) if p.dim() == 4} if self.packs else {}
+        # the one-pass update of the deep weights (step): _fused = the (offset, numel) ranges the last step updated that way, which
+        # zero_grad leaves alone; _rest = the ranges between them; _round = the accumulation round (hip/ops._OVERWRITE)
+        self._fused, self._rest, self._round, self._ow_ptrs = [], [(0, total)], [0], []
+        import weakref
+        weakref.finalize(self, ops.overwrite_drop, self._ow_ptrs)
         self._hook = None
         if isinstance(module, torch.nn.Module):
             # through a weak reference: the module must not keep a dropped optimizer (and its four flat buckets, 2.5 GB for
@@ -90,6 +96,7 @@ class FlatAdam:
             self._hook = None
         self.repack_on_touch = False
         self.packs = []
+        self._unfuse()
 
     repack_on_touch = False     # set by an engine that holds captured graphs: those read the packed copies without asking
 
@@ -110,14 +117,70 @@ class FlatAdam:
     on_zero = None          # set by ChunkedReducer: a new accumulation round of this bucket begins
 
     def zero_grad(self):
-        self.g.zero_()
+        self._round[0] += 1
+        if not self._fused:
+            self.g.zero_()
+        else:
+            # the ranges of the last one-pass update stay as they are: that kernel cleared them behind its read, or (hip/ops.
+            # WGRAD_OVERWRITE) the first weight-gradient launch of the round writes them without reading
+            for a, b in self._rest:
+                self.g[a:b].zero_()
         if self.on_zero is not None:
             self.on_zero()
 
+    # One pass over the deep convolution weights (set by the single-process AttnGAN engine for its discriminators): a weight
+    # whose forward and data-gradient panels are both in use is updated AND packed by one launch (hip/ops.adam_pack_both)
+    # instead of being read by adam_kernel and read again by wpack2_kernel, and its gradient is not cleared by a fill.  Off:
+    # one adam_step over the bucket, then the packs.  Data parallel (hip/ops.GRAD_HOOKS: the reducer reads .grad between the
+    # backward and this step) always takes that path.
+    fuse_packs = False
+
+    def _unfuse(self):
+        """back to the plain path: every launch adds again, and the next zero_grad clears the whole bucket"""
+        ops.overwrite_drop(self._ow_ptrs)
+        self._fused, self._rest = [], [(0, self.numel)]
+
     def step(self, grad_scale=1.0):
-        ops.adam_step(self.p, self.g, self.m, self.v, self.ema, self.lr, 0.5, 0.999, 1e-8,
-                      dev_state=self.state, eps_mode=self.eps_mode, grad_scale=grad_scale)
-        self.repack()
+        take = self.fuse_packs and ops.DIRECT_GRAD and not ops.GRAD_HOOKS
+        fused = [pk for pk in self.packs if pk.adam_fusable()] if take else []
+        overwrite = bool(ops.WGRAD_OVERWRITE)
+        if self._ow_ptrs:
+            for o, n in self._fused:      # zero_grad left it alone and no launch wrote it in this round: a consumed gradient
+                if ops.overwrite_stale(self.g[o:o + n]):
+                    self.g[o:o + n].zero_()
+            if not fused or not overwrite:
+                ops.overwrite_drop(self._ow_ptrs)
+        if not fused:
+            self._unfuse()
+            ops.adam_step(self.p, self.g, self.m, self.v, self.ema, self.lr, 0.5, 0.999, 1e-8,
+                          dev_state=self.state, eps_mode=self.eps_mode, grad_scale=grad_scale)
+            self.repack()
+            return
+        ranges = sorted(self._pk_range[id(pk)] for pk in fused)
+        kw = dict(dev_state=self.state, eps_mode=self.eps_mode, grad_scale=grad_scale)
+        sl = lambda t, o, n: None if t is None else t[o:o + n]
+        ops.adam_prep(self.state, self.lr, 0.5, 0.999, self.eps_mode)      # once: every launch below reads the same step size
+        st = ops.stream_ptr()
+        for pk in fused:
+            o, n = self._pk_range[id(pk)]
+            g = self.g[o:o + n]
+            if overwrite and ops.overwrite_register(g, self._round):
+                self._ow_ptrs.append(g.data_ptr())
+            ops.adam_pack_both(pk, self.p[o:o + n], g, self.m[o:o + n], self.v[o:o + n], sl(self.ema, o, n), self.lr, 0.5, 0.999,
+                               1e-8, zero_g=not overwrite, **kw)
+        rest, at = [], 0
+        for o, n in ranges + [(self.numel, 0)]:
+            if o > at:
+                rest.append((at, o))
+            at = o + n
+        for a, b in rest:
+            ops.adam_apply(self.p[a:b], self.g[a:b], self.m[a:b], self.v[a:b], sl(self.ema, a, b - a), 0.5, 0.999, 1e-8, **kw)
+        self._fused, self._rest = ranges, rest
+        # the images: the fused weights' panels are current (one event behind the last launch orders their uses on other
+        # streams), everything else -- other panels, Winograd / dconv2 images, the up-convolutions' virtual filters -- as repack()
+        self._pk_cell[0] += 1
+        ops._stamp(st, [(pk.slots[d], pk.cell) for pk in fused for d in (0, 1)])
+        ops.repack_all(self.packs, packed={id(pk) for pk in fused})
 
     def ema_params(self):
         return [self.ema[o:o + p.numel()].view_as(p) for p, o in zip(self.params, self.offsets)]
@@ -596,6 +659,8 @@ class TrainEngine:
         self.distributed = bool(distributed) and dist.is_available() and dist.is_initialized() \
             and (dist.get_world_size() > 1 or bool(os.environ.get("MOGAN_FORCE_DIST")))   # env: exercise the RCCL path at N=1
         self.world = dist.get_world_size() if self.distributed else 1
+        for o in self.optDs:                      # (single process: nobody reads .grad between the backward and Adam)
+            o.fuse_packs = ops.FUSE_ADAM_PACK and not self.distributed
         self.use_graph = use_graph
         self._graph = None
         self._static = None

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mogan_hip.h"
+#include "mogan_adam.h"
 
 namespace {
 
@@ -421,7 +422,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    long long n4, long long n, float beta1, float beta2, float eps,
                                                    float step_size, float inv_sqrt_bc2, int eps_mode, float gscale,
                                                    float ema_decay, const float* __restrict__ dev_state) {
-    if (dev_state) { step_size = dev_state[1]; inv_sqrt_bc2 = dev_state[2]; }
+    const AdamCoef ac = adam_coef(beta1, beta2, eps, step_size, inv_sqrt_bc2, eps_mode, gscale, ema_decay, dev_state);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         const long long e = i * 4;
         float pv[4], gv[4], mv[4], vv[4], ev[4];
@@ -434,13 +435,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
             for (int k = 0; k < 4; ++k) if (e + k < n) { pv[k] = p[e + k]; gv[k] = g[e + k]; mv[k] = m[e + k]; vv[k] = v[e + k]; if (ema) ev[k] = ema[e + k]; }
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float gg = gv[k] * gscale;
-            mv[k] = mv[k] * beta1 + (1.f - beta1) * gg;
-            vv[k] = vv[k] * beta2 + (1.f - beta2) * gg * gg;
-            const float denom = eps_mode == 0 ? (sqrtf(vv[k]) * inv_sqrt_bc2 + eps) : (sqrtf(vv[k]) + eps);
-            pv[k] = pv[k] - step_size * (mv[k] / denom);
-            if (ema) ev[k] = ev[k] * ema_decay + (1.f - ema_decay) * pv[k];
+        for (int k = 0; k < 4; ++k) {                      // (mogan_adam.h: the update itself)
+            if (ema) adam_update<true>(ac, pv[k], gv[k], mv[k], vv[k], ev[k]);
+            else adam_update<false>(ac, pv[k], gv[k], mv[k], vv[k], ev[k]);
         }
         if (full) {
             *(float4*)(p + e) = *(float4*)pv; *(float4*)(m + e) = *(float4*)mv; *(float4*)(v + e) = *(float4*)vv;
@@ -869,6 +866,24 @@ int mogan_adam_step(float* p, const float* g, float* m, float* v, float* ema, lo
     const long long n4 = (n + 3) / 4;
     hipLaunchKernelGGL(adam_kernel, dim3(nblk(n4)), dim3(256), 0, stream, p, g, m, v, ema, n4, n, beta1, beta2, eps,
                        step_size, inv_sqrt_bc2, eps_mode, grad_scale, ema_decay, (const float*)dev_state);
+    return ok_launch();
+}
+
+// The same step in two parts, for an owner that updates a bucket in several launches (trainer.FlatAdam: the deep convolution
+// weights through mogan_pk_adam_pack_both, the rest of the bucket here): the device-resident count advances ONCE ...
+int mogan_adam_prep(float* dev_state, float lr, float beta1, float beta2, int eps_mode, hipStream_t stream) {
+    if (!dev_state) return MOGAN_ERR_SHAPE;
+    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, stream, dev_state, lr, beta1, beta2, eps_mode);
+    return ok_launch();
+}
+// ... and every range reads the step size and bias correction it left in dev_state
+int mogan_adam_apply(float* p, const float* g, float* m, float* v, float* ema, long long n, float beta1, float beta2, float eps,
+                     const float* dev_state, int eps_mode, float grad_scale, float ema_decay, hipStream_t stream) {
+    if (!p || !g || !m || !v || !dev_state || n <= 0) return MOGAN_ERR_SHAPE;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) != 0) return MOGAN_ERR_SHAPE;
+    const long long n4 = (n + 3) / 4;
+    hipLaunchKernelGGL(adam_kernel, dim3(nblk(n4)), dim3(256), 0, stream, p, g, m, v, ema, n4, n, beta1, beta2, eps, 0.f, 0.f,
+                       eps_mode, grad_scale, ema_decay, dev_state);
     return ok_launch();
 }
 

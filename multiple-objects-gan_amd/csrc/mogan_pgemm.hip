@@ -33,6 +33,8 @@
 #include "mogan_internal.h"
 #include "mogan_mma.h"
 #include "mogan_bn.h"
+#include "mogan_adam.h"
+#include <math.h>
 #include <type_traits>
 #ifndef PK_NSET
 #define PK_NSET 3
@@ -385,28 +387,9 @@ __global__ __launch_bounds__(256) void wpack_kernel(const WpackP p) {
 struct Wpack2P { const float* w; unsigned char* Af; unsigned char* Ad; int Cout, Cin, KW, s, ph, pw, KSf, KSd;
                  unsigned long long cls_stride; };
 
+// the block's tile L[tap][32 co][16 ci + 1] (fp32, complete) -> its lane slots of the forward and the data-gradient panels
 template <int KHW>
-__global__ __launch_bounds__(256) void wpack2_kernel(const Wpack2P p) {
-    __shared__ float L[KHW * 32 * 17];                 // [tap][32 co][16 ci + 1]
-    const int tid = threadIdx.x;
-    const int co0 = blockIdx.x * 32, ci0 = blockIdx.y * 16;
-    constexpr int ROW = 16 * KHW;                      // floats per co row of the tile (contiguous in the master)
-    if constexpr (ROW % 4 == 0) {
-        for (int q = tid; q < 32 * ROW / 4; q += 256) {
-            const int mi = q / (ROW / 4), r4 = (q - mi * (ROW / 4)) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (co0 + mi < p.Cout) v = *(const float4*)(p.w + ((size_t)(co0 + mi) * p.Cin + ci0) * KHW + r4);
-            const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const int r = r4 + j; L[((r % KHW) * 32 + mi) * 17 + r / KHW] = e[j]; }
-        }
-    } else {
-        for (int q = tid; q < 32 * ROW; q += 256) {
-            const int mi = q / ROW, r = q - mi * ROW;
-            L[((r % KHW) * 32 + mi) * 17 + r / KHW] = (co0 + mi < p.Cout) ? p.w[((size_t)(co0 + mi) * p.Cin + ci0) * KHW + r] : 0.f;
-        }
-    }
-    __syncthreads();
+__device__ __forceinline__ void wpack2_store(const float* L, const Wpack2P& p, int tid, int co0, int ci0) {
     const int nkw = p.KW / p.s;
     for (int it = tid; it < KHW * 128; it += 256) {
         const int tap = it >> 7, sub = it & 127;
@@ -435,6 +418,70 @@ __global__ __launch_bounds__(256) void wpack2_kernel(const Wpack2P p) {
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) *(uint4*)(d + pl * 1024) = make_uint4(w[pl][0], w[pl][1], w[pl][2], w[pl][3]);
     }
+}
+
+template <int KHW>
+__global__ __launch_bounds__(256) void wpack2_kernel(const Wpack2P p) {
+    __shared__ float L[KHW * 32 * 17];                 // [tap][32 co][16 ci + 1]
+    const int tid = threadIdx.x;
+    const int co0 = blockIdx.x * 32, ci0 = blockIdx.y * 16;
+    constexpr int ROW = 16 * KHW;                      // floats per co row of the tile (contiguous in the master)
+    if constexpr (ROW % 4 == 0) {
+        for (int q = tid; q < 32 * ROW / 4; q += 256) {
+            const int mi = q / (ROW / 4), r4 = (q - mi * (ROW / 4)) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (co0 + mi < p.Cout) v = *(const float4*)(p.w + ((size_t)(co0 + mi) * p.Cin + ci0) * KHW + r4);
+            const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const int r = r4 + j; L[((r % KHW) * 32 + mi) * 17 + r / KHW] = e[j]; }
+        }
+    } else {
+        for (int q = tid; q < 32 * ROW; q += 256) {
+            const int mi = q / ROW, r = q - mi * ROW;
+            L[((r % KHW) * 32 + mi) * 17 + r / KHW] = (co0 + mi < p.Cout) ? p.w[((size_t)(co0 + mi) * p.Cin + ci0) * KHW + r] : 0.f;
+        }
+    }
+    __syncthreads();
+    wpack2_store<KHW>(L, p, tid, co0, ci0);
+}
+
+// The optimizer step and the pack in ONE pass over a deep weight (mogan_pk_adam_pack_both): the block's 32 co x 16 ci x taps
+// slice of p, g, m, v (and ema) is 16 * KHW contiguous floats per co, read with 16-byte loads; the update is adam_kernel's
+// (mogan_adam.h); p, m, v (and ema) go back, g is cleared for the next accumulation round (zero_g), and the panels are written
+// from the NEW p, which never leaves the chip in between -- wpack2_kernel's tile, wpack2_kernel's stores.
+struct Wpack2AdamP { Wpack2P pk; float* p; float* g; float* m; float* v; float* ema; const float* dev_state;
+                     float beta1, beta2, eps, step_size, inv_sqrt_bc2, gscale, ema_decay; int eps_mode, zero_g; };
+
+template <int KHW, bool HAS_EMA>
+__global__ __launch_bounds__(256) void wpack2_adam_kernel(const Wpack2AdamP a) {
+    __shared__ float L[KHW * 32 * 17];                 // [tap][32 co][16 ci + 1]
+    const Wpack2P& p = a.pk;
+    const int tid = threadIdx.x;
+    const int co0 = blockIdx.x * 32, ci0 = blockIdx.y * 16;
+    constexpr int ROW = 16 * KHW;
+    static_assert(ROW % 4 == 0, "16-byte accesses of a co row");
+    const AdamCoef k = adam_coef(a.beta1, a.beta2, a.eps, a.step_size, a.inv_sqrt_bc2, a.eps_mode, a.gscale, a.ema_decay,
+                                 a.dev_state);
+    for (int q = tid; q < 32 * ROW / 4; q += 256) {
+        const int mi = q / (ROW / 4), r4 = (q - mi * (ROW / 4)) * 4;
+        float pv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (co0 + mi < p.Cout) {
+            const size_t o = ((size_t)(co0 + mi) * p.Cin + ci0) * KHW + r4;
+            float gv[4], mv[4], vv[4], ev[4] = {0.f, 0.f, 0.f, 0.f};
+            *(float4*)pv = *(const float4*)(a.p + o); *(float4*)gv = *(const float4*)(a.g + o);
+            *(float4*)mv = *(const float4*)(a.m + o); *(float4*)vv = *(const float4*)(a.v + o);
+            if (HAS_EMA) *(float4*)ev = *(const float4*)(a.ema + o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) adam_update<HAS_EMA>(k, pv[j], gv[j], mv[j], vv[j], ev[j]);
+            *(float4*)(a.p + o) = *(float4*)pv; *(float4*)(a.m + o) = *(float4*)mv; *(float4*)(a.v + o) = *(float4*)vv;
+            if (HAS_EMA) *(float4*)(a.ema + o) = *(float4*)ev;
+            if (a.zero_g) *(float4*)(a.g + o) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int r = r4 + j; L[((r % KHW) * 32 + mi) * 17 + r / KHW] = pv[j]; }
+    }
+    __syncthreads();
+    wpack2_store<KHW>(L, p, tid, co0, ci0);
 }
 
 
@@ -965,6 +1012,44 @@ int mogan_pk_weight_pack_both(const float* w, void* wpk_fwd, void* wpk_dgrad, in
             return rc ? rc : mogan_pk_weight_pack(w, wpk_dgrad, Cout, Cin, KH, KW, stride, ph, pw, 1, stream);
         }
     }
+    return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH;
+}
+
+// Every rejection -- pointers, their alignment, the step count, both panel geometries, the channel counts, the tap count -- is
+// answered before the launch: a rejected call has touched neither the weight nor its moments nor a panel.
+int mogan_pk_adam_pack_both(float* p, float* g, float* m, float* v, float* ema, void* wpk_fwd, void* wpk_dgrad, int Cout, int Cin,
+                            int KH, int KW, int stride, int ph, int pw, float lr, float beta1, float beta2, float eps, int step,
+                            const float* dev_state, int eps_mode, float grad_scale, float ema_decay, int zero_g,
+                            hipStream_t stream) {
+    PkGeom gf, gd;
+    if (!p || !g || !m || !v || !wpk_fwd || !wpk_dgrad || (!dev_state && step < 1)) return MOGAN_ERR_SHAPE;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)wpk_fwd | (uintptr_t)wpk_dgrad) & 15) != 0)
+        return MOGAN_ERR_SHAPE;
+    if (!pk_geom(Cout, Cin, KH, KW, stride, 0, gf) || !pk_geom(Cout, Cin, KH, KW, stride, 1, gd)) return MOGAN_ERR_SHAPE;
+    if (Cin % 32 || Cout % 32) return MOGAN_ERR_SHAPE;
+    const int taps = KH * KW;
+    if (taps != 16 && taps != 9 && taps != 1) return MOGAN_ERR_SHAPE;
+    Wpack2AdamP a{};
+    a.pk.w = p; a.pk.Af = (unsigned char*)wpk_fwd; a.pk.Ad = (unsigned char*)wpk_dgrad; a.pk.Cout = Cout; a.pk.Cin = Cin;
+    a.pk.KW = KW; a.pk.s = stride; a.pk.ph = ph; a.pk.pw = pw; a.pk.KSf = gf.KS; a.pk.KSd = gd.KS; a.pk.cls_stride = gd.cls_bytes;
+    a.p = p; a.g = g; a.m = m; a.v = v; a.ema = ema; a.dev_state = dev_state;
+    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.eps_mode = eps_mode; a.gscale = grad_scale; a.ema_decay = ema_decay;
+    a.zero_g = zero_g ? 1 : 0;
+    if (!dev_state) {                                     // (as mogan_adam_step: the host's step count)
+        const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+        a.step_size = eps_mode == 0 ? (float)(lr / bc1) : (float)(lr * sqrt(bc2) / bc1);
+        a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
+    const dim3 grid((unsigned)(Cout / 32), (unsigned)(Cin / 16));
+#define MOGAN_ADAM_PACK(T)                                                                                          \
+    if (ema) hipLaunchKernelGGL((wpack2_adam_kernel<T, true>), grid, dim3(256), 0, stream, a);                      \
+    else hipLaunchKernelGGL((wpack2_adam_kernel<T, false>), grid, dim3(256), 0, stream, a)
+    switch (taps) {
+        case 16: MOGAN_ADAM_PACK(16); break;
+        case 9: MOGAN_ADAM_PACK(9); break;
+        default: MOGAN_ADAM_PACK(1); break;
+    }
+#undef MOGAN_ADAM_PACK
     return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH;
 }
 

@@ -49,6 +49,7 @@ SIGNATURES = {
     "mogan_pk_weight_bytes": [I] * 6,
     "mogan_pk_weight_pack": [P, P] + [I] * 8 + [P],
     "mogan_pk_weight_pack_both": [P, P, P] + [I] * 7 + [P],
+    "mogan_pk_adam_pack_both": [P] * 7 + [I] * 7 + [F, F, F, F, I, P, I, F, F, I, P],
     "mogan_conv2d_fwd_pk": [P, P, P] + [I] * 10 + [P, Z, P],
     "mogan_conv2d_dgrad_pk": [P, P, P] + [I] * 10 + [P, Z, P],
     "mogan_pk_debug_force": [I, I, I],
@@ -112,6 +113,8 @@ SIGNATURES = {
     "mogan_bilinear_fwd": [P, P, I, I, I, I, I, P],
     "mogan_bilinear_bwd": [P, P, I, I, I, I, I, P],
     "mogan_adam_step": [P, P, P, P, P, L, F, F, F, F, I, P, I, F, F, P],
+    "mogan_adam_prep": [P, F, F, F, I, P],
+    "mogan_adam_apply": [P, P, P, P, P, L, F, F, F, P, I, F, F, P],
     "mogan_conv2d_affine_fwd_ex": [P, L, P, P, P, P, L, P, L, I] + [I] * 11 + [P, Z, P],
     "mogan_conv2d_fwd_ex": [P, L, P, P, L, P, L, I] + [I] * 10 + [P, Z, P],
     "mogan_conv2d_dgrad_ex": [P, L, P, P, L, P, L, I] + [I] * 10 + [P, Z, P],

@@ -120,20 +120,64 @@ _MERGE_K = 2048
 _MERGE_W = 1 << 21
 
 
+# The deep weights whose optimizer step and pack run as one pass (trainer.FlatAdam, mogan_pk_adam_pack_both) are not cleared
+# by zero_grad.  WGRAD_OVERWRITE = True: the FIRST weight-gradient launch of an accumulation round writes dW instead of adding
+# to it (the merged real + fake launch, as a rule the only one), later ones of the round -- the wrong-pair call of a
+# conditional head, leftovers at the join -- add; nobody clears or reads a gradient nobody needs.  False: the fused kernel
+# clears g behind its read (zero_g) and every launch adds, as everywhere else.  _OVERWRITE: gradient buffer address ->
+# [the owner's round counter (a one-element list, bumped by its zero_grad), the round of the buffer's last launch].
+FUSE_ADAM_PACK = os.environ.get("MOGAN_FUSE_ADAM_PACK", "1") != "0"       # read by trainer.TrainEngine when it is built
+WGRAD_OVERWRITE = os.environ.get("MOGAN_WGRAD_OVERWRITE", "1") != "0"
+_OVERWRITE = {}
+
+
+def overwrite_register(g, round_cell):
+    """g (a parameter's range of a flat gradient bucket) is no longer cleared by its owner: the first launch of each round
+    overwrites it.  The round in progress counts as begun -- a launch before the next zero_grad adds, as it did before."""
+    if g.data_ptr() in _OVERWRITE:
+        return False
+    _OVERWRITE[g.data_ptr()] = [round_cell, round_cell[0]]
+    return True
+
+
+def overwrite_drop(ptrs):
+    """the owner clears these gradients itself again (or is gone)"""
+    for p in ptrs:
+        _OVERWRITE.pop(p, None)
+    del ptrs[:]
+
+
+def overwrite_stale(g):
+    """g is registered and has received no launch in its owner's current round: it still holds the last round's gradient"""
+    rec = _OVERWRITE.get(g.data_ptr())
+    return rec is not None and rec[1] != rec[0][0]
+
+
+def _first_of_round(g):
+    """True: this launch into g is the first of its owner's accumulation round and g was not cleared -- it must overwrite"""
+    rec = _OVERWRITE.get(g.data_ptr()) if _OVERWRITE else None
+    if rec is None:
+        return False
+    first = rec[1] != rec[0][0]
+    rec[1] = rec[0][0]
+    return first
+
+
 def _wgrad_launch(dy, x, w_shape, geom, g):
     stride, ph, pw, up = geom
+    acc = not _first_of_round(g)
     if WGRAD_SIDE_STREAM:
         cur, side = _wgrad_stream()
         side.wait_stream(cur)                     # dy (and the zeroed / partly accumulated grad) are ready
         with torch.cuda.stream(side):
-            conv2d_wgrad(dy, x, w_shape, stride, ph, pw, up, out=g, accumulate=True)
+            conv2d_wgrad(dy, x, w_shape, stride, ph, pw, up, out=g, accumulate=acc)
         fr = _wgrad_frames[-1]
         if side not in fr.used:
             fr.used.append(side)
         fr.keep.append((dy, x))                   # freed only after the join (see join_wgrad)
         _grad_hit(g, side)
     else:
-        conv2d_wgrad(dy, x, w_shape, stride, ph, pw, up, out=g, accumulate=True)
+        conv2d_wgrad(dy, x, w_shape, stride, ph, pw, up, out=g, accumulate=acc)
         _grad_hit(g)
 
 
@@ -396,12 +440,22 @@ class WeightPacks:
         _stamp(st, [(slot, self.cell)])
         PK_STATS["packs"] += 1
 
+    def both_in_use(self):
+        """both panels are in use, for one geometry, on a shape mogan_pk_weight_pack_both packs in one launch"""
+        s0, s1 = self.slots.get(0), self.slots.get(1)
+        Cout, Cin = self.w.shape[:2]
+        return s0 is not None and s1 is not None and s0.geom == s1.geom and Cin % 32 == 0 and Cout % 32 == 0
+
+    def adam_fusable(self):
+        """... and the optimizer step can ride in that launch (mogan_pk_adam_pack_both: 4x4, 3x3 and 1x1 filters)"""
+        return self.both_in_use() and self.w.shape[2] * self.w.shape[3] in (16, 9, 1)
+
     def repack(self):
         """re-pack every copy in use now, on the current stream (the owner just changed the weight): both directions from one
         read of the master where both are in use (mogan_pk_weight_pack_both)"""
         s0, s1 = self.slots.get(0), self.slots.get(1)
         Cout, Cin, KH, KW = self.w.shape
-        if s0 is not None and s1 is not None and s0.geom == s1.geom and Cin % 32 == 0 and Cout % 32 == 0:
+        if self.both_in_use():
             stride, ph, pw = s0.geom
             st = stream_ptr()
             call("mogan_pk_weight_pack_both", ptr(self.w), s0.buf.data_ptr(), s1.buf.data_ptr(), Cout, Cin, KH, KW, stride, ph, pw, st)
@@ -508,13 +562,15 @@ def k4_build_group(pks):
     PK_STATS["k4_builds"] = PK_STATS.get("k4_builds", 0) + 1
 
 
-def repack_all(packs):
+def repack_all(packs, packed=()):
     """Every derived weight image of a bucket brought up to date on the current stream (the owner changed the weights): the
     packed panels pack by pack, the virtual filters of the up-convolutions in one launch, then the prepared filter images of
-    all weights -- those built from the virtual filters among them -- in one launch."""
+    all weights -- those built from the virtual filters among them -- in one launch.  `packed`: ids of the packs whose panels
+    the owner's optimizer step has already written (adam_pack_both)."""
     items, k4s = [], []
     for pk in packs:
-        pk.repack()
+        if id(pk) not in packed:
+            pk.repack()
         items += [(pk, d, im) for d, im in pk.wino.items()]
         if pk.k4 is not None:                  # the virtual filters of an up-convolution, then the images built from them
             k4s.append(pk)
@@ -2321,6 +2377,31 @@ def adam_step(p, g, m, v, ema, lr, beta1, beta2, eps, step=0, dev_state=None, ep
     """In-place fused Adam (+EMA) over flat fp32 buckets (trainer.py:137-148,341-342)."""
     call("mogan_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), lr, beta1, beta2, eps, step,
          ptr(dev_state), eps_mode, grad_scale, ema_decay, stream_ptr())
+
+
+def adam_prep(dev_state, lr, beta1, beta2, eps_mode=0):
+    """advance the device-resident step count once: what adam_apply / adam_pack_both launches of this step then read"""
+    call("mogan_adam_prep", ptr(dev_state), lr, beta1, beta2, eps_mode, stream_ptr())
+
+
+def adam_apply(p, g, m, v, ema, beta1, beta2, eps, dev_state, eps_mode=0, grad_scale=1.0, ema_decay=0.999):
+    """adam_step's element pass over one range of a bucket, with the step size adam_prep left in dev_state"""
+    call("mogan_adam_apply", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), beta1, beta2, eps, ptr(dev_state), eps_mode,
+         grad_scale, ema_decay, stream_ptr())
+
+
+def adam_pack_both(pk, p, g, m, v, ema, lr, beta1, beta2, eps, step=0, dev_state=None, eps_mode=0, grad_scale=1.0,
+                   ema_decay=0.999, zero_g=True):
+    """The Adam (+EMA) step of ONE deep convolution weight and both of its packed copies in one pass over it
+    (mogan_pk_adam_pack_both); p, g, m, v, ema: the weight's ranges of the flat buckets, pk: its WeightPacks with both panels in
+    use for one geometry.  The caller stamps the panels current (_stamp) behind its last launch."""
+    Cout, Cin, KH, KW = pk.w.shape
+    s0, s1 = pk.slots[0], pk.slots[1]
+    stride, ph, pw = s0.geom
+    call("mogan_pk_adam_pack_both", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), s0.buf.data_ptr(), s1.buf.data_ptr(), Cout, Cin, KH,
+         KW, stride, ph, pw, lr, beta1, beta2, eps, step, ptr(dev_state), eps_mode, grad_scale, ema_decay, 1 if zero_g else 0,
+         stream_ptr())
+    PK_STATS["adam_packs"] = PK_STATS.get("adam_packs", 0) + 1
 
 
 # ------------------------------------------------------------------------------- text encoder (csrc/mogan_rnn.hip)
