@@ -1,15 +1,18 @@
 """coco-attngan checkpoint evaluation (mirror of code/coco/attngan/trainer.py:387-579, plus the scores of DESIGN.md sections 9c-9k).
 
 `CheckpointEvaluation` is the base of `trainer.condGANTrainer` that holds every path which reads a finished checkpoint instead of
-training one: `sampling` / `sample` (images), `r_precision`, and `pool_codes` with the three scores `fid` / `kid` / `prdc` that share
-its pass, `swd`, `msssim` and `spectrum`, which take the pass's images instead of their codes, and `scene_fid`, which takes the images and
-their boxes and runs the trunk on the objects, and `memorisation`, which searches the pass's codes in a bank of the TRAIN split's.  It needs `self.device`, `self.data_loader`,
-`self.n_words` and `self.ixtoword` of the trainer and nothing of the train step.  What these paths have in common is written
-once here: the NET_G guard and the save-directory rule (`net_g_missing`, `eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
-(`generate_seeded`), and what the three scores do around their own device calls (`PooledCodes`, `trunk_note`)."""
+training one: `sampling` / `sample` (images), `r_precision`, and `pool_codes`, the one pass over the data loader, with the eight scores
+of the table `SCORES` that can share it.  It needs `self.device`, `self.data_loader`, `self.n_words` and `self.ixtoword` of the trainer
+and nothing of the train step.  What these paths have in common is written once here: the NET_G guard and the save-directory rule
+(`net_g_missing`, `eval_save_dir`), the text side of a batch (`encode_text`), the seeded generation whose draw order the tests rely on
+(`generate_seeded`), the keys every score's JSON shares (`write_score`) and what the scores on the pooled codes do around their own
+device calls (`PooledCodes`, `trunk_note`).
+
+How scores share a pass is written once too (`SCORES`, `shared_pass`, `run_scores`, `fed`): a new score costs its
+method, one row of `SCORES` and -- where it reads the images -- an accumulator with `sink`, optionally `resample_sink`, and `params`."""
 import json
 import os
-from types import SimpleNamespace
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -71,6 +74,38 @@ def write_json(save_dir, name, out):
         json.dump(out, f, indent=1, sort_keys=True)
 
 
+def write_score(split_dir, who, out, seed, note):
+    """adds the keys every score's JSON shares to `out`, writes <save directory>/<who>.json and returns the directory"""
+    out.update({"seed": int(seed), "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E, "note": note})
+    save_dir = eval_save_dir(split_dir)
+    write_json(save_dir, who, out)
+    return save_dir
+
+
+# The scores that can share one pass, in the order a shared pass finishes them (memorisation last: its grid re-reads training
+# images).  name: the method and main.py's flag.  takes, also the keyword of the hand-over: "codes" -- both sides' pooled codes;
+# "objects" -- the images, their boxes and the trunk, not the real images' own codes; "images" -- the images only.  factory: the method
+# that makes the accumulator from (num_samples, seed) and the score's keywords `params`; a "codes" row's rides in the codes.
+Score = namedtuple("Score", "name takes factory params")
+SCORES = {s.name: s for s in (
+    Score("scene_fid", "objects", "scene_fid_objects", ("min_side",)),
+    Score("swd", "images", "swd_images", ("patches", "dirs", "repeats", "min_res")),
+    Score("msssim", "images", "msssim_images", ("scales", "same_caption")),
+    Score("spectrum", "images", "spectrum_images", ("window",)),
+    Score("fid", "codes", None, ()),
+    Score("kid", "codes", None, ()),
+    Score("prdc", "codes", None, ()),
+    Score("memorisation", "codes", "thumbnails", ("show",)))}
+
+
+def fan_out(sinks):
+    """one callable that hands a batch to every sink of one kind, in order; None for none"""
+    def every(*batch):
+        for sink in sinks:
+            sink(*batch)
+    return every if sinks else None
+
+
 def encode_text(text_encoder, captions, cap_lens):
     """The text side of one batch (trainer.py:431-437): (words_embs, sent_emb, mask), both embeddings contiguous, the
     mask of the padding words cut to the word count the encoder returned.  Call it under torch.no_grad()."""
@@ -119,16 +154,15 @@ class PooledCodes:
                 codes = dict(codes, real=None)
             elif codes["real"] is None:
                 raise ValueError("%s: the codes handed over hold no real side%s" % (who, or_else))
-        self.who, self.seed, self.n, self.digest = who, int(seed), codes["n"], codes["trunk_digest"]
+        self.who, self.seed, self.n, self.digest, self.split_dir = who, int(seed), codes["n"], codes["trunk_digest"], split_dir
         self.real = None if codes["real"] is None else codes["real"][:self.n]
         self.fake = codes["fake"][:self.n]
         self.save_dir = eval_save_dir(split_dir)
 
     def write(self, out, n_real, n_fake, note):
         """adds the common keys to `out`, writes <save_dir>/<who>.json and returns `out`"""
-        out.update({"n_real": int(n_real), "n_fake": int(n_fake), "seed": self.seed, "NET_G": cfg.TRAIN.NET_G,
-                    "NET_E": cfg.TRAIN.NET_E, "trunk_digest": self.digest, "note": note})
-        write_json(self.save_dir, self.who, out)
+        out.update({"n_real": int(n_real), "n_fake": int(n_fake), "trunk_digest": self.digest})
+        write_score(self.split_dir, self.who, out, self.seed, note)
         return out
 
     def result(self, out, return_codes):
@@ -349,7 +383,7 @@ class CheckpointEvaluation(object):
         if net_g_missing():
             return None
         netG, text_encoder, image_encoder, gen = self._load_seeded(seed, trunk)
-        rows = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        rows = self.pass_shape(num_samples)[1]
         digest = fake_codes = real_codes = None
         if trunk:
             D = int(image_encoder.emb_cnn_code.weight.shape[1])             # 2048: the pooled code's width
@@ -383,6 +417,55 @@ class CheckpointEvaluation(object):
                     object_sink(imgs[-1], fake, tm, take, image_encoder)
             n += take
         return {"real": real_codes, "fake": fake_codes, "n": n, "trunk_digest": digest, "seed": int(seed)}
+
+    def pass_shape(self, num_samples):
+        """(size, images) of a pass: the side of the tree's final resolution and how many images the pass will see at most"""
+        return cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1), max(1, min(int(num_samples), len(self.data_loader.dataset)))
+
+    def shared_pass(self, split_dir, num_samples, seed, accs):
+        """pool_codes for the scores `accs` names (score -> its accumulator or None), every keyword derived from SCORES: the trunk runs
+        where a score takes codes or objects, on the real images where one takes codes; the sinks are composed per kind in table order"""
+        takes = {SCORES[name].takes for name in accs}
+        made = [(SCORES[name].takes == "objects", accs[name]) for name in SCORES if accs.get(name) is not None]
+        return self.pool_codes(
+            split_dir, num_samples, seed, want_real="codes" in takes, trunk=bool(takes & {"codes", "objects"}),
+            image_sink=fan_out([acc.sink for boxes, acc in made if not boxes]),
+            object_sink=fan_out([acc.sink for boxes, acc in made if boxes]),
+            resample_sink=fan_out([acc.resample_sink for _, acc in made if getattr(acc, "resample_sink", None) is not None]))
+
+    def fed(self, who, split_dir, num_samples, acc, **params):
+        """The hand-over rule of the scores with an accumulator: `acc` None -- the score's factory makes one under `params` and a pass of
+        the score's own feeds it; else a pass the caller shared has fed it, and it must have been made under `params`.  Returns it."""
+        if acc is None:
+            acc = getattr(self, SCORES[who].factory)(num_samples, **params)
+            self.shared_pass(split_dir, num_samples, params["seed"], {who: acc})
+        elif acc.params != params:
+            raise ValueError("%s: the accumulator handed over was made under other parameters (%s) = %s"
+                             % (who, ", ".join(acc.params), tuple(acc.params.values())))
+        return acc
+
+    def run_scores(self, split_dir, asked, num_samples=30000, seed=100):
+        """The scores `asked` names (score -> its own keyword arguments) from ONE pass: the accumulators are made, shared_pass runs once,
+        each score finishes in table order from what it is handed.  One score alone runs its own method without a hand-over (fid() may
+        then keep the real images out of the trunk, swd(), msssim() and spectrum() load no image encoder).  Returns score -> result."""
+        if not asked or set(asked) - set(SCORES):
+            raise ValueError("run_scores: one score at least of %s expected, got %s" % (list(SCORES), list(asked)))
+        if len(asked) == 1:
+            (name, kw), = asked.items()
+            return {name: getattr(self, name)(split_dir, num_samples, seed, **kw)}
+        if net_g_missing():
+            return None
+        accs = {}
+        for row in (SCORES[name] for name in SCORES if name in asked):
+            kw = {k: asked[row.name][k] for k in row.params if k in asked[row.name]}
+            accs[row.name] = row.factory and getattr(self, row.factory)(num_samples, seed, **kw)
+        codes = self.shared_pass(split_dir, num_samples, seed, accs)
+        out = {}
+        for name, acc in accs.items():
+            takes = SCORES[name].takes
+            handed = acc if takes != "codes" else codes if acc is None else dict(codes, thumbnails=acc)
+            out[name] = getattr(self, name)(split_dir, num_samples, seed, **dict(asked[name], **{takes: handed}))
+        return out
 
     def fid(self, split_dir, num_samples=30000, seed=100, stats_path=None, return_codes=False, codes=None):
         """Frechet distance between real and generated images of the checkpoint TRAIN.NET_G in the Inception pool codes of
@@ -500,18 +583,13 @@ class CheckpointEvaluation(object):
 
     def swd_images(self, num_samples=30000, seed=100, patches=128, dirs=128, repeats=4, min_res=16):
         """The accumulator swd() fills: attngan/swd.SlicedWasserstein for the tree's final resolution and as many images as the
-        pass will see, with `sink`, the (real, fake, take) callable pool_codes' image_sink wants.  A caller that shares one pass
-        between swd() and the trunk's scores makes it first and hands it to both (main.py)."""
+        pass will see, whose `sink` is the (real, fake, take) callable pool_codes' image_sink wants.  A caller that shares one pass
+        between swd() and other scores makes it first and hands it to both (run_scores)."""
         from .swd import SlicedWasserstein
-        size = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1)
-        images = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        size, images = self.pass_shape(num_samples)
         acc = SlicedWasserstein(size, 3, images * int(patches), patches, dirs, repeats, min_res, seed, self.device)
         print("SWD: %.2f GB of descriptors on the device (%d levels x 2 sides x %d rows x %d values, fp32)"
               % (acc.bytes / 1e9, len(acc.sizes), acc.rows, acc.desc["real"][0].shape[1]))
-
-        def sink(real, fake, take):
-            acc.add(real[:take].float().contiguous(), fake[:take].float().contiguous())
-        acc.sink = sink
         return acc
 
     def swd(self, split_dir, num_samples=30000, seed=100, patches=128, dirs=128, repeats=4, min_res=16, images=None):
@@ -524,58 +602,32 @@ class CheckpointEvaluation(object):
         <NET_G minus .pth>/<split>/swd.json and returns its content."""
         if net_g_missing():
             return None
-        if images is None:
-            images = self.swd_images(num_samples, seed, patches, dirs, repeats, min_res)
-            self.pool_codes(split_dir, num_samples, seed, want_real=False, image_sink=images.sink, trunk=False)
-        elif ((images.seed, images.patches, images.dirs, images.repeats, images.sizes[-1])
-              != (int(seed), int(patches), int(dirs), int(repeats), int(min_res))):
-            raise ValueError("swd: the images handed over were gathered under other parameters (seed, patches, dirs, repeats, "
-                             "min_res) = %s" % ((images.seed, images.patches, images.dirs, images.repeats, images.sizes[-1]),))
+        images = self.fed("swd", split_dir, num_samples, images, seed=int(seed), patches=int(patches), dirs=int(dirs),
+                          repeats=int(repeats), min_res=int(min_res))
         if images.n < 1:
             raise ValueError("swd: the data loader gave no batch")
         res = images.result()
         n = images.n // images.patches
         out = {"swd": res["swd"], "levels": res["levels"], "per_level": res["per_level"], "patches": images.patches,
-               "dirs": images.dirs, "repeats": images.repeats, "n_real": n, "n_fake": n, "seed": int(seed),
-               "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E,
-               "note": "Sliced Wasserstein distance x 1000 between Laplacian-pyramid descriptors (7x7 neighbourhoods) of the real "
-                       "and the generated images, per level and averaged: trunk-free -- no image encoder is involved, the figure "
-                       "does not depend on any encoder weights.  It depends on the number of descriptors per image (patches = "
-                       "%d), on dirs, repeats and the seed, and is comparable under equal settings only.  The images enter as "
-                       "fp32 in [-1, 1], not quantised to 8 bits as in Karras et al.'s code." % images.patches}
-        save_dir = eval_save_dir(split_dir)
-        write_json(save_dir, "swd", out)
+               "dirs": images.dirs, "repeats": images.repeats, "n_real": n, "n_fake": n}
+        save_dir = write_score(
+            split_dir, "swd", out, seed,
+            "Sliced Wasserstein distance x 1000 between Laplacian-pyramid descriptors (7x7 neighbourhoods) of the real "
+            "and the generated images, per level and averaged: trunk-free -- no image encoder is involved, the figure "
+            "does not depend on any encoder weights.  It depends on the number of descriptors per image (patches = "
+            "%d), on dirs, repeats and the seed, and is comparable under equal settings only.  The images enter as "
+            "fp32 in [-1, 1], not quantised to 8 bits as in Karras et al.'s code." % images.patches)
         print("SWD (%d real, %d generated images; %d patches, %d directions, %d repeats): %.4f = mean of %s at levels %s -> %s/swd.json"
               % (n, n, images.patches, images.dirs, images.repeats, out["swd"], ["%.4f" % v for v in out["per_level"]],
                  out["levels"], save_dir))
         return out
 
     def msssim_images(self, num_samples=30000, seed=100, scales=5, same_caption=True):
-        """The accumulator msssim() fills: one attngan/msssim.PairSimilarity per figure ("real", "generated" and, with
-        `same_caption`, "same_caption") for the tree's final resolution and as many pairs as the pass can give, with `sink`, the
-        (real, fake, take) callable of pool_codes' image_sink, and `resample_sink`, the (fake, fake_again, take) callable of its
-        resample_sink (None without `same_caption`).  Within a batch, of the `take` leading images, row j is paired with row
-        j + take // 2 for j < take // 2.  A caller that shares one pass between msssim() and other scores makes it first and
-        hands it to both (main.py)."""
-        from .msssim import PairSimilarity
-        size = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1)
-        images = max(1, min(int(num_samples), len(self.data_loader.dataset)))
-        acc = SimpleNamespace(seed=int(seed), scales=int(scales), same_caption=bool(same_caption))
-        acc.figures = {name: PairSimilarity(size, 3, max(1, images // 2), scales, self.device) for name in ("real", "generated")}
-        if same_caption:
-            acc.figures["same_caption"] = PairSimilarity(size, 3, images, scales, self.device)
-
-        def sink(real, fake, take):
-            half = take // 2
-            if half:
-                for name, t in (("real", real), ("generated", fake)):
-                    t = t[:2 * half].float()
-                    acc.figures[name].add(t[:half].contiguous(), t[half:].contiguous())
-
-        def resample_sink(fake, fake_again, take):
-            acc.figures["same_caption"].add(fake[:take].float().contiguous(), fake_again[:take].float().contiguous())
-        acc.sink, acc.resample_sink = sink, resample_sink if same_caption else None
-        return acc
+        """The accumulator msssim() fills, as swd_images() is swd()'s: attngan/msssim.PairFigures for the tree's final resolution and as
+        many pairs as the pass can give"""
+        from .msssim import PairFigures
+        size, images = self.pass_shape(num_samples)
+        return PairFigures(size, 3, images, scales, same_caption, seed, self.device)
 
     def msssim(self, split_dir, num_samples=30000, seed=100, scales=5, same_caption=True, images=None):
         """Multi-scale structural similarity between PAIRS of images (Wang et al. 2003 as Odena et al. 2017 use it; DESIGN.md section
@@ -590,13 +642,7 @@ class CheckpointEvaluation(object):
         <NET_G minus .pth>/<split>/msssim.json and returns its content."""
         if net_g_missing():
             return None
-        if images is None:
-            images = self.msssim_images(num_samples, seed, scales, same_caption)
-            self.pool_codes(split_dir, num_samples, seed, want_real=False, image_sink=images.sink, trunk=False,
-                            resample_sink=images.resample_sink)
-        elif (images.seed, images.scales, images.same_caption) != (int(seed), int(scales), bool(same_caption)):
-            raise ValueError("msssim: the images handed over were scored under other parameters (seed, scales, same_caption) = %s"
-                             % ((images.seed, images.scales, images.same_caption),))
+        images = self.fed("msssim", split_dir, num_samples, images, seed=int(seed), scales=int(scales), same_caption=bool(same_caption))
         if any(f.n < 1 for f in images.figures.values()):
             raise ValueError("msssim: the data loader gave no pair of images")
         out = {}
@@ -604,29 +650,26 @@ class CheckpointEvaluation(object):
             res = f.result()
             out[name] = {"mean": res["mean"], "std": res["std"], "ssim": res["ssim"], "cs": res["cs"], "pairs": res["pairs"],
                          "clamped": res["clamped"]}
-        out.update({"levels": list(images.figures["real"].sizes), "scales": images.scales, "seed": int(seed),
-                    "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E,
-                    "note": "Multi-scale structural similarity between pairs of images, mean and population standard deviation over "
-                            "the pairs, with the per-level means of ssim and cs: trunk-free -- no image encoder is involved.  "
-                            "HIGHER means LESS varied.  real / generated: within a batch row j against row j + take // 2; the "
-                            "batches are sorted by caption length, so a pair's captions are of similar length.  same_caption: "
-                            "two images for one caption, boxes and labels under independent noise; near 1 means the generator "
-                            "ignores its noise.  A pair with a negative level mean scores 0 and is counted as clamped.  The images "
-                            "enter as fp32 in [-1, 1], not quantised to 8 bits."})
-        save_dir = eval_save_dir(split_dir)
-        write_json(save_dir, "msssim", out)
+        out.update({"levels": list(images.figures["real"].sizes), "scales": images.scales})
+        save_dir = write_score(
+            split_dir, "msssim", out, seed,
+            "Multi-scale structural similarity between pairs of images, mean and population standard deviation over "
+            "the pairs, with the per-level means of ssim and cs: trunk-free -- no image encoder is involved.  "
+            "HIGHER means LESS varied.  real / generated: within a batch row j against row j + take // 2; the "
+            "batches are sorted by caption length, so a pair's captions are of similar length.  same_caption: "
+            "two images for one caption, boxes and labels under independent noise; near 1 means the generator "
+            "ignores its noise.  A pair with a negative level mean scores 0 and is counted as clamped.  The images "
+            "enter as fp32 in [-1, 1], not quantised to 8 bits.")
         print("MS-SSIM (%d scales; mean +- std over pairs): %s -> %s/msssim.json"
               % (images.scales, ", ".join("%s %.4f +- %.4f (%d pairs)" % (k, out[k]["mean"], out[k]["std"], out[k]["pairs"])
                                           for k in ("real", "generated", "same_caption") if k in out), save_dir))
         return out
 
     def spectrum_images(self, num_samples=30000, seed=100, window="hann"):
-        """The accumulator spectrum() fills: attngan/spectrum.RadialSpectrum for the tree's final resolution and as many images as
-        the pass will see, whose `sink` is the (real, fake, take) callable pool_codes' image_sink wants.  A caller that shares one
-        pass between spectrum() and other scores makes it first and hands it to both (main.py)."""
+        """The accumulator spectrum() fills, as swd_images() is swd()'s: attngan/spectrum.RadialSpectrum for the tree's final resolution
+        and as many images as the pass will see"""
         from .spectrum import RadialSpectrum
-        size = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1)
-        images = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        size, images = self.pass_shape(num_samples)
         return RadialSpectrum(size, 3, images, window, self.device, seed=seed)
 
     def spectrum(self, split_dir, num_samples=30000, seed=100, window="hann", images=None):
@@ -642,28 +685,22 @@ class CheckpointEvaluation(object):
         from .spectrum import window_name
         if net_g_missing():
             return None
-        if images is None:
-            images = self.spectrum_images(num_samples, seed, window)
-            self.pool_codes(split_dir, num_samples, seed, want_real=False, image_sink=images.sink, trunk=False)
-        elif (images.seed, images.window) != (int(seed), window_name(window)):
-            raise ValueError("spectrum: the images handed over were scored under other parameters (seed, window) = %s"
-                             % ((images.seed, images.window),))
+        images = self.fed("spectrum", split_dir, num_samples, images, seed=int(seed), window=window_name(window))
         if images.n < 1:
             raise ValueError("spectrum: the data loader gave no batch")
         out = images.result()
         n = out.pop("n")
-        out.update({"size": images.size, "window": images.window, "n_real": n, "n_fake": n, "seed": int(seed),
-                    "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E,
-                    "note": "Radial (azimuthally averaged) power spectrum of the luminance of the real and the generated images, in dB "
-                            "per bin of integer radius, with the log-spectral distance lsd_db, the ratio of the power above a "
-                            "quarter of the sampling frequency hf_db (positive: too much fine-scale power -- noise, grids; negative: "
-                            "blur), the spectral slopes and the bin of the largest excess with its period in pixels: trunk-free -- "
-                            "no image encoder is involved.  Every figure depends on the window (%s) and is comparable under the "
-                            "same window only.  The images enter as fp32 in [-1, 1], not quantised to 8 bits.  Bins beyond S / 2 "
-                            "cover partial rings only (the corners of the frequency square; the period-2 checkerboard is the last "
-                            "bin)." % images.window})
-        save_dir = eval_save_dir(split_dir)
-        write_json(save_dir, "spectrum", out)
+        out.update({"size": images.size, "window": images.window, "n_real": n, "n_fake": n})
+        save_dir = write_score(
+            split_dir, "spectrum", out, seed,
+            "Radial (azimuthally averaged) power spectrum of the luminance of the real and the generated images, in dB "
+            "per bin of integer radius, with the log-spectral distance lsd_db, the ratio of the power above a "
+            "quarter of the sampling frequency hf_db (positive: too much fine-scale power -- noise, grids; negative: "
+            "blur), the spectral slopes and the bin of the largest excess with its period in pixels: trunk-free -- "
+            "no image encoder is involved.  Every figure depends on the window (%s) and is comparable under the "
+            "same window only.  The images enter as fp32 in [-1, 1], not quantised to 8 bits.  Bins beyond S / 2 "
+            "cover partial rings only (the corners of the frequency square; the period-2 checkerboard is the last "
+            "bin)." % images.window)
         def shown(v, form):                                     # a figure none of whose bins holds power is None
             return "n/a" if v is None else form % v
         print("Spectrum (%d real, %d generated images; window %s): LSD %.4f dB, HF %s dB, slopes %s / %s dB per decade, peak "
@@ -674,12 +711,10 @@ class CheckpointEvaluation(object):
 
     def scene_fid_objects(self, num_samples=30000, seed=100, min_side=1):
         """The accumulator scene_fid() fills: attngan/scenefid.ObjectCodes for the tree's final resolution, as many images as the
-        pass will see and the loader's batch size as the one batch shape the trunk runs at, with `sink`, the (real, fake, tm, take,
-        image_encoder) callable of pool_codes' object_sink.  A caller that shares one pass between scene_fid() and other scores
-        makes it first and hands it to both (main.py)."""
+        pass will see and the loader's batch size as the one batch shape the trunk runs at, whose `sink` is the (real, fake, tm, take,
+        image_encoder) callable of pool_codes' object_sink; shared as swd_images() is"""
         from .scenefid import ObjectCodes
-        size = cfg.TREE.BASE_SIZE << (cfg.TREE.BRANCH_NUM - 1)
-        images = max(1, min(int(num_samples), len(self.data_loader.dataset)))
+        size, images = self.pass_shape(num_samples)
         return ObjectCodes(images, int(self.data_loader.batch_size), size, min_side, seed, self.device)
 
     def scene_fid(self, split_dir, num_samples=30000, seed=100, min_side=1, objects=None, return_codes=False):
@@ -697,12 +732,7 @@ class CheckpointEvaluation(object):
         from .fid import frechet_distance, trunk_digest
         if net_g_missing():
             return None
-        if objects is None:
-            objects = self.scene_fid_objects(num_samples, seed, min_side)
-            self.pool_codes(split_dir, num_samples, seed, want_real=False, object_sink=objects.sink)
-        elif (objects.seed, objects.min_side) != (int(seed), float(min_side)):
-            raise ValueError("scene_fid: the objects handed over were gathered under other parameters (seed, min_side) = %s"
-                             % ((objects.seed, objects.min_side),))
+        objects = self.fed("scene_fid", split_dir, num_samples, objects, seed=int(seed), min_side=float(min_side))
         real, fake = objects.finish()
         n = objects.n
         if n < 2:
@@ -721,10 +751,8 @@ class CheckpointEvaluation(object):
             print("SceneFID: %d objects for %d features -- the covariances are rank-deficient, the figure is biased and only "
                   "comparable at equal n (the JSON records it)" % (n, D))
         out = dict(terms, scene_fid=dist)
-        out.update({"n_objects": int(n), "n_images": int(objects.n_images), "min_side": objects.min_side, "seed": int(seed),
-                    "NET_G": cfg.TRAIN.NET_G, "NET_E": cfg.TRAIN.NET_E, "trunk_digest": digest, "note": note})
-        save_dir = eval_save_dir(split_dir)
-        write_json(save_dir, "scene_fid", out)
+        out.update({"n_objects": int(n), "n_images": int(objects.n_images), "min_side": objects.min_side, "trunk_digest": digest})
+        save_dir = write_score(split_dir, "scene_fid", out, seed, note)
         print("SceneFID (%d objects of %d images, real and generated): %.4f = |dmu|^2 %.4f + Tr S_real %.4f + Tr S_fake %.4f - 2 x %.4f "
               "-> %s/scene_fid.json" % (n, objects.n_images, dist, terms["mean_sq"], terms["tr_s1"], terms["tr_s2"], terms["tr_sqrt"],
                                         save_dir))
@@ -785,6 +813,10 @@ class CheckpointEvaluation(object):
             np.random.set_state(states[1])
         return NeighbourBank(codes.cpu(), np.arange(rows), own, name)
 
+    def thumbnails(self, num_samples=30000, seed=100, show=16):
+        """The accumulator memorisation() draws its grid from: a Thumbnails, or None where no row is shown"""
+        return Thumbnails() if int(show) > 0 else None
+
     def memorisation(self, split_dir, num_samples=30000, seed=100, bank_path=None, bank_size=None, k=5, show=16, codes=None,
                      bank=None, return_codes=False):
         """Is the checkpoint TRAIN.NET_G reproducing its TRAINING images?  (attngan/memorisation.py has the
@@ -812,9 +844,8 @@ class CheckpointEvaluation(object):
         if k < 1 or k > 8 or show < 0:
             raise ValueError("memorisation: 1 <= k <= 8 and show >= 0 expected, got k = %d, show = %d" % (k, show))
         if codes is None:
-            thumbs = Thumbnails() if show > 0 else None
-            codes = self.pool_codes(split_dir, num_samples, seed, image_sink=None if thumbs is None else thumbs.sink)
-            codes = dict(codes, thumbnails=thumbs)
+            thumbs = self.thumbnails(show=show)
+            codes = dict(self.shared_pass(split_dir, num_samples, seed, {"memorisation": thumbs}), thumbnails=thumbs)
         c = PooledCodes(self, "memorisation", split_dir, num_samples, seed, codes)
         thumbs = codes.get("thumbnails") if show > 0 else None
         n, D = c.n, int(c.fake.shape[1])

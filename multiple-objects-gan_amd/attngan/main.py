@@ -2,7 +2,10 @@
 (--cfg --gpu --resume --data_dir --manualSeed), plus --synthetic N to train on generated batches when the
 COCO pickles are not present.  One process per GPU: launch with
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 main.py --cfg cfg/coco_train.yml
-(`--gpu` is kept for compatibility; the device comes from LOCAL_RANK)."""
+(`--gpu` is kept for compatibility; the device comes from LOCAL_RANK).
+
+Evaluation (TRAIN.FLAG False): every score of evaluate.SCORES has a flag of its name, `asked_scores` maps the flags to each score's
+keywords, and CheckpointEvaluation.run_scores gives any number of them from one pass.  A new score adds its flags and its entry there."""
 import argparse
 import datetime
 import os
@@ -20,11 +23,13 @@ if __package__ in (None, ""):
     mogan_loader.load()
     from mogan_amd.attngan.miscc.config import cfg, cfg_from_file
     from mogan_amd.attngan.datasets import SyntheticTextDataset, TextDataset
+    from mogan_amd.attngan.evaluate import SCORES
     from mogan_amd.attngan.trainer import condGANTrainer as trainer
     from mogan_amd.hip import lib as hiplib
 else:
     from .miscc.config import cfg, cfg_from_file
     from .datasets import SyntheticTextDataset, TextDataset
+    from .evaluate import SCORES
     from .trainer import condGANTrainer as trainer
     from ..hip import lib as hiplib
 
@@ -120,27 +125,27 @@ def parse_args(argv=None):
     parser.add_argument('--nn_show', type=int, default=16, metavar='M',
                         help='with --memorisation: the M most suspicious generated images are listed and drawn (0: no nn_grid.png)')
     args = parser.parse_args(argv)
-    if args.memorisation and (args.sampling or args.r_precision):
-        parser.error('--memorisation cannot be combined with --sampling or --r_precision')
+    for name in SCORES:
+        if getattr(args, name) and (args.sampling or args.r_precision):
+            parser.error('--%s cannot be combined with --sampling or --r_precision' % name)
     if not 1 <= args.nn_k <= 8:
         parser.error('--nn_k must be in 1..8')
     if args.nn_show < 0 or (args.nn_bank_size is not None and args.nn_bank_size < 2):
         parser.error('--nn_show must not be negative and --nn_bank_size must be 2 at least')
-    if args.spectrum and (args.sampling or args.r_precision):
-        parser.error('--spectrum cannot be combined with --sampling or --r_precision')
-    if args.scene_fid and (args.sampling or args.r_precision):
-        parser.error('--scene_fid cannot be combined with --sampling or --r_precision')
-    if args.msssim and (args.sampling or args.r_precision):
-        parser.error('--msssim cannot be combined with --sampling or --r_precision')
-    if args.swd and (args.sampling or args.r_precision):
-        parser.error('--swd cannot be combined with --sampling or --r_precision')
-    if args.fid and (args.sampling or args.r_precision):
-        parser.error('--fid cannot be combined with --sampling or --r_precision')
-    if args.kid and (args.sampling or args.r_precision):
-        parser.error('--kid cannot be combined with --sampling or --r_precision')
-    if args.prdc and (args.sampling or args.r_precision):
-        parser.error('--prdc cannot be combined with --sampling or --r_precision')
     return args
+
+
+def asked_scores(args):
+    """score -> that score's own keyword arguments, for the scores of evaluate.SCORES whose flag is set, in the table's order"""
+    every = {"scene_fid": dict(min_side=args.scene_fid_min_side),
+             "swd": dict(patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats, min_res=args.swd_min_res),
+             "msssim": dict(scales=args.msssim_scales, same_caption=not args.msssim_no_resample),
+             "spectrum": dict(window=args.spectrum_window),
+             "fid": dict(stats_path=args.fid_stats),
+             "kid": dict(subsets=args.kid_subsets, subset_size=args.kid_subset_size),
+             "prdc": dict(k_pr=args.prdc_k_pr, k_dc=args.prdc_k_dc),
+             "memorisation": dict(bank_path=args.nn_bank, bank_size=args.nn_bank_size, k=args.nn_k, show=args.nn_show)}
+    return {name: every[name] for name in SCORES if getattr(args, name)}
 
 
 def main(argv=None):
@@ -191,8 +196,8 @@ def main(argv=None):
         output_dir = args.resume
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
-    with_bbox = evaluate and not (args.sampling or args.r_precision or args.fid or args.kid or args.prdc or args.swd
-                                 or args.msssim or args.spectrum or args.scene_fid or args.memorisation)
+    asked = asked_scores(args)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or asked)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -215,68 +220,10 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
-    elif args.fid + args.kid + args.prdc + args.swd + args.msssim + args.spectrum + args.scene_fid + args.memorisation > 1:
-        from .evaluate import Thumbnails
-        mem_kw = dict(seed=args.manualSeed, bank_path=args.nn_bank, bank_size=args.nn_bank_size, k=args.nn_k, show=args.nn_show)
-        thumbs = Thumbnails() if args.memorisation and args.nn_show > 0 and cfg.TRAIN.NET_G != '' else None
-        sf_kw = dict(seed=args.manualSeed, min_side=args.scene_fid_min_side)
-        objects = algo.scene_fid_objects(**sf_kw) if args.scene_fid and cfg.TRAIN.NET_G != '' else None
-        ms_kw = dict(seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
-        pairs = algo.msssim_images(**ms_kw) if args.msssim and cfg.TRAIN.NET_G != '' else None
-        swd_kw = dict(seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
-                      min_res=args.swd_min_res)
-        images = algo.swd_images(**swd_kw) if args.swd and cfg.TRAIN.NET_G != '' else None
-        sp_kw = dict(seed=args.manualSeed, window=args.spectrum_window)
-        spectra = algo.spectrum_images(**sp_kw) if args.spectrum and cfg.TRAIN.NET_G != '' else None
-        # one pass over the loader and the trunk for all; --swd, --msssim and --spectrum take the pass's images where the others take
-        # their codes, and the trunk stays out where only those three are asked for; --scene_fid takes the images, their boxes and the
-        # trunk, and the real images' own codes stay out where none of --fid --kid --prdc --memorisation wants them; --memorisation
-        # takes the codes and, for its grid, thumbnails of the generated images
-        sinks = [acc.sink for acc in (images, pairs, spectra, thumbs) if acc is not None]
-
-        def image_sink(real, fake, take):
-            for sink in sinks:
-                sink(real, fake, take)
-        whole = bool(args.fid or args.kid or args.prdc or args.memorisation)
-        codes = algo.pool_codes(split_dir, seed=args.manualSeed, want_real=whole, image_sink=image_sink if sinks else None,
-                                trunk=whole or args.scene_fid,
-                                resample_sink=None if pairs is None else pairs.resample_sink,
-                                object_sink=None if objects is None else objects.sink)
-        if codes is not None:
-            if objects is not None:
-                algo.scene_fid(split_dir, objects=objects, **sf_kw)
-            if images is not None:
-                algo.swd(split_dir, images=images, **swd_kw)
-            if pairs is not None:
-                algo.msssim(split_dir, images=pairs, **ms_kw)
-            if spectra is not None:
-                algo.spectrum(split_dir, images=spectra, **sp_kw)
-            if args.fid:
-                algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats, codes=codes)
-            if args.kid:
-                algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size, codes=codes)
-            if args.prdc:
-                algo.prdc(split_dir, seed=args.manualSeed, k_pr=args.prdc_k_pr, k_dc=args.prdc_k_dc, codes=codes)
-            if args.memorisation:                                    # last: its grid re-reads training images
-                algo.memorisation(split_dir, codes=dict(codes, thumbnails=thumbs), **mem_kw)
-    elif args.fid:
-        algo.fid(split_dir, seed=args.manualSeed, stats_path=args.fid_stats)
-    elif args.kid:
-        algo.kid(split_dir, seed=args.manualSeed, subsets=args.kid_subsets, subset_size=args.kid_subset_size)
-    elif args.prdc:
-        algo.prdc(split_dir, seed=args.manualSeed, k_pr=args.prdc_k_pr, k_dc=args.prdc_k_dc)
-    elif args.swd:
-        algo.swd(split_dir, seed=args.manualSeed, patches=args.swd_patches, dirs=args.swd_dirs, repeats=args.swd_repeats,
-                 min_res=args.swd_min_res)
-    elif args.scene_fid:
-        algo.scene_fid(split_dir, seed=args.manualSeed, min_side=args.scene_fid_min_side)
-    elif args.memorisation:
-        algo.memorisation(split_dir, seed=args.manualSeed, bank_path=args.nn_bank, bank_size=args.nn_bank_size, k=args.nn_k,
-                          show=args.nn_show)
-    elif args.msssim:
-        algo.msssim(split_dir, seed=args.manualSeed, scales=args.msssim_scales, same_caption=not args.msssim_no_resample)
-    elif args.spectrum:
-        algo.spectrum(split_dir, seed=args.manualSeed, window=args.spectrum_window)
+    elif asked:
+        # any number of scores from ONE pass over the loader (evaluate.SCORES says what each takes from it); one score alone runs
+        # its own method, which may then leave out what a shared pass needs (the trunk, the real images' codes)
+        algo.run_scores(split_dir, asked, seed=args.manualSeed)
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:

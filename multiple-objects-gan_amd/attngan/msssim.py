@@ -146,3 +146,30 @@ class PairSimilarity:
         per_level = [[math.fsum(terms[:, j, t].tolist()) / self.n for j in range(len(self.sizes))] for t in (0, 1)]
         return {"mean": mean, "std": std, "ssim": per_level[0], "cs": per_level[1], "levels": list(self.sizes), "pairs": self.n,
                 "clamped": int(clamped.sum())}
+
+
+class PairFigures:
+    """The figures of a pass over real and generated images, one PairSimilarity each under `figures`: "real" and "generated" --
+    within a batch, of the `take` leading images, row j is paired with row j + take // 2 for j < take // 2 -- and, with
+    `same_caption`, "same_caption": every generated image against a second one for the same conditioning.  images: how many images
+    the pass will see at most.  `sink` is the (real, fake, take) callable of pool_codes' image_sink, `resample_sink` the (fake,
+    fake_again, take) callable of its resample_sink (None without `same_caption`); `seed` is kept for the hand-over check only."""
+
+    def __init__(self, size, channels, images, scales=5, same_caption=True, seed=100, device="cuda"):
+        self.seed, self.scales, self.same_caption = int(seed), int(scales), bool(same_caption)
+        self.params = {"seed": self.seed, "scales": self.scales, "same_caption": self.same_caption}      # for the hand-over check
+        self.figures = {name: PairSimilarity(size, channels, max(1, int(images) // 2), scales, device) for name in ("real", "generated")}
+        if self.same_caption:
+            self.figures["same_caption"] = PairSimilarity(size, channels, int(images), scales, device)
+        else:
+            self.resample_sink = None                          # the pass then generates no second image
+
+    def sink(self, real, fake, take):
+        half = take // 2
+        if half:
+            for name, t in (("real", real), ("generated", fake)):
+                t = t[:2 * half].float()
+                self.figures[name].add(t[:half].contiguous(), t[half:].contiguous())
+
+    def resample_sink(self, fake, fake_again, take):
+        self.figures["same_caption"].add(fake[:take].float().contiguous(), fake_again[:take].float().contiguous())

@@ -79,6 +79,7 @@ class ObjectCodes:
             raise ValueError("scenefid: rows, chunk, size and max_objects >= 1 expected, got %d, %d, %d, %d"
                              % (self.rows, self.chunk, self.size, self.max_objects))
         self.min_side, self.seed, self.device = float(min_side), int(seed), torch.device(device)
+        self.params = {"seed": self.seed, "min_side": self.min_side}      # what it was made under: the hand-over check compares it
         self.resize = resize
         self.stage = {k: torch.zeros((self.chunk, 3, TRUNK_SIZE, TRUNK_SIZE), dtype=torch.float32, device=self.device)
                       for k in ("real", "fake")}

@@ -183,6 +183,7 @@ class RadialSpectrum:
         self.size, self.channels, self.images, self.seed = check_size(size), int(channels), int(images), int(seed)
         weight = channel_weights(self.channels)
         self.window = window_name(window)
+        self.params = {"seed": self.seed, "window": self.window}     # what it was made under: the hand-over check compares it
         if self.images < 1:
             raise ValueError("spectrum: room for one image at least expected, got %d" % self.images)
         win = make_window(self.window, self.size)

@@ -153,6 +153,8 @@ class SlicedWasserstein:
                      for side in ("real", "fake")}
         self.rng = {"real": np.random.RandomState(self.seed), "fake": np.random.RandomState(self.seed + 1)}
         self.n = 0                                             # rows filled per level and side
+        self.params = {"seed": self.seed, "patches": self.patches, "dirs": self.dirs, "repeats": self.repeats,
+                       "min_res": self.sizes[-1]}                  # what it was made under: a shared pass's hand-over check compares it
 
     def pyramid(self, batch):
         """the Laplacian levels of an fp32 (B, C, size, size) batch, finest first, each (B, C, s, s)"""
@@ -199,6 +201,10 @@ class SlicedWasserstein:
             for level, table, desc in zip(self.pyramid(batch.detach()), tables, self.desc[side]):
                 ops.swd_gather(level, table, desc, self.n)
         self.n += R
+
+    def sink(self, real, fake, take):
+        """the (real, fake, take) callable of pool_codes' image_sink"""
+        self.add(real[:take].float().contiguous(), fake[:take].float().contiguous())
 
     def result(self):
         import torch
