@@ -837,6 +837,26 @@ size_t mogan_knn_cross_ws_bytes(long long M, long long N, int K);
 int mogan_knn_cross_f64(const float* q, long long M, const float* p, long long N, int D, int K, double* d2, int32_t* idx, void* ws,
                         size_t ws_bytes, hipStream_t stream);
 
+/* mogan_knn_cross_f64 with a label per row: what object accuracy by nearest labelled training crops is computed from (DESIGN.md
+ * section 9m; csrc/mogan_knn.hip, the same two kernels under a template flag; the reference has no code for it).  qlabel (M) and
+ * plabel (N) are int32, arbitrary: a negative label has no special meaning.
+ *   d2, idx (M, K)          exactly mogan_knn_cross_f64's for the same q, p, K, bit for bit; the labels play no part in them
+ *   same_d2, same_idx (M)   the first pair (d2(q_j, p_i), i) under the order above (distance, equal bits by position) among the
+ *                           rows with plabel[i] == qlabel[j]
+ *   other_d2, other_idx (M) the same among the rows with plabel[i] != qlabel[j]
+ * The distances are the ones above (a bit copy is at exactly 0).  An empty set -- a query label the bank does not hold, a bank that
+ * is all of the query's label -- gives +inf and 2^31 - 1; a NaN distance is never listed.  The order is total, so no result depends
+ * on how the support tiles are split into shares; no atomics, no distance matrix, the same bits on every call.  1 <= K <= 8, N >= K.
+ * The workspace is required, 8-byte aligned: mogan_knn_cross_f64's followed by the shares' two pairs per query,
+ *   mogan_knn_label_ws_bytes(M, N, K) = mogan_knn_cross_ws_bytes(M, N, K) + 24 shares M             (0 for arguments the call rejects)
+ * MOGAN_ERR_WS where ws is NULL, misaligned or shorter, nothing launched.  MOGAN_ERR_SHAPE before any HIP call (and before the
+ * workspace is looked at): a NULL q / qlabel / p / plabel / d2 / idx / same_d2 / same_idx / other_d2 / other_idx, K < 1, K > 8,
+ * N < K, M < 1, M or N > 2^31 - 1, D < 1, D > 65536. */
+size_t mogan_knn_label_ws_bytes(long long M, long long N, int K);
+int mogan_knn_label_f64(const float* q, const int32_t* qlabel, long long M, const float* p, const int32_t* plabel, long long N, int D,
+                        int K, double* d2, int32_t* idx, double* same_d2, int32_t* same_idx, double* other_d2, int32_t* other_idx,
+                        void* ws, size_t ws_bytes, hipStream_t stream);
+
 /* The sliced Wasserstein distance of Karras et al. 2018 between real and generated images (DESIGN.md section 9g;
  * csrc/mogan_swd.hip; the reference has no code for it): Laplacian pyramid, 7 x 7 descriptors, their moments, their projections
  * and the sum of |a - b| per direction; the sort in between is the caller's.  All images and descriptors are fp32 and dense.  No

@@ -31,6 +31,15 @@
 // walks the support tiles of its share; the selecting thread keeps the 8 first (d2, i) pairs in registers under the lexicographic
 // order `before` (by distance, equal bits by position), which is a total order on the pairs of a row: the K first of a set of
 // pairs do not depend on how it was partitioned, so cross_merge_kernel merges the shares' lists under the same order.
+//
+// LABEL (mogan_knn_label_f64): the same two kernels with an int32 label per query and per bank row.  Beside
+// the K list, which the labels play no part in, a selecting thread keeps the first pair under `before` among the rows of its
+// query's label and the first among all other rows -- two more (d2, i) pairs in registers, the tile's 64 bank labels in LDS.  The
+// first of a set under a total order does not depend on the partition either, so the shares' pairs merge like the lists.  An
+// empty set keeps (+inf, NO_ROW).  The score's rows are short (D = 256, 768), so selection counts: in the LABEL instantiations
+// all four waves select, a quarter of a tile's columns each for the 64 queries, keep their lists over the share's tiles and meet
+// in LDS behind the loop, where wave 0 merges them under the same order (measured: DESIGN.md section 9m).  Without LABEL one wave
+// selects: mogan_knn_cross_f64's path, whose timing that section holds to its parent's.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "mogan_gram64.h"
@@ -199,11 +208,19 @@ __device__ __forceinline__ void insert8(double (&best)[K_MAX], int32_t (&at)[K_M
 // an empty slot: after every pair a set can hold (positions end at 2^31 - 2), so a share of fewer than K columns merges as it is
 constexpr int32_t NO_ROW = 2147483647;
 
-template <bool VEC>
+// LABEL: lab_d / lab_at (shares, M, 2) hold a share's first pair among the rows of the query's label [0] and among the others [1]
+template <bool VEC, bool LABEL>
 __global__ __launch_bounds__(NT) void cross_kernel(const float* __restrict__ q, long long M, const float* __restrict__ p, long long N,
                                                    int D, int K, const double* __restrict__ nq, const double* __restrict__ np,
-                                                   double* __restrict__ part, int32_t* __restrict__ part_at) {
+                                                   double* __restrict__ part, int32_t* __restrict__ part_at,
+                                                   const int32_t* __restrict__ qlabel, const int32_t* __restrict__ plabel,
+                                                   double* __restrict__ lab_d, int32_t* __restrict__ lab_at) {
     __shared__ GramLds sm;
+    int32_t* lab = nullptr;                                            // the tile's bank labels
+    if constexpr (LABEL) {
+        __shared__ int32_t lab_s[CT];
+        lab = lab_s;
+    }
     const int tid = threadIdx.x;
     const GramLane ln;
     const long long r0 = (long long)blockIdx.x * CT;
@@ -225,11 +242,21 @@ __global__ __launch_bounds__(NT) void cross_kernel(const float* __restrict__ q, 
         at[t] = NO_ROW;
     }
     double* dist = &sm[0][0][0];
-    const long long own = r0 + tid;                                    // the query of the selecting thread (tid < 64)
+    // SEL waves select: wave w takes the tile's columns [w CT / SEL, (w + 1) CT / SEL) for the 64 queries, one query per lane
+    constexpr int SEL = LABEL ? NT / CT : 1, COLS = CT / SEL;
+    const int srow = SEL > 1 ? tid & (CT - 1) : tid, sw = SEL > 1 ? tid / CT : 0;      // one wave: the row is the thread
+    const bool selects = tid < CT * SEL;
+    const long long own = r0 + srow;                                   // the query of a selecting thread
+    double ld[2] = {INFINITY, INFINITY};                               // [0] the query's label, [1] any other
+    int32_t la[2] = {NO_ROW, NO_ROW};
+    int32_t ql = 0;
+    if constexpr (LABEL) ql = own < M ? qlabel[own] : 0;
     f64x4 acc[2][2];
     for (long long bt = t_lo; bt < t_hi; ++bt) {
         const long long c0 = bt * CT;
         gram_tile<VEC>(q, M, r0, p, N, c0, D, false, sm, acc);
+        if constexpr (LABEL)
+            if (tid < CT) lab[tid] = c0 + tid < N ? plabel[c0 + tid] : 0;
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             const int cl = ln.col(0, n);
@@ -240,15 +267,61 @@ __global__ __launch_bounds__(NT) void cross_kernel(const float* __restrict__ q, 
                 for (int j = 0; j < 4; ++j) dist[ln.row(0, m, j) * LDD + cl] = sqdist(na[m * 4 + j], nb, acc[m][n][j]);
         }
         __syncthreads();
-        if (tid < CT) {
+        if (selects) {
             const long long lim = N - c0 < CT ? N - c0 : CT;
-            for (int c = 0; c < (int)lim; ++c) {
-                const double v = dist[tid * LDD + c];
+            const int c_hi = SEL > 1 && (sw + 1) * COLS < (int)lim ? (sw + 1) * COLS : (int)lim;
+            for (int c = sw * COLS; c < c_hi; ++c) {
+                const double v = dist[srow * LDD + c];
                 const int32_t i = (int32_t)(c0 + c);
                 if (before(v, i, best[K_MAX - 1], at[K_MAX - 1])) insert8(best, at, v, i);
+                if constexpr (LABEL) {
+                    const bool mine = lab[c] == ql;
+                    const bool first = before(v, i, mine ? ld[0] : ld[1], mine ? la[0] : la[1]);
+                    if (first && mine) { ld[0] = v; la[0] = i; }
+                    if (first && !mine) { ld[1] = v; la[1] = i; }
+                }
             }
         }
         __syncthreads();
+    }
+    if constexpr (SEL > 1) {
+        // the waves' lists of a query meet in LDS (the distance tile is free behind the loop's last barrier) and wave 0 merges them
+        // under the same order: [wave - 1][slot][query], the K lists' K_MAX slots first, then the two label pairs
+        constexpr int SLOTS = K_MAX + 2;
+        static_assert((SEL - 1) * SLOTS * CT * 3 <= 2 * 2 * KC * LDW, "the waves' lists live in the staging image");
+        double* md = dist;
+        int32_t* mi = (int32_t*)(dist + (SEL - 1) * SLOTS * CT);
+        if (sw > 0) {
+            const int o = (sw - 1) * SLOTS * CT + srow;
+#pragma unroll
+            for (int t = 0; t < K_MAX; ++t) {
+                md[o + t * CT] = best[t];
+                mi[o + t * CT] = at[t];
+            }
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                md[o + (K_MAX + w) * CT] = ld[w];
+                mi[o + (K_MAX + w) * CT] = la[w];
+            }
+        }
+        __syncthreads();
+        if (sw == 0) {
+            for (int s = 0; s < SEL - 1; ++s) {
+                const int o = s * SLOTS * CT + srow;
+#pragma unroll
+                for (int t = 0; t < K_MAX; ++t) {
+                    const double v = md[o + t * CT];
+                    const int32_t i = mi[o + t * CT];
+                    if (before(v, i, best[K_MAX - 1], at[K_MAX - 1])) insert8(best, at, v, i);
+                }
+#pragma unroll
+                for (int w = 0; w < 2; ++w) {
+                    const double v = md[o + (K_MAX + w) * CT];
+                    const int32_t i = mi[o + (K_MAX + w) * CT];
+                    if (before(v, i, ld[w], la[w])) { ld[w] = v; la[w] = i; }
+                }
+            }
+        }
     }
     if (tid < CT && own < M) {
         const size_t o = ((size_t)blockIdx.y * (size_t)M + (size_t)own) * K;
@@ -258,12 +331,21 @@ __global__ __launch_bounds__(NT) void cross_kernel(const float* __restrict__ q, 
                 part[o + t] = best[t];
                 part_at[o + t] = at[t];
             }
+        if constexpr (LABEL) {
+            const size_t l = ((size_t)blockIdx.y * (size_t)M + (size_t)own) * 2;
+            lab_d[l] = ld[0]; lab_d[l + 1] = ld[1];
+            lab_at[l] = la[0]; lab_at[l + 1] = la[1];
+        }
     }
 }
 
+template <bool LABEL>
 __global__ __launch_bounds__(NT) void cross_merge_kernel(const double* __restrict__ part, const int32_t* __restrict__ part_at,
                                                          long long M, int K, int shares, double* __restrict__ d2,
-                                                         int32_t* __restrict__ idx) {
+                                                         int32_t* __restrict__ idx, const double* __restrict__ lab_d,
+                                                         const int32_t* __restrict__ lab_at, double* __restrict__ same_d2,
+                                                         int32_t* __restrict__ same_idx, double* __restrict__ other_d2,
+                                                         int32_t* __restrict__ other_idx) {
     const long long row = (long long)blockIdx.x * NT + threadIdx.x;
     if (row >= M) return;
     double best[K_MAX];
@@ -288,6 +370,21 @@ __global__ __launch_bounds__(NT) void cross_merge_kernel(const double* __restric
             d2[o + t] = best[t];
             idx[o + t] = at[t];
         }
+    if constexpr (LABEL) {
+        double ld[2] = {INFINITY, INFINITY};
+        int32_t la[2] = {NO_ROW, NO_ROW};
+        for (int s = 0; s < shares; ++s) {
+            const size_t l = ((size_t)s * (size_t)M + (size_t)row) * 2;
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                const double v = lab_d[l + w];
+                const int32_t i = lab_at[l + w];
+                if (before(v, i, ld[w], la[w])) { ld[w] = v; la[w] = i; }
+            }
+        }
+        same_d2[row] = ld[0]; same_idx[row] = la[0];
+        other_d2[row] = ld[1]; other_idx[row] = la[1];
+    }
 }
 
 // SIDE 0: the radius belongs to the support point (r2 (N, R), by column); SIDE 1: to the query (r2 (M, R), by row)
@@ -393,6 +490,37 @@ static int launch_norms(const float* x, long long N, int D, double* norms, bool 
 
 static inline size_t up8(size_t b) { return (b + 7) & ~(size_t)7; }
 
+// the launches of mogan_knn_cross_f64 and, with LABEL, of mogan_knn_label_f64, whose workspace is the former's followed by the
+// shares' label pairs: lab_d (shares, M, 2) fp64, lab_at (shares, M, 2) int32
+template <bool LABEL>
+static int launch_cross(const float* q, const int32_t* qlabel, long long M, const float* p, const int32_t* plabel, long long N, int D,
+                        int K, double* d2, int32_t* idx, double* same_d2, int32_t* same_idx, double* other_d2, int32_t* other_idx,
+                        void* ws, hipStream_t stream) {
+    const bool vec = D % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)p & 15) == 0;
+    const int shares = shares_of(M, N);
+    const size_t lists = (size_t)shares * (size_t)M * (size_t)K;
+    double* nq = (double*)ws;
+    double* np = nq + M;
+    double* part = np + N;
+    int32_t* part_at = (int32_t*)(part + lists);
+    double* lab_d = LABEL ? (double*)((char*)part_at + up8(lists * sizeof(int32_t))) : nullptr;
+    int32_t* lab_at = LABEL ? (int32_t*)(lab_d + (size_t)shares * (size_t)M * 2) : nullptr;
+    if (launch_norms(q, M, D, nq, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
+    if (launch_norms(p, N, D, np, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
+    const dim3 grid((unsigned)tiles_of(M), shares);
+    if (vec)
+        hipLaunchKernelGGL((cross_kernel<true, LABEL>), grid, dim3(NT), 0, stream, q, M, p, N, D, K, (const double*)nq,
+                           (const double*)np, part, part_at, qlabel, plabel, lab_d, lab_at);
+    else
+        hipLaunchKernelGGL((cross_kernel<false, LABEL>), grid, dim3(NT), 0, stream, q, M, p, N, D, K, (const double*)nq,
+                           (const double*)np, part, part_at, qlabel, plabel, lab_d, lab_at);
+    if (ok_launch() != 0) return MOGAN_ERR_LAUNCH;
+    hipLaunchKernelGGL(cross_merge_kernel<LABEL>, dim3((unsigned)((M + NT - 1) / NT)), dim3(NT), 0, stream, (const double*)part,
+                       (const int32_t*)part_at, M, K, shares, d2, idx, (const double*)lab_d, (const int32_t*)lab_at, same_d2,
+                       same_idx, other_d2, other_idx);
+    return ok_launch();
+}
+
 }  // namespace
 
 extern "C" {
@@ -467,25 +595,22 @@ int mogan_knn_cross_f64(const float* q, long long M, const float* p, long long N
     if (!q || !p || !d2 || !idx || K < 1 || K > K_MAX || M < 1 || N < (long long)K || M > N_MAX || N > N_MAX || D < 1 || D > D_MAX)
         return MOGAN_ERR_SHAPE;
     if (!ws || ((uintptr_t)ws & 7) != 0 || ws_bytes < mogan_knn_cross_ws_bytes(M, N, K)) return MOGAN_ERR_WS;
-    const bool vec = D % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)p & 15) == 0;
-    const int shares = shares_of(M, N);
-    double* nq = (double*)ws;
-    double* np = nq + M;
-    double* part = np + N;
-    int32_t* part_at = (int32_t*)(part + (size_t)shares * (size_t)M * (size_t)K);
-    if (launch_norms(q, M, D, nq, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
-    if (launch_norms(p, N, D, np, vec, stream) != 0) return MOGAN_ERR_LAUNCH;
-    const dim3 grid((unsigned)tiles_of(M), shares);
-    if (vec)
-        hipLaunchKernelGGL(cross_kernel<true>, grid, dim3(NT), 0, stream, q, M, p, N, D, K, (const double*)nq, (const double*)np,
-                           part, part_at);
-    else
-        hipLaunchKernelGGL(cross_kernel<false>, grid, dim3(NT), 0, stream, q, M, p, N, D, K, (const double*)nq, (const double*)np,
-                           part, part_at);
-    if (ok_launch() != 0) return MOGAN_ERR_LAUNCH;
-    hipLaunchKernelGGL(cross_merge_kernel, dim3((unsigned)((M + NT - 1) / NT)), dim3(NT), 0, stream, (const double*)part,
-                       (const int32_t*)part_at, M, K, shares, d2, idx);
-    return ok_launch();
+    return launch_cross<false>(q, nullptr, M, p, nullptr, N, D, K, d2, idx, nullptr, nullptr, nullptr, nullptr, ws, stream);
+}
+
+size_t mogan_knn_label_ws_bytes(long long M, long long N, int K) {
+    const size_t lists = mogan_knn_cross_ws_bytes(M, N, K);
+    return lists == 0 ? 0 : lists + (size_t)shares_of(M, N) * (size_t)M * 2 * (sizeof(double) + sizeof(int32_t));
+}
+
+int mogan_knn_label_f64(const float* q, const int32_t* qlabel, long long M, const float* p, const int32_t* plabel, long long N, int D,
+                        int K, double* d2, int32_t* idx, double* same_d2, int32_t* same_idx, double* other_d2, int32_t* other_idx,
+                        void* ws, size_t ws_bytes, hipStream_t stream) {
+    if (!q || !qlabel || !p || !plabel || !d2 || !idx || !same_d2 || !same_idx || !other_d2 || !other_idx || K < 1 || K > K_MAX ||
+        M < 1 || N < (long long)K || M > N_MAX || N > N_MAX || D < 1 || D > D_MAX)
+        return MOGAN_ERR_SHAPE;
+    if (!ws || ((uintptr_t)ws & 7) != 0 || ws_bytes < mogan_knn_label_ws_bytes(M, N, K)) return MOGAN_ERR_WS;
+    return launch_cross<true>(q, qlabel, M, p, plabel, N, D, K, d2, idx, same_d2, same_idx, other_d2, other_idx, ws, stream);
 }
 
 }  // extern "C"

@@ -154,6 +154,8 @@ SIGNATURES = {
     "mogan_ball_count_f64": [P, L, P, L, I, P, I, I, P, P, Z, P],
     "mogan_knn_cross_ws_bytes": [L, L, I],
     "mogan_knn_cross_f64": [P, L, P, L, I, I, P, P, P, Z, P],
+    "mogan_knn_label_ws_bytes": [L, L, I],
+    "mogan_knn_label_f64": [P, P, L, P, P, L, I, I, P, P, P, P, P, P, P, Z, P],
     "mogan_pyr_down": [P, L, I, I, P, P],
     "mogan_lap_residual": [P, P, L, I, I, P, P],
     "mogan_swd_gather": [P, I, I, I, I, P, L, P, L, L, P],
@@ -197,7 +199,8 @@ class TailArgs(ctypes.Structure):               # MoganTailArgs
 _RESTYPE = {"mogan_bn_ws_bytes": Z, "mogan_upconv3x3_ws_bytes": Z, "mogan_pk_weight_bytes": Z, "mogan_pk_panel_bytes": Z,
             "mogan_wino_prep_bytes": Z, "mogan_conv_prep_bytes": Z, "mogan_poly3_mmd_ws_bytes": Z,
             "mogan_knn_sqdist_ws_bytes": Z, "mogan_ball_count_ws_bytes": Z, "mogan_swd_moments_ws_bytes": Z,
-            "mogan_ssim_level_ws_bytes": Z, "mogan_knn_cross_ws_bytes": Z, "mogan_radial_power_ws_bytes": Z}
+            "mogan_ssim_level_ws_bytes": Z, "mogan_knn_cross_ws_bytes": Z, "mogan_radial_power_ws_bytes": Z,
+            "mogan_knn_label_ws_bytes": Z}
 _ERRORS = {-1: "MOGAN_ERR_SHAPE", -2: "MOGAN_ERR_LAUNCH", -3: "MOGAN_ERR_WS"}
 
 _lib = None

@@ -1945,6 +1945,40 @@ def knn_cross(q, p, K):
     return d2, idx
 
 
+def knn_label(q, qlabel, p, plabel, K):
+    """knn_cross with an int32 label per row (mogan_knn_label_f64): (d2 (M, K) fp64, idx (M, K) int32, same_d2 (M) fp64, same_idx (M)
+    int32, other_d2 (M) fp64, other_idx (M) int32) on the device.  d2 / idx are knn_cross's bit for bit; same_* is the first pair
+    under the same order (distance, equal bits by position) among the rows of p whose label equals the query's, other_* among the
+    rows whose label differs; an empty set gives +inf and 2^31 - 1.  Labels are arbitrary int32.  No gradient.  Nothing is converted
+    or copied for the caller: knn_cross's checks, and labels that are not int32, dense, on the codes' device, of length M and N are
+    a ValueError."""
+    _codes("knn_label", (("q", q), ("p", p)))
+    K = int(K)
+    M, N, D = q.shape[0], p.shape[0], q.shape[1]
+    if K < 1 or K > 8 or K > N:
+        raise ValueError("knn_label: 1 <= K <= min(8, N) expected, got K = %d for %d rows of p" % (K, N))
+    for name, t, n in (("qlabel", qlabel, M), ("plabel", plabel, N)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32:
+            raise ValueError("knn_label: int32 labels expected, %s is %s" % (name, getattr(t, "dtype", type(t))))
+        if t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
+            raise ValueError("knn_label: dense labels (%d,) expected, %s is %s with strides %s" % (n, name, tuple(t.shape),
+                                                                                                tuple(t.stride())))
+        if t.device != q.device:
+            raise ValueError("knn_label: the labels must be on the codes' device (%s, %s is on %s)" % (q.device, name, t.device))
+    q, p = q.detach(), p.detach()
+    pq, pp = ptr(q), ptr(p)
+    ws, ws_bytes, own = _scratch(q.device, int(lib.load().mogan_knn_label_ws_bytes(M, N, K)))
+    d2 = torch.empty((M, K), dtype=torch.float64, device=q.device)
+    idx = torch.empty((M, K), dtype=torch.int32, device=q.device)
+    same_d2, other_d2 = (torch.empty((M,), dtype=torch.float64, device=q.device) for _ in range(2))
+    same_idx, other_idx = (torch.empty((M,), dtype=torch.int32, device=q.device) for _ in range(2))
+    call("mogan_knn_label_f64", pq, ptr(qlabel), M, pp, ptr(plabel), N, D, K, ptr(d2), ptr(idx), ptr(same_d2), ptr(same_idx),
+         ptr(other_d2), ptr(other_idx), ws, ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(q.device))
+    return d2, idx, same_d2, same_idx, other_d2, other_idx
+
+
 def ball_counts(q, p, r2, side="support"):
     """count (M, R) int32 on the device, count[j, c] = #{ i : d2(q_j, p_i) <= r2[., c] } for fp32 queries q (M, D), fp32 support
     points p (N, D) and fp64 squared radii r2 (mogan_ball_count_f64; the distances are knn_sqdist's, bit for bit).  side

@@ -98,8 +98,13 @@ class CocoTextDataset(data.Dataset):
     EMBEDDINGS = {"cnn-rnn": "char-CNN-RNN-embeddings.pickle", "cnn-gru": "char-CNN-GRU-embeddings.pickle",
                   "skip-thought": "skip-thought-embeddings.pickle"}
 
-    def __init__(self, data_dir, img_dir, imsize, split='train', embedding_type='cnn-rnn', transform=None, crop=True, stage=1):
-        self.transform, self.imsize, self.crop, self.stage = transform, imsize, crop, stage
+    def __init__(self, data_dir, img_dir, imsize, split='train', embedding_type='cnn-rnn', transform=None, crop=True, stage=1,
+                 fixed=False):
+        """fixed (an addition, for stackgan/evaluate.py; needs crop=False): an item draws nothing -- the FIRST embedding of the image,
+        and in stage 2 the data's boxes as both box sets (relative boxes do not change under a plain resize)"""
+        self.transform, self.imsize, self.crop, self.stage, self.fixed = transform, imsize, crop, stage, bool(fixed)
+        if self.fixed and crop:
+            raise ValueError("CocoTextDataset: fixed items are uncropped items, crop=False expected")
         self.data_dir, self.img_dir = data_dir, img_dir
         self.split_dir = os.path.join(data_dir, split)
         self.max_objects = 3
@@ -119,6 +124,8 @@ class CocoTextDataset(data.Dataset):
         img = self.get_img(self.img_dir + "/" + key + ".jpg")
         bbox, label = self.bboxes[index], self.labels[index]
         embeddings = self.embeddings[index, :, :]
+        if self.fixed:
+            return img, ([bbox, bbox.copy()] if self.stage != 1 else bbox), label, embeddings[0, :]
         embedding = embeddings[random.randint(0, embeddings.shape[0] - 1), :]
         if self.crop:
             img, bbox = crop_imgs(img, bbox, self.imsize, self.stage, self.max_objects)
@@ -135,8 +142,9 @@ CLEVR_COLORS = {"gray": 0, "red": 1, "blue": 2, "green": 3, "brown": 4, "purple"
 class ClevrTextDataset(data.Dataset):
     """code/clevr/miscc/datasets.py TextDataset: one scene json per item; the flip is drawn per image load."""
 
-    def __init__(self, data_dir, imsize, split='train', transform=None):
-        self.transform, self.imsize, self.data_dir = transform, imsize, data_dir
+    def __init__(self, data_dir, imsize, split='train', transform=None, flip=True):
+        """flip=False (an addition, for stackgan/evaluate.py): no image is flipped and nothing is drawn"""
+        self.transform, self.imsize, self.data_dir, self.flip = transform, imsize, data_dir, bool(flip)
         self.split_dir = os.path.join(data_dir, split)
         self.img_dir = os.path.join(self.split_dir, "images")
         self.scene_dir = os.path.join(self.split_dir, "scenes")
@@ -149,7 +157,7 @@ class ClevrTextDataset(data.Dataset):
         img = Image.open(img_path).convert('RGB')
         if self.transform is not None:
             img = self.transform(img)
-        flip_img = random.random() < 0.5
+        flip_img = self.flip and random.random() < 0.5
         if flip_img:
             img = torch.flip(img, dims=[2])
         return img, flip_img

@@ -19,6 +19,21 @@ from ..hip import ops
 from . import losses
 
 
+def generate(netG, variant, stage, b):
+    """The generator call of the family, written once for the train step and for stackgan/evaluate.py's pass: (fake, mu, logvar) of
+    the batch fields `b` (StackGANEngine's); mu and logvar are None for the trees without text."""
+    if variant.text and stage == 2:
+        _, fake, mu, logvar, _ = netG(b["txt_embedding"], b["z"], b["tmi"], b["tm_s2"], b["tmi_s2"],
+                                      b["label_one_hot"], eps=b.get("eps"), eps_s1=b.get("eps_s1"))
+    elif variant.text:
+        _, fake, mu, logvar, _ = netG(b["txt_embedding"], b["z"], b["tmi"], b["label_one_hot"],
+                                      eps=b.get("eps"))
+    else:
+        out = netG(b["z"], b["tmi"], b["label_one_hot"])
+        fake, mu, logvar = (out[1] if isinstance(out, tuple) else out), None, None
+    return fake, mu, logvar
+
+
 class StackGANEngine:
     """`variant` is one of nets.COCO / CLEVR / MNIST; `stage` 1 or 2 (stage 2 exists for coco only).
     Batch fields (device tensors): real_imgs, z, tm, tmi, label_one_hot and, for coco, txt_embedding,
@@ -52,17 +67,7 @@ class StackGANEngine:
         flat.step(grad_scale=1.0 / self.world)
 
     def generate(self, b):
-        v = self.variant
-        if v.text and self.stage == 2:
-            _, fake, mu, logvar, _ = self.netG(b["txt_embedding"], b["z"], b["tmi"], b["tm_s2"], b["tmi_s2"],
-                                               b["label_one_hot"], eps=b.get("eps"), eps_s1=b.get("eps_s1"))
-        elif v.text:
-            _, fake, mu, logvar, _ = self.netG(b["txt_embedding"], b["z"], b["tmi"], b["label_one_hot"],
-                                               eps=b.get("eps"))
-        else:
-            out = self.netG(b["z"], b["tmi"], b["label_one_hot"])
-            fake, mu, logvar = (out[1] if isinstance(out, tuple) else out), None, None
-        return fake, mu, logvar
+        return generate(self.netG, self.variant, self.stage, b)
 
     def device_step(self, b):
         v, netG, netD = self.variant, self.netG, self.netD
