@@ -364,7 +364,8 @@ int mogan_upconv3x3_dgrad(const float* dy, const float* w, float* dx, int B, int
                           size_t ws_bytes, hipStream_t stream);
 int mogan_upconv3x3_wgrad(const float* dy, const float* x, float* dw, int B, int Cin, int Hs, int Ws, int Cout,
                           int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
-/* backward of nearest x2 upsample: dx[b,c,y,x] = sum of the 2x2 block of du (B*C planes of 2H x 2W) */
+/* backward of nearest x2 upsample: dx[b,c,y,x] = sum of the 2x2 block of du (B*C planes of 2H x 2W).
+ * MOGAN_ERR_SHAPE before any HIP call: planes, H or W <= 0, a NULL du or dx. */
 int mogan_down2_sum(const float* du, float* dx, int planes, int H, int W, hipStream_t stream);
 
 /* generic strided batched GEMM: C[z][m][n] (+)= sum_k A[z][m][k] * B[z][k][n]; strides in elements.
@@ -434,7 +435,9 @@ int mogan_act_bwd(const float* x, const float* dy, float* dx, int B, int C, int 
 /* y (rows,C,HW) += bias[C];  dbias[c] (+)= sum over rows,HW of dy */
 int mogan_bias_add(float* y, const float* bias, int rows, int C, int HW, hipStream_t stream);
 int mogan_bias_grad(const float* dy, float* dbias, int rows, int C, int HW, int accumulate, hipStream_t stream);
-/* y = a + b (n elements); y = a*alpha */
+/* y = a + b (n elements); y = a*alpha.  These two and the group pair below: plain IEEE fp32 operations, one per element and
+ * group.  n == 0 is answered first, with 0 and without a launch (an empty tensor's pointer is NULL).
+ * MOGAN_ERR_SHAPE before any HIP call: n < 0, G <= 0, a NULL pointer. */
 int mogan_add(const float* a, const float* b, float* y, long long n, hipStream_t stream);
 /* y = ((x_0 + x_1) + x_2) + ... over the G groups of n values of x (G*n values); backward: dx_g = dy for every group */
 int mogan_group_sum(const float* x, float* y, long long n, int G, hipStream_t stream);
@@ -597,7 +600,14 @@ int mogan_scalar_scale(const float* g, const float* weights, int n, float* const
 /* ---------------------------------------------------------------- pooling / resize (CNN_ENCODER trunk)
  * max_pool2d(k,s, no padding): fwd records the offset of the first maximum of each window in idx (uint8,
  * same shape as y; nullable), bwd gathers through it (ties -> first, like torch),
- * avg_pool2d(k,s,pad, count_include_pad), bilinear resize (align_corners=0) -- model.py:256,264,271,301 */
+ * avg_pool2d(k,s,pad, count_include_pad), bilinear resize (align_corners=0) -- model.py:256,264,271,301
+ * MOGAN_ERR_SHAPE before any HIP call:
+ *   mogan_maxpool_fwd(_ex): planes (B, C), k or s <= 0, H < k, W < k, k*k > 255 (idx holds a*k+b in a byte), a NULL x or y;
+ *   mogan_maxpool_bwd(_ex): the same list, k > 2 s (the gather form reads at most 2 x 2 windows), a NULL idx, dy or dx
+ *                           (relu_of is nullable);
+ *   mogan_avgpool_fwd, mogan_avgpool_bwd(_ex): k or s <= 0 (before anything is divided), pad < 0, 2 pad > k (as torch),
+ *                           planes, H or W <= 0, H + 2 pad < k, W + 2 pad < k, a NULL x / y or dy / dx (relu_of is nullable);
+ *   mogan_bilinear_fwd, mogan_bilinear_bwd: planes, H, W, OH or OW <= 0, a NULL pointer. */
 int mogan_maxpool_fwd(const float* x, float* y, uint8_t* idx, int planes, int H, int W, int k, int s,
                       hipStream_t stream);
 int mogan_maxpool_bwd(const uint8_t* idx, const float* dy, float* dx, int planes, int H, int W, int k, int s,
@@ -615,9 +625,10 @@ int mogan_maxpool_bwd_ex(const uint8_t* idx, const float* dy, long long dy_bstri
                          int accumulate, int B, int C, int H, int W, int k, int s, hipStream_t stream);
 int mogan_avgpool_bwd_ex(const float* dy, float* dx, const float* relu_of, int accumulate, int planes, int H, int W, int k,
                          int s, int pad, hipStream_t stream);
-/* dx (+)= dz where z > 0 (z: the ReLU's output) */
+/* dx (+)= dz where z > 0 (z: the ReLU's output).  MOGAN_ERR_SHAPE before any HIP call: n <= 0, a NULL pointer. */
 int mogan_relu_bwd(const float* z, const float* dz, float* dx, long long n, int accumulate, hipStream_t stream);
-/* B rows of n contiguous floats between two batch-strided tensors */
+/* B rows of n contiguous floats between two batch-strided tensors.  MOGAN_ERR_SHAPE before any HIP call: B or n <= 0,
+ * a NULL src or dst. */
 int mogan_copy_strided(const float* src, long long src_bstride, float* dst, long long dst_bstride, int B, long long n,
                        hipStream_t stream);
 int mogan_bilinear_fwd(const float* x, float* y, int planes, int H, int W, int OH, int OW, hipStream_t stream);
@@ -631,7 +642,11 @@ int mogan_bilinear_bwd(const float* dy, float* dx, int planes, int H, int W, int
  * resample:  Pillow's antialiased BILINEAR resize of the square u8 image `in` (B,S,S,3) to OS x OS (transforms.Resize),
  *            then ToTensor + Normalize -> out (B,3,OS,OS) f32.  bounds (OS,2) / kk (OS,ksize): Pillow's coefficient
  *            tables (precompute_coeffs + normalize_coeffs_8bpc, 22-bit fixed point; the same table serves both passes of
- *            a square resize), built by the host (attngan/feeder.py); tmp (B,S,OS,3) u8 scratch.  Bit-identical to PIL. */
+ *            a square resize), built by the host (attngan/feeder.py); tmp (B,S,OS,3) u8 scratch.  Bit-identical to PIL.
+ * MOGAN_ERR_SHAPE before any HIP call: crop_flip: B or size <= 0, ori < size, a NULL src, params, q or out;
+ *            resample: B, S, OS or ksize <= 0, a NULL in, tmp, out, bounds or kk.
+ * The crop offsets live on the device and cannot be checked by the host: 0 <= h1, w1 <= ori - size is the caller's
+ * contract (attngan/feeder.draw_crop keeps it). */
 int mogan_feed_crop_flip(const uint8_t* src, const int32_t* params, uint8_t* q, float* out, int B, int ori, int size,
                          hipStream_t stream);
 int mogan_feed_resample(const uint8_t* in, uint8_t* tmp, float* out, const int32_t* bounds, const int32_t* kk, int ksize,

@@ -643,30 +643,37 @@ int mogan_bias_grad(const float* dy, float* dbias, int rows, int C, int HW, int 
     hipLaunchKernelGGL(bias_grad_kernel, dim3(C), dim3(256), 0, stream, dy, dbias, rows, C, HW, accumulate);
     return ok_launch();
 }
+// The four sums: n == 0 is answered first, with 0 (an empty tensor's pointer is NULL); MOGAN_ERR_SHAPE before any HIP call for
+// n < 0, G <= 0 and a NULL pointer.
 int mogan_add(const float* a, const float* b, float* y, long long n, hipStream_t stream) {
-    if (n <= 0) return n == 0 ? 0 : MOGAN_ERR_SHAPE;
+    if (n == 0) return 0;
+    if (n < 0 || !a || !b || !y) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(add_kernel, dim3(nblk(n)), dim3(256), 0, stream, a, b, y, n);
     return ok_launch();
 }
 // y[i] = ((x[i] + x[n+i]) + x[2n+i]) + ... over the G groups of n values (the object pathways' h_0 + h_1 + h_2, in the loop's
 // order); its backward: every group receives dy
 int mogan_group_sum(const float* x, float* y, long long n, int G, hipStream_t stream) {
-    if (n <= 0 || G <= 0) return n == 0 ? 0 : MOGAN_ERR_SHAPE;
+    if (n == 0) return 0;
+    if (n < 0 || G <= 0 || !x || !y) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(group_sum_kernel, dim3(nblk(n)), dim3(256), 0, stream, x, y, n, G);
     return ok_launch();
 }
 int mogan_group_bcast(const float* dy, float* dx, long long n, int G, hipStream_t stream) {
-    if (n <= 0 || G <= 0) return n == 0 ? 0 : MOGAN_ERR_SHAPE;
+    if (n == 0) return 0;
+    if (n < 0 || G <= 0 || !dy || !dx) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(group_bcast_kernel, dim3(nblk(n)), dim3(256), 0, stream, dy, dx, n, G);
     return ok_launch();
 }
 int mogan_scale(const float* a, float alpha, float* y, long long n, hipStream_t stream) {
-    if (n <= 0) return n == 0 ? 0 : MOGAN_ERR_SHAPE;
+    if (n == 0) return 0;
+    if (n < 0 || !a || !y) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(scale_kernel, dim3(nblk(n)), dim3(256), 0, stream, a, alpha, y, n);
     return ok_launch();
 }
+// MOGAN_ERR_SHAPE before any HIP call: planes, H or W <= 0, a NULL du or dx
 int mogan_down2_sum(const float* du, float* dx, int planes, int H, int W, hipStream_t stream) {
-    if (planes <= 0 || H <= 0 || W <= 0) return MOGAN_ERR_SHAPE;
+    if (planes <= 0 || H <= 0 || W <= 0 || !du || !dx) return MOGAN_ERR_SHAPE;
     const long long n = (long long)planes * H * W;
     hipLaunchKernelGGL(down2_sum_kernel, dim3(nblk(n)), dim3(256), 0, stream, du, dx, n, H, W);
     return ok_launch();
@@ -734,8 +741,9 @@ int mogan_reparam_bwd(const float* logvar, const float* eps, const float* dc, fl
     return ok_launch();
 }
 
+// MOGAN_ERR_SHAPE before any HIP call: n <= 0, a NULL z, dz or dx
 int mogan_relu_bwd(const float* z, const float* dz, float* dx, long long n, int accumulate, hipStream_t stream) {
-    if (n <= 0) return MOGAN_ERR_SHAPE;
+    if (n <= 0 || !z || !dz || !dx) return MOGAN_ERR_SHAPE;
     hipLaunchKernelGGL(relu_bwd_kernel, dim3(nblk(n)), dim3(256), 0, stream, z, dz, dx, n, accumulate);
     return ok_launch();
 }
@@ -786,15 +794,19 @@ int mogan_concat_bwd(const float* ddst, void* const* dsrc, const int* C, const i
 
 int mogan_copy_strided(const float* src, long long src_bstride, float* dst, long long dst_bstride, int B, long long n,
                        hipStream_t stream) {
-    if (B <= 0 || n <= 0) return MOGAN_ERR_SHAPE;
+    if (B <= 0 || n <= 0 || !src || !dst) return MOGAN_ERR_SHAPE;       // (all of it before any HIP call)
     hipLaunchKernelGGL(copy_strided_kernel, dim3(nblk((long long)B * n)), dim3(256), 0, stream, src, src_bstride, dst,
                        dst_bstride, n, (long long)B * n);
     return ok_launch();
 }
 
+// Max pool, all four entry points.  MOGAN_ERR_SHAPE before any HIP call: B, C (planes), k or s <= 0, H < k, W < k, k * k > 255 (the
+// window offset a * k + b is a byte), a NULL x or y (idx is nullable); the backward also: k > 2 s (see the kernel), a NULL idx,
+// dy or dx (relu_of is nullable).
 int mogan_maxpool_fwd_ex(const float* x, float* y, long long y_bstride, uint8_t* idx, int B, int C, int H, int W, int k,
                          int s, hipStream_t stream) {
-    if (B <= 0 || C <= 0 || k <= 0 || s <= 0 || H < k || W < k || k * k > 255) return MOGAN_ERR_SHAPE;
+    if (B <= 0 || C <= 0 || k <= 0 || s <= 0 || H < k || W < k || k > 15) return MOGAN_ERR_SHAPE;      // (k * k <= 255, no overflow)
+    if (!x || !y) return MOGAN_ERR_SHAPE;
     const int OH = (H - k) / s + 1, OW = (W - k) / s + 1;
     if (y_bstride < 0) y_bstride = (long long)C * OH * OW;
     const long long n = (long long)B * C * OH * OW;
@@ -808,7 +820,8 @@ int mogan_maxpool_fwd(const float* x, float* y, uint8_t* idx, int planes, int H,
 }
 int mogan_maxpool_bwd_ex(const uint8_t* idx, const float* dy, long long dy_bstride, float* dx, const float* relu_of,
                          int accumulate, int B, int C, int H, int W, int k, int s, hipStream_t stream) {
-    if (B <= 0 || C <= 0 || k <= 0 || s <= 0 || H < k || W < k || k > 2 * s) return MOGAN_ERR_SHAPE;      // (k <= 2 s: see the kernel)
+    if (B <= 0 || C <= 0 || k <= 0 || s <= 0 || H < k || W < k || k > 15) return MOGAN_ERR_SHAPE;
+    if (k > 2 * (long long)s || !idx || !dy || !dx) return MOGAN_ERR_SHAPE;                                  // (k <= 2 s: see the kernel)
     const int OH = (H - k) / s + 1, OW = (W - k) / s + 1;
     if (dy_bstride < 0) dy_bstride = (long long)C * OH * OW;
     const long long n = (long long)B * C * H * W;
@@ -820,16 +833,23 @@ int mogan_maxpool_bwd(const uint8_t* idx, const float* dy, float* dx, int planes
                       hipStream_t stream) {
     return mogan_maxpool_bwd_ex(idx, dy, -1, dx, nullptr, 0, 1, planes, H, W, k, s, stream);
 }
+// Average pool, all three entry points.  MOGAN_ERR_SHAPE before any HIP call (and before anything is divided): k or s <= 0,
+// pad < 0, 2 pad > k (as torch), planes, H or W <= 0, H + 2 pad < k, W + 2 pad < k (no window fits: with a non-negative numerator
+// C's division is the floor division the callers size y with), a NULL x / y or dy / dx (relu_of is nullable).
+static inline bool avgpool_ok(int planes, int H, int W, int k, int s, int pad) {
+    if (k <= 0 || s <= 0 || pad < 0 || 2 * (long long)pad > k) return false;
+    return planes > 0 && H > 0 && W > 0 && (long long)H + 2 * pad >= k && (long long)W + 2 * pad >= k;
+}
 int mogan_avgpool_fwd(const float* x, float* y, int planes, int H, int W, int k, int s, int pad, hipStream_t stream) {
+    if (!avgpool_ok(planes, H, W, k, s, pad) || !x || !y) return MOGAN_ERR_SHAPE;
     const int OH = (H + 2 * pad - k) / s + 1, OW = (W + 2 * pad - k) / s + 1;
-    if (planes <= 0 || OH <= 0 || OW <= 0) return MOGAN_ERR_SHAPE;
     const long long n = (long long)planes * OH * OW;
     POOL_LAUNCH(avgpool_fwd_kernel, n, dim3(nblk(n)), dim3(256), 0, stream, x, y, n, H, W, OH, OW, k, s, pad);
     return ok_launch();
 }
 int mogan_avgpool_bwd_ex(const float* dy, float* dx, const float* relu_of, int accumulate, int planes, int H, int W, int k,
                          int s, int pad, hipStream_t stream) {
-    if (planes <= 0 || k <= 0 || s <= 0) return MOGAN_ERR_SHAPE;
+    if (!avgpool_ok(planes, H, W, k, s, pad) || !dy || !dx) return MOGAN_ERR_SHAPE;
     const int OH = (H + 2 * pad - k) / s + 1, OW = (W + 2 * pad - k) / s + 1;
     const long long n = (long long)planes * H * W;
     POOL_LAUNCH(avgpool_bwd_kernel, n, dim3(nblk(n)), dim3(256), 0, stream, dy, dx, n, H, W, OH, OW, k, s, pad, relu_of,
@@ -840,14 +860,15 @@ int mogan_avgpool_bwd(const float* dy, float* dx, int planes, int H, int W, int 
                       hipStream_t stream) {
     return mogan_avgpool_bwd_ex(dy, dx, nullptr, 0, planes, H, W, k, s, pad, stream);
 }
+// Bilinear, both ways.  MOGAN_ERR_SHAPE before any HIP call: planes, H, W, OH or OW <= 0, a NULL pointer
 int mogan_bilinear_fwd(const float* x, float* y, int planes, int H, int W, int OH, int OW, hipStream_t stream) {
-    if (planes <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return MOGAN_ERR_SHAPE;
+    if (planes <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || !x || !y) return MOGAN_ERR_SHAPE;
     const long long n = (long long)planes * OH * OW;
     POOL_LAUNCH(bilinear_fwd_kernel, n, dim3(nblk(n)), dim3(256), 0, stream, x, y, n, H, W, OH, OW);
     return ok_launch();
 }
 int mogan_bilinear_bwd(const float* dy, float* dx, int planes, int H, int W, int OH, int OW, hipStream_t stream) {
-    if (planes <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return MOGAN_ERR_SHAPE;
+    if (planes <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || !dy || !dx) return MOGAN_ERR_SHAPE;
     const long long n = (long long)planes * H * W;        // one thread per input element; every element is written
     POOL_LAUNCH(bilinear_bwd_kernel, n, dim3(nblk(n)), dim3(256), 0, stream, dy, dx, n, H, W, OH, OW);
     return ok_launch();

@@ -92,7 +92,8 @@ extern "C" {
 
 int mogan_feed_crop_flip(const uint8_t* src, const int32_t* params, uint8_t* q, float* out, int B, int ori, int size,
                          hipStream_t stream) {
-    if (B <= 0 || size <= 0 || ori < size) return MOGAN_ERR_SHAPE;
+    // all of it before any HIP call.  The crop offsets live on the device: 0 <= h1, w1 <= ori - size is the caller's contract
+    if (B <= 0 || size <= 0 || ori < size || !src || !params || !q || !out) return MOGAN_ERR_SHAPE;
     const long long n = (long long)B * size * size;
     hipLaunchKernelGGL(feed_crop_kernel, dim3(nblk(n)), dim3(256), 0, stream, src, params, q, out, ori, size, n);
     return ok_launch();
@@ -100,7 +101,7 @@ int mogan_feed_crop_flip(const uint8_t* src, const int32_t* params, uint8_t* q, 
 
 int mogan_feed_resample(const uint8_t* in, uint8_t* tmp, float* out, const int32_t* bounds, const int32_t* kk, int ksize,
                         int B, int S, int OS, hipStream_t stream) {
-    if (B <= 0 || S <= 0 || OS <= 0 || ksize <= 0) return MOGAN_ERR_SHAPE;
+    if (B <= 0 || S <= 0 || OS <= 0 || ksize <= 0 || !in || !tmp || !out || !bounds || !kk) return MOGAN_ERR_SHAPE;   // before any HIP call
     const long long nh = (long long)B * S * OS, nv = (long long)B * OS * OS;
     hipLaunchKernelGGL(feed_resample_h_kernel, dim3(nblk(nh)), dim3(256), 0, stream, in, tmp, bounds, kk, ksize, S, S, OS, nh);
     hipLaunchKernelGGL(feed_resample_v_kernel, dim3(nblk(nv)), dim3(256), 0, stream, (const uint8_t*)tmp, out, bounds, kk,
