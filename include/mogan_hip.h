@@ -991,6 +991,32 @@ size_t mogan_radial_power_ws_bytes(int B, int S);
 int mogan_radial_power_f64(const float* x, int B, int C, int S, const float* weight, const float* window, const double* twiddle,
                            const int* bins, int n_bins, double* out, void* ws, size_t ws_bytes, hipStream_t stream);
 
+/* The sums of the layout-shift score: what changes between an image generated under the data's layout and the image generated from
+ * the same noise, text and labels with ONE box moved (csrc/mogan_layout.hip; attngan/layoutshift.py has the
+ * whole definition and the numpy oracle; the reference has no code for it).  a, b (P, C, S, S) fp32, dense: P pairs, a under the
+ * data's layout, b under the edit; edit (P, 6) int32 = (x0, y0, x1, y1, dx, dy): the moved object's pixel rectangle [x0, x1) x
+ * [y0, y1) and its offset in pixels; others (P, G, 4) int32 = (x0, y0, x1, y1), the rectangles of the image's other objects, one
+ * with x1 <= x0 is absent, and they may reach past the image; sums (P, 7) fp64; counts (P, 5) int32.  All on the device.
+ * A pixel's class: 0 the old rectangle only, 1 the new one (old + (dx, dy)) only, 2 both, 3 neither and inside a rectangle of
+ * `others`, 4 the rest.  Per pair, everything after the loads in fp64:
+ *     sums[k]   = sum over the pixels p of class k and the channels of (a[p] - b[p])^2                      k = 0..4
+ *     sums[5]   = sum over the pixels p of the old rectangle and the channels of (a[p] - b[p + delta])^2    "moved"
+ *     sums[6]   = the same with a[p + delta] in the place of b[p + delta]                                   "baseline"
+ *     counts[k] = pixels of class k (they add up to S S)
+ *   One workgroup per pair, its threads striding over the pixels with seven fp64 partials and five counts each, added in LDS in a
+ *   fixed tree; no atomics, no workspace:
+ *     (a) the same inputs give the same bits on every call;
+ *     (b) a pair's outputs depend on its own rows only -- the same bits at P = 1 and at any position of any batch;
+ *     (c) b a bit copy of a gives sums[0..4] == 0.0 exactly and sums[5] == sums[6] bit for bit;
+ *     (d) exchanging a and b changes no bit of sums[0..4];
+ *     (e) delta = (0, 0) gives sums[6] == 0.0.
+ *   Safe by construction: a pair whose edit rectangle is empty or not inside the image, or whose shifted copy is not inside it,
+ *   reads no image data and gets zeros in all twelve outputs.  Every element of sums and counts is written on every call.
+ *   P >= 1, 1 <= C <= 4, 2 <= S <= 1024, 0 <= G <= 8, P C S S <= 2^31 - 1.
+ * MOGAN_ERR_SHAPE before any HIP call: a NULL pointer (others apart where G = 0), any dimension outside the ranges above. */
+int mogan_box_shift_sums_f64(const float* a, const float* b, long long P, int C, int S, const int* edit, const int* others, int G,
+                             double* sums, int* counts, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

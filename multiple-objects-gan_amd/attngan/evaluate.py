@@ -9,7 +9,10 @@ and nothing of the train step.  What these paths have in common is written once 
 device calls (`PooledCodes`, `trunk_note`).
 
 How scores share a pass is written once too (`SCORES`, `shared_pass`, `run_scores`, `fed`): a new score costs its
-method, one row of `SCORES` and -- where it reads the images -- an accumulator with `sink`, optionally `resample_sink`, and `params`."""
+method, one row of `SCORES` and -- where it reads the images -- an accumulator with `sink`, optionally `resample_sink`, and `params`.
+
+`layout_shift` is a mode of its own as `r_precision` is: it generates every image a second time under an edited
+layout (`draw_noise`, `generate_from`, `moved_matrices`), which no shared pass does."""
 import json
 import os
 from collections import namedtuple
@@ -121,11 +124,33 @@ def generate_seeded(netG, gen, words_embs, sent_emb, mask, tmi, label_one_hot):
     """One 256x256 image per caption from the seeded device generator `gen`: `noise` (B, Z_DIM) is drawn first, then the
     conditioning noise `eps` (B, CONDITION_DIM) -- the order is a contract, r_precision and pool_codes see the same images
     under the same seed."""
+    noise, eps = draw_noise(gen, sent_emb)
+    return generate_from(netG, noise, eps, words_embs, sent_emb, mask, tmi, label_one_hot)
+
+
+def draw_noise(gen, sent_emb):
+    """generate_seeded's draws, in its order: (noise (B, Z_DIM), eps (B, CONDITION_DIM)) on sent_emb's device"""
     B = sent_emb.shape[0]
     noise = torch.randn(B, cfg.GAN.Z_DIM, device=sent_emb.device, generator=gen)
     eps = torch.randn(B, cfg.GAN.CONDITION_DIM, device=sent_emb.device, generator=gen)
+    return noise, eps
+
+
+def generate_from(netG, noise, eps, words_embs, sent_emb, mask, tmi, label_one_hot):
+    """generate_seeded's generator call under given draws: layout_shift() calls it twice with one pair of draws and two layouts"""
     fake_imgs, _, _, _ = netG(noise, sent_emb, words_embs, mask, tmi, label_one_hot, eps=eps)
     return fake_imgs[-1]
+
+
+def moved_matrices(tmi, table, boxes=None):
+    """`tmi` (B, G, 2, 3) with the matrix of every moved slot of the edit table (layoutshift.ShiftResponse.edits) replaced by that
+    of its moved box (hip/ops.bbox_to_theta; `boxes` (n, 4) where they are not the table's own); every other slot keeps its bits"""
+    boxes = table["moved"] if boxes is None else boxes
+    out = tmi.clone()
+    if len(table["row"]):
+        inv = ops.bbox_to_theta(boxes.to(tmi.device).float().contiguous())[1]
+        out[table["row"].to(tmi.device), table["slot"].to(tmi.device)] = inv.to(tmi.dtype)
+    return out
 
 
 def trunk_note(what, figure, unit):
@@ -355,7 +380,7 @@ class CheckpointEvaluation(object):
         return out
 
     def pool_codes(self, split_dir, num_samples=30000, seed=100, want_real=True, image_sink=None, trunk=True, resample_sink=None,
-                   object_sink=None):
+                   object_sink=None, generate=None):
         """The one pass over the data loader that the scores share: the real 256x256 image and one generated 256x256 image per
         caption (EMA generator, eval mode, noise from the seeded device generator exactly as r_precision draws it) go through
         CNN_ENCODER.pool_code; the codes stay on the device in two preallocated (num_samples, 2048) fp32 buffers.  `want_real`
@@ -375,7 +400,10 @@ class CheckpointEvaluation(object):
         `object_sink`, where given, is called once per batch with (real, fake, tm, take, image_encoder): the images as for
         `image_sink`, the batch's box matrices `tm` (B, 3, 2, 3) on the device and the pass's image encoder (scene_fid() cuts the
         objects out there and runs the trunk on them).  It needs the trunk: ValueError with trunk=False.  It draws nothing, so
-        every other score's images and codes are those of a pass without it."""
+        every other score's images and codes are those of a pass without it.
+        `generate`, where given, makes a batch's image in generate_seeded's place: it is called with (netG, gen, words_embs, sent_emb,
+        mask, tm, tmi, label_one_hot, keys, take) and owes the pass generate_seeded's draws and image (layout_shift() generates a
+        second image from the same draws there)."""
         from .datasets import prepare_data
         from .fid import trunk_digest
         if object_sink is not None and not trunk:
@@ -404,7 +432,10 @@ class CheckpointEvaluation(object):
             take = min(captions.shape[0], rows - n)
             with torch.no_grad():
                 words_embs, sent_emb, mask = encode_text(text_encoder, captions, cap_lens)
-                fake = generate_seeded(netG, gen, words_embs, sent_emb, mask, tmi, label_one_hot)
+                if generate is None:
+                    fake = generate_seeded(netG, gen, words_embs, sent_emb, mask, tmi, label_one_hot)
+                else:
+                    fake = generate(netG, gen, words_embs, sent_emb, mask, tm, tmi, label_one_hot, keys, take)
                 if resample_sink is not None:
                     resample_sink(fake, generate_seeded(netG, gen_again, words_embs, sent_emb, mask, tmi, label_one_hot), take)
                 if trunk:
@@ -759,6 +790,55 @@ class CheckpointEvaluation(object):
         if return_codes:
             image, box = objects.objects()
             return out, {"real": real.cpu(), "fake": fake.cpu(), "image": image, "box": box}
+        return out
+
+    def layout_shift(self, split_dir, num_samples=30000, seed=100, min_shift=None, min_side=1, show=16, image_sink=None):
+        """Layout control of the checkpoint TRAIN.NET_G by moving ONE box (attngan/layoutshift.py has the
+        definition): every caption's image is generated twice from the same noise, eps, text and labels -- A under the data's `tmi`,
+        bit for bit the image every other score sees under `seed`, and B under `tmi` with only the moved slot's matrix replaced --
+        and hip/ops.box_shift_sums gives, per pair in one launch per batch, how much changed inside the old and the new rectangle,
+        in the other objects and in the rest, and whether the old rectangle's content is found again at the new place (follow = 1)
+        or stayed where it was (follow = 0).  A mode of its own as r_precision() is, not a row of SCORES: it generates a second
+        image under another layout.  No image encoder is loaded.  `image_sink`, where given, is called once per batch with
+        (A, B, edit table, take).  Writes <NET_G minus .pth>/<split>/layout_shift.json and, where show > 0, layout_grid.png -- one row
+        [A with the old box | B with the new box | |A - B|] per pair of most_ignored -- and returns the JSON's content."""
+        from .layoutshift import ShiftResponse, layout_grid
+        from .scenefid import boxes_from_theta
+        if net_g_missing():
+            return None
+        size, rows = self.pass_shape(num_samples)
+        acc = ShiftResponse(size, 3, rows, min_shift, min_side, seed, self.device, keep=show)
+
+        def pair(netG, gen, words_embs, sent_emb, mask, tm, tmi, label_one_hot, keys, take):
+            noise, eps = draw_noise(gen, sent_emb)
+            a = generate_from(netG, noise, eps, words_embs, sent_emb, mask, tmi, label_one_hot)
+            table = acc.edits(boxes_from_theta(tm.cpu()), take)                    # the one read-back of the layout
+            b = generate_from(netG, noise, eps, words_embs, sent_emb, mask, moved_matrices(tmi, table), label_one_hot)
+            acc.add(a.float(), b.float(), table, keys=keys)
+            if image_sink is not None:
+                image_sink(a, b, table, take)
+            return a
+        self.pool_codes(split_dir, num_samples, seed, want_real=False, trunk=False, generate=pair)
+        out = acc.result(show)
+        out.update({"size": size, "show": len(out["most_ignored"]), "grid": None})
+        save_dir = eval_save_dir(split_dir)
+        if acc.kept:
+            out["grid"] = layout_grid(save_dir, acc.kept, acc.info)
+        write_score(
+            split_dir, "layout_shift", out, seed,
+            "Layout control by moving one box: every image is generated twice from the same noise, text and labels, under the data's "
+            "layout (A) and with one object's box moved by at least min_shift pixels (B).  follow = 1 - moved / baseline over the old "
+            "rectangle: 1 -- the object travelled with its box, 0 -- the edit was ignored.  locality: the share of the squared change "
+            "that lies inside the old and the new rectangle; area_share is its chance level.  spill_others / spill_background: the "
+            "mean squared change per pixel in the other objects' rectangles / in the rest, over that of the box pixels.  mean +- "
+            "population std over the pairs; flat (baseline 0), unchanged (B == A), no_objects and immovable are counted.  The images "
+            "enter as fp32 in [-1, 1], not quantised to 8 bits.  Every figure depends on min_shift and min_side.")
+        f, loc = out["follow"], out["locality"]
+        shown = lambda v: "n/a" if v["mean"] is None else "%.4f +- %.4f (%d)" % (v["mean"], v["std"], v["n"])
+        print("Layout shift (%d pairs of %d images; %d without objects, %d immovable, %d unchanged, %d flat; min_shift %d px): follow "
+              "%s, locality %s at area share %s -> %s/layout_shift.json%s"
+              % (out["n_pairs"], out["n_images"], out["no_objects"], out["immovable"], out["unchanged"], out["flat"], out["min_shift"],
+                 shown(f), shown(loc), shown(out["area_share"]), save_dir, "" if out["grid"] is None else " and %s" % out["grid"]))
         return out
 
     def train_split(self):

@@ -5,7 +5,8 @@ COCO pickles are not present.  One process per GPU: launch with
 (`--gpu` is kept for compatibility; the device comes from LOCAL_RANK).
 
 Evaluation (TRAIN.FLAG False): every score of evaluate.SCORES has a flag of its name, `asked_scores` maps the flags to each score's
-keywords, and CheckpointEvaluation.run_scores gives any number of them from one pass.  A new score adds its flags and its entry there."""
+keywords, and CheckpointEvaluation.run_scores gives any number of them from one pass.  A new score adds its flags and its entry there.
+--layout_shift (CheckpointEvaluation.layout_shift) is a mode of its own beside --sampling and --r_precision."""
 import argparse
 import datetime
 import os
@@ -124,10 +125,29 @@ def parse_args(argv=None):
     parser.add_argument('--nn_k', type=int, default=5, metavar='K', help='with --memorisation: training neighbours listed and drawn per image (1..8)')
     parser.add_argument('--nn_show', type=int, default=16, metavar='M',
                         help='with --memorisation: the M most suspicious generated images are listed and drawn (0: no nn_grid.png)')
+    parser.add_argument('--layout_shift', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): layout control by moving ONE box -- every image generated twice from the '
+                             'same noise, text and labels, under the data\'s layout and with one object\'s box moved; does the object '
+                             'travel with its box (follow), and does anything else change (locality, spill)?  '
+                             '(condGANTrainer.layout_shift: no image encoder involved) -> <NET_G minus .pth>/<split>/layout_shift.json '
+                             'and layout_grid.png; a mode of its own: not together with --sampling, --r_precision or any score flag')
+    parser.add_argument('--ls_min_shift', type=int, default=None, metavar='PX',
+                        help='with --layout_shift: the box moves by PX pixels at least along one axis (an eighth of the side by default)')
+    parser.add_argument('--ls_min_side', type=float, default=1, metavar='PX',
+                        help='with --layout_shift: leave out boxes whose shorter side is below PX pixels')
+    parser.add_argument('--ls_show', type=int, default=16, metavar='N',
+                        help='with --layout_shift: the N pairs that followed the edit least are listed and drawn (0: no layout_grid.png)')
     args = parser.parse_args(argv)
-    for name in SCORES:
+    for name in list(SCORES) + ['layout_shift']:
         if getattr(args, name) and (args.sampling or args.r_precision):
             parser.error('--%s cannot be combined with --sampling or --r_precision' % name)
+    for name in SCORES:
+        if getattr(args, name) and args.layout_shift:
+            parser.error('--%s cannot be combined with --layout_shift' % name)
+    if args.ls_show < 0 or (args.ls_min_shift is not None and args.ls_min_shift < 1):
+        parser.error('--ls_show must not be negative and --ls_min_shift must be 1 at least')
+    if not 0 <= args.ls_min_side < float('inf'):                      # NaN fails both comparisons
+        parser.error('--ls_min_side must be a finite number of pixels, 0 at least')
     if not 1 <= args.nn_k <= 8:
         parser.error('--nn_k must be in 1..8')
     if args.nn_show < 0 or (args.nn_bank_size is not None and args.nn_bank_size < 2):
@@ -197,7 +217,7 @@ def main(argv=None):
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
     asked = asked_scores(args)
-    with_bbox = evaluate and not (args.sampling or args.r_precision or asked)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or asked or args.layout_shift)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -220,6 +240,8 @@ def main(argv=None):
         algo.sampling(split_dir)                  # main.py:157 (commented alternative): the whole validation split
     elif args.r_precision:
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
+    elif args.layout_shift:
+        algo.layout_shift(split_dir, seed=args.manualSeed, min_shift=args.ls_min_shift, min_side=args.ls_min_side, show=args.ls_show)
     elif asked:
         # any number of scores from ONE pass over the loader (evaluate.SCORES says what each takes from it); one score alone runs
         # its own method, which may then leave out what a shared pass needs (the trunk, the real images' codes)

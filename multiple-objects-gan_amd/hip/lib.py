@@ -169,6 +169,7 @@ SIGNATURES = {
     "mogan_roi_resize": [P, I, I, I, I, P, P, L, P, I, I, P],
     "mogan_radial_power_ws_bytes": [I, I],
     "mogan_radial_power_f64": [P, I, I, I, P, P, P, P, I, P, P, Z, P],
+    "mogan_box_shift_sums_f64": [P, P, L, I, I, P, P, I, P, P, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }

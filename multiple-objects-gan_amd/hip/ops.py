@@ -2249,6 +2249,53 @@ def roi_resize(x, boxes, image_index, OH, OW, out=None):
     return out
 
 
+def box_shift_sums(a, b, edit, others):
+    """The sums of the layout-shift score in one launch (mogan_box_shift_sums_f64; attngan/layoutshift.py has
+    the definition): fp32 a, b (P, C, S, S) on one device with C in 1..4 and S in 2..1024 -- a generated under the data's layout, b
+    under the edit; edit (P, 6) int32 = (x0, y0, x1, y1, dx, dy) and others (P, G, 4) int32 = (x0, y0, x1, y1), G in 0..8, are HOST
+    tensors -- checked here, then uploaded -- -> (sums (P, 7) fp64, counts (P, 5) int32) on a's device.  No gradient.  Nothing is
+    converted or copied for the caller: a wrong type, dtype, rank, stride or device is a ValueError, and so is a bad rectangle: an
+    edit rectangle that is empty or not inside the image, or whose copy shifted by (dx, dy) is not inside it."""
+    a = _dense_f32("box_shift_sums", "a", a, 4)
+    b = _dense_f32("box_shift_sums", "b", b, 4)
+    P, C, S, S2 = a.shape
+    if tuple(b.shape) != tuple(a.shape) or b.device != a.device:
+        raise ValueError("box_shift_sums: a and b must have one shape and one device, got %s on %s and %s on %s"
+                         % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    if S != S2 or C > 4 or S < 2 or S > 1024 or a.numel() > 2 ** 31 - 1:
+        raise ValueError("box_shift_sums: a (P, 1..4, S, S) with S in 2..1024 and fewer than 2^31 elements expected, got %s"
+                         % (tuple(a.shape),))
+    for name, t, ndim in (("edit", edit, 2), ("others", others, 3)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.device.type != "cpu":
+            raise ValueError("box_shift_sums: %s must be a host tensor of torch.int32, got %s %s"
+                             % (name, getattr(t, "dtype", type(t)), getattr(t, "device", "")))
+        if t.dim() != ndim or not t.is_contiguous():
+            raise ValueError("box_shift_sums: %s must be a contiguous tensor of %d dimensions, got %s with strides %s"
+                             % (name, ndim, tuple(t.shape), tuple(t.stride())))
+    if tuple(edit.shape) != (P, 6) or others.shape[0] != P or others.shape[2] != 4 or others.shape[1] > 8:
+        raise ValueError("box_shift_sums: edit (%d, 6) and others (%d, 0..8, 4) expected, got %s and %s"
+                         % (P, P, tuple(edit.shape), tuple(others.shape)))
+    if a.device.type == "meta":
+        raise ValueError("box_shift_sums: a is a meta tensor")
+    # the legality of an edit row, as attngan/layoutshift._row_ok (the oracle) and the kernel's own guard (csrc/mogan_layout.hip) state it
+    e = edit.to(torch.int64)
+    x0, y0, x1, y1, dx, dy = (e[:, k] for k in range(6))
+    bad = ~((x0 >= 0) & (y0 >= 0) & (x1 > x0) & (y1 > y0) & (x1 <= S) & (y1 <= S)
+            & (x0 + dx >= 0) & (y0 + dy >= 0) & (x1 + dx <= S) & (y1 + dy <= S))
+    if bool(bad.any()):
+        r = int(bad.nonzero()[0])
+        raise ValueError("box_shift_sums: edit row %d, rectangle (%d, %d, %d, %d) moved by (%d, %d), is empty or leaves the %d x %d "
+                         "image" % ((r,) + tuple(int(v) for v in edit[r]) + (S, S)))
+    G = int(others.shape[1])
+    pa, pb = ptr(a), ptr(b)                                    # (a host tensor raises here, before anything is uploaded)
+    both = torch.cat([edit.reshape(-1), others.reshape(-1)]).to(a.device)       # one upload: 24 + 16 G bytes per pair
+    sums = torch.empty((P, 7), dtype=torch.float64, device=a.device)
+    counts = torch.empty((P, 5), dtype=torch.int32, device=a.device)
+    call("mogan_box_shift_sums_f64", pa, pb, P, C, S, ptr(both), (ptr(both) + 24 * P) if G else None, G, ptr(sums), ptr(counts),
+         stream_ptr())
+    return sums, counts
+
+
 _twiddles = {}
 
 

@@ -14,6 +14,9 @@ generator runs in eval mode under no_grad through engine.generate, the train ste
 with text), then eps_s1 (stage II) from ONE seeded device torch.Generator, in that order -- a contract: the images do not depend
 on which scores are asked.  msssim's same_caption ("same layout, labels and text, fresh noise") draws from a second generator
 seeded seed + 1.  A file holds the bytes of its score run alone.
+
+`FamilyEvaluation.layout_shift` (attngan/layoutshift.py has the definition) is a mode of its own, not a row of
+SCORES: a pass that generates every image twice from one set of draws, under the data's layout and with one box moved.
 """
 import json
 import os
@@ -45,13 +48,18 @@ def generate_seeded(netG, variant, stage, cfg, b, gen):
     """One image per item of the prepared batch `b` under noise from the seeded device generator `gen`: z (B, Z_DIM), then for the
     trees with text eps (B, CONDITION_DIM), then in stage II eps_s1 (B, CONDITION_DIM) -- the order is a contract.  `b` keeps its
     own fields: the draws go into a copy."""
+    return generate(netG, variant, stage, draw_noise(variant, stage, cfg, b, gen))[0]
+
+
+def draw_noise(variant, stage, cfg, b, gen):
+    """generate_seeded's draws, in its order, in a copy of the prepared batch `b`: layout_shift() generates twice from one copy"""
     B, dev = b["real_imgs"].shape[0], b["real_imgs"].device
     b = dict(b, z=torch.randn(B, cfg.Z_DIM, device=dev, generator=gen))
     if variant.text:
         b["eps"] = torch.randn(B, cfg.GAN.CONDITION_DIM, device=dev, generator=gen)
         if stage == 2:
             b["eps_s1"] = torch.randn(B, cfg.GAN.CONDITION_DIM, device=dev, generator=gen)
-    return generate(netG, variant, stage, b)[0]
+    return b
 
 
 def object_slots(boxes, take, size, min_side=1):
@@ -207,10 +215,12 @@ class FamilyEvaluation:
         nets = self.trainer.load_network_stageI() if self.stage == 1 else self.trainer.load_network_stageII()
         return None if nets is None else nets[0].eval()
 
-    def one_pass(self, num_samples, seed, image_sinks=(), resample_sinks=(), object_sinks=()):
+    def one_pass(self, num_samples, seed, image_sinks=(), resample_sinks=(), object_sinks=(), generate=None):
         """real and generated images of the loader's first `num_samples` items to the sinks: image_sinks (real, fake, take),
         resample_sinks (fake, fake_again, take), object_sinks (real, fake, tm, label_one_hot, take) with the matrices of the boxes at
-        the images' own size.  Returns the number of images."""
+        the images' own size.  `generate`, where given, makes a batch's image in generate_seeded's place: it is called with (netG,
+        prepared batch, the seeded generator, take, images before the batch) and owes the pass generate_seeded's draws and image
+        (layout_shift() generates a second image from the same draws there).  Returns the number of images."""
         netG = self.load_generator()
         if netG is None:
             raise ValueError("evaluate: the generator could not be loaded (cfg.NET_G = %r)" % (self.cfg.NET_G,))
@@ -227,7 +237,10 @@ class FamilyEvaluation:
             b = self.trainer.prepare_batch(data, self.stage)
             take = min(int(b["real_imgs"].shape[0]), rows - n)
             with torch.no_grad():
-                fake = generate_seeded(netG, self.variant, self.stage, self.cfg, b, gen)
+                if generate is None:
+                    fake = generate_seeded(netG, self.variant, self.stage, self.cfg, b, gen)
+                else:
+                    fake = generate(netG, b, gen, take, n)
                 for sink in resample_sinks:
                     sink(fake, generate_seeded(netG, self.variant, self.stage, self.cfg, b, gen_again), take)
                 for sink in image_sinks:
@@ -327,6 +340,65 @@ class FamilyEvaluation:
                        "window (%s) and is comparable under the same window only.  The images enter as fp32 in [-1, 1]." % acc.window)
         print("Spectrum (%d real, %d generated %dx%d images; window %s): LSD %.4f dB -> %s/spectrum.json"
               % (m, m, self.size, self.size, acc.window, out["lsd_db"], d))
+        return out
+
+    # ------------------------------------------------------------------------------------------ layout shift
+    def layout_shift(self, num_samples=30000, seed=100, min_shift=None, min_side=1, show=16, image_sink=None):
+        """Layout control by moving ONE box (attngan/layoutshift.py has the definition): every item's image is
+        generated twice from the same z / eps / eps_s1, labels and text -- A under the data's matrices, the image every score of
+        run_scores sees under `seed`, and B with only the moved slot's inverse matrix replaced -- and hip/ops.box_shift_sums scores
+        the pairs, one launch per batch.  Stage II moves both box sets by the same relative offset and scores the 256 x 256 image at
+        the stage-II boxes.  A mode of its own, not a row of SCORES.  `image_sink`, where given, is called once per batch with
+        (A, B, edit table, take).  Writes layout_shift.json and, where show > 0, layout_grid.png; returns the JSON's content."""
+        from ..attngan.evaluate import moved_matrices
+        from ..attngan.layoutshift import ShiftResponse, layout_grid
+        if self.cfg.NET_G == '':
+            print('Error: the path for model NET_G is not found!')
+            return None
+        acc = ShiftResponse(self.size, self.channels, self.images(num_samples), min_shift, min_side, seed, self.device, keep=show)
+        scored = "tm_s2" if self.stage == 2 else "tm"
+
+        def pair(netG, b, gen, take, first):
+            b = draw_noise(self.variant, self.stage, self.cfg, b, gen)
+            a = generate(netG, self.variant, self.stage, b)[0]
+            table = acc.edits(boxes_from_theta(b[scored].cpu()), take)                # the one read-back of the layout
+            edited = dict(b)
+            if self.stage == 2:
+                # the stage-I boxes travel by the same RELATIVE offset: (dx, dy) / 256, rounded once to fp32
+                moved = boxes_from_theta(b["tm"].cpu())[table["row"], table["slot"]].double()
+                moved[:, :2] += table["edit"][:, 4:6].double() / float(self.size)
+                edited["tmi"] = moved_matrices(b["tmi"], table, moved.float())
+                edited["tmi_s2"] = moved_matrices(b["tmi_s2"], table)
+            else:
+                edited["tmi"] = moved_matrices(b["tmi"], table)
+            again = generate(netG, self.variant, self.stage, edited)[0]
+            acc.add(a.float(), again.float(), table,
+                    keys=[dataset_key(self.loader.dataset, first + j) for j in range(int(a.shape[0]))])
+            if image_sink is not None:
+                image_sink(a, again, table, take)
+            return a
+        self.one_pass(num_samples, seed, generate=pair)
+        out = acc.result(show)
+        out.update({"show": len(out["most_ignored"]), "grid": None})
+        d = self.save_dir()
+        if acc.kept:
+            out["grid"] = layout_grid(d, acc.kept, acc.info)
+        note = ("Layout control by moving one box: every image is generated twice from the same noise, labels and text, under the "
+                "data's layout (A) and with one object's box moved by at least min_shift pixels (B).  follow = 1 - moved / baseline "
+                "over the old rectangle: 1 -- the object travelled with its box, 0 -- the edit was ignored.  locality: the share of the "
+                "squared change inside the old and the new rectangle; area_share is its chance level.  spill_others / "
+                "spill_background: the mean squared change per pixel in the other objects' rectangles / in the rest, over that of the "
+                "box pixels.  mean +- population std over the pairs; flat, unchanged, no_objects and immovable are counted.  Every "
+                "figure depends on min_shift and min_side.")
+        if self.synthetic:
+            note += " Synthetic data."
+        self.write("layout_shift", out, seed, note)
+        shown = lambda v: "n/a" if v["mean"] is None else "%.4f +- %.4f (%d)" % (v["mean"], v["std"], v["n"])
+        print("Layout shift (%d pairs of %d %dx%d images; %d without objects, %d immovable, %d unchanged, %d flat; min_shift %d px): "
+              "follow %s, locality %s at area share %s -> %s/layout_shift.json%s"
+              % (out["n_pairs"], out["n_images"], self.size, self.size, out["no_objects"], out["immovable"], out["unchanged"],
+                 out["flat"], out["min_shift"], shown(out["follow"]), shown(out["locality"]), shown(out["area_share"]), d,
+                 "" if out["grid"] is None else " and %s" % out["grid"]))
         return out
 
     # ------------------------------------------------------------------------------------------ object accuracy

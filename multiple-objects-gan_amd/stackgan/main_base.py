@@ -3,7 +3,8 @@ code/multi-mnist/main.py): --cfg / --gpu / --data_dir / --manualSeed as in the r
 TRAIN.FLAG, `sample` from the checkpoint cfg.NET_G otherwise -- plus --synthetic N (train on N synthetic items: there are no
 datasets on the GPU box), --max_epoch, --batch_size, --output_dir, --graph.  With TRAIN.FLAG False and any of --object_accuracy
 --swd --msssim --spectrum the checkpoint is SCORED instead of sampled: one pass over the evaluation split (the 'test' split, or N
-synthetic items) serves all the asked scores (stackgan/evaluate.py).  Each tree's
+synthetic items) serves all the asked scores (stackgan/evaluate.py); --layout_shift, a mode of its own, scores
+the checkpoint's layout control by moving one box.  Each tree's
 main.py binds its own cfg / trainer to `run`."""
 import argparse
 import datetime
@@ -53,8 +54,26 @@ def parse_args(argv=None):
     parser.add_argument('--spectrum', action='store_true', help=scores + 'radial power spectrum -> spectrum.json')
     parser.add_argument('--spectrum_window', type=str, default='hann', choices=('hann', 'none'),
                         help='with --spectrum: the window applied before the transform')
+    parser.add_argument('--layout_shift', action='store_true',
+                        help=scores + 'layout control by moving ONE box: every image generated twice from the same noise, labels and '
+                             'text, under the data\'s layout and with one object\'s box moved -> layout_shift.json and layout_grid.png; '
+                             'a mode of its own: not together with any score flag')
+    parser.add_argument('--ls_min_shift', type=int, default=None, metavar='PX',
+                        help='with --layout_shift: the box moves by PX pixels at least along one axis (an eighth of the side by default)')
+    parser.add_argument('--ls_min_side', type=float, default=1, metavar='PX',
+                        help='with --layout_shift: leave out boxes whose shorter side is below PX pixels')
+    parser.add_argument('--ls_show', type=int, default=16, metavar='N',
+                        help='with --layout_shift: the N pairs that followed the edit least are listed and drawn (0: no layout_grid.png)')
     parser.add_argument('--num_samples', type=int, default=30000, metavar='N', help='with a score flag: images scored at most')
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    for name in ('object_accuracy', 'swd', 'msssim', 'spectrum'):
+        if getattr(args, name) and args.layout_shift:
+            parser.error('--%s cannot be combined with --layout_shift' % name)
+    if args.ls_show < 0 or (args.ls_min_shift is not None and args.ls_min_shift < 1):
+        parser.error('--ls_show must not be negative and --ls_min_shift must be 1 at least')
+    if not 0 <= args.ls_min_side < float('inf'):                      # NaN fails both comparisons
+        parser.error('--ls_min_side must be a finite number of pixels, 0 at least')
+    return args
 
 
 def evaluation_datasets(tree, cfg, stage, args, want_bank):
@@ -88,7 +107,11 @@ def score(tree, cfg, stage, trainer_cls, args, asked, output_dir):
     loader = torch.utils.data.DataLoader(dataset, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=False, shuffle=False, num_workers=workers)
     algo = trainer_cls(output_dir, use_graph=False)
     algo.evaluation = FamilyEvaluation(algo, stage, loader, split, bank, synthetic=bool(args.synthetic))
-    algo.scores = algo.evaluation.run_scores(asked, num_samples=args.num_samples, seed=args.manualSeed)
+    if args.layout_shift:
+        algo.scores = {"layout_shift": algo.evaluation.layout_shift(args.num_samples, args.manualSeed, args.ls_min_shift,
+                                                                    args.ls_min_side, args.ls_show)}
+    else:
+        algo.scores = algo.evaluation.run_scores(asked, num_samples=args.num_samples, seed=args.manualSeed)
     return algo
 
 
@@ -116,7 +139,7 @@ def run(tree, cfg, cfg_from_file, trainer_cls, argv=None):
     stage = int(cfg.get("STAGE", 1))
     from .evaluate import asked_scores
     asked = asked_scores(args)
-    if asked and not cfg.TRAIN.FLAG:                                   # scoring a checkpoint (cfg.NET_G)
+    if (asked or args.layout_shift) and not cfg.TRAIN.FLAG:            # scoring a checkpoint (cfg.NET_G)
         return score(tree, cfg, stage, trainer_cls, args, asked, output_dir)
     if not cfg.TRAIN.FLAG:                                             # sampling from a checkpoint (cfg.NET_G)
         algo = trainer_cls(output_dir, use_graph=False)
