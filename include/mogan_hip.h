@@ -1017,6 +1017,35 @@ int mogan_radial_power_f64(const float* x, int B, int C, int S, const float* wei
 int mogan_box_shift_sums_f64(const float* a, const float* b, long long P, int C, int S, const int* edit, const int* others, int G,
                              double* sums, int* counts, hipStream_t stream);
 
+/* The sums of the Inception Score: the softmax of a classifier head over pool codes, reduced per row and per split without the
+ * (row, class) matrix ever reaching memory (csrc/mogan_softmax_head.hip; attngan/inception_score.py has the
+ * whole definition and the numpy oracle; the reference has no code for it).  x (n, D) codes, w (C, D) and bias (C) the head, all
+ * fp32, dense, widened exactly; row_lse (n, or NULL), row_h (n) and psum (S, C) fp64.  All on the device.  The n rows are cut into
+ * S contiguous splits, split s = [floor(s n / S), floor((s + 1) n / S)) -- the rule is part of this contract.  Everything after the
+ * loads in fp64:
+ *     z[i][y]    = <x_i, w_y> + bias[y]             on v_mfma_f64_16x16x4_f64 in 64 x 64 tiles, k along D in index order
+ *     row_lse[i] = log sum_y exp(z[i][y])           the maximum subtracted
+ *     p[i][y]    = exp(z[i][y] - row_lse[i])
+ *     row_h[i]   = sum_y p[i][y] (z[i][y] - row_lse[i])         a p of exactly 0 adds exactly 0, never a NaN
+ *     psum[s][y] = sum_{i in split s} p[i][y]
+ *   A workgroup owns a stripe of 64 rows -- the stripes of a split start at the split's first row -- and walks the head's column
+ *   tiles twice, recomputing the logits: once for the log-sum-exp, once for p; one double per (stripe, class) goes to the
+ *   workspace and a last launch of the same call adds a split's stripes in stripe order.  No atomics, every sum in one fixed order:
+ *     (a) the same inputs give the same bits on every call;
+ *     (b) row_lse[i] and row_h[i] depend on row i, the head, D and C only -- not on n, S or the row's position;
+ *     (c) psum[s] depends on the split's rows in order and on the head only: it is, bit for bit, psum of the S = 1 call on those
+ *         rows alone;
+ *     (d) C = 1 gives row_h == 0.0, row_lse == z and psum == the split's row count, exactly.
+ *   Every element of the outputs is written.  Non-finite inputs give non-finite outputs in their rows and splits, nothing else.
+ *   The workspace is required, 8-byte aligned: mogan_softmax_head_ws_bytes(n, C, S) = 8 S T C, T = ceil(ceil(n / S) / 64) (0 for
+ *   arguments the call rejects); MOGAN_ERR_WS where ws is NULL, misaligned or shorter, nothing launched.
+ *   1 <= n <= 2^31 - 1, 1 <= D <= 65536, 1 <= C <= 2^20, 1 <= S <= min(n, 65535).
+ * MOGAN_ERR_SHAPE before any HIP call (and before the workspace is looked at): a NULL x / w / bias / row_h / psum, an x, w or bias
+ * that is not 4-byte aligned, a row_lse, row_h or psum that is not 8-byte aligned, any dimension outside the ranges above. */
+size_t mogan_softmax_head_ws_bytes(long long n, int C, int S);
+int mogan_softmax_head_f64(const float* x, long long n, int D, const float* w, const float* bias, int C, int S, double* row_lse,
+                           double* row_h, double* psum, void* ws, size_t ws_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

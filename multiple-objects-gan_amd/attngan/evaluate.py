@@ -12,7 +12,11 @@ How scores share a pass is written once too (`SCORES`, `shared_pass`, `run_score
 method, one row of `SCORES` and -- where it reads the images -- an accumulator with `sink`, optionally `resample_sink`, and `params`.
 
 `layout_shift` is a mode of its own as `r_precision` is: it generates every image a second time under an edited
-layout (`draw_noise`, `generate_from`, `moved_matrices`), which no shared pass does."""
+layout (`draw_noise`, `generate_from`, `moved_matrices`), which no shared pass does.
+
+`inception_score` is a mode of its own too: it needs a classifier head from a file (`score_head`), which no row of
+`SCORES` does, and reads the pooled codes through `PooledCodes` as the table's "codes" scores do.  A trainer's `trunk_path`, where set,
+makes `_load_image_encoder` load the Inception trunk from a torchvision file after the encoder's construction."""
 import json
 import os
 from collections import namedtuple
@@ -268,6 +272,21 @@ class CheckpointEvaluation(object):
     def _load_image_encoder(self):
         """The image encoder that TRAIN.NET_E's text encoder was trained with: the `image_encoder` twin of its path, by
         build_models' rule and with its error, frozen, on the device, in eval mode."""
+        image_encoder = self._host_image_encoder()
+        for p in image_encoder.parameters():
+            p.requires_grad = False
+        return image_encoder.to(self.device).eval()
+
+    def _state_file(self, path):
+        """the state dict in `path`; a method that has read the file already for its own ends (inception_score(): the head) leaves it
+        in `_state_read` for the length of its pass, so one file is read once"""
+        from .inception import read_state_file
+        read = getattr(self, "_state_read", None)
+        return read[1] if read is not None and read[0] == path else read_state_file(path)
+
+    def _host_image_encoder(self):
+        """_load_image_encoder's encoder on the host, weights and buffers as the pass will run them: constructed, NET_E's image
+        encoder loaded, then the trunk of the trainer's `trunk_path`"""
         image_encoder = self._new_image_encoder()
         if cfg.TRAIN.NET_E != '':
             img_path = cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder')
@@ -276,9 +295,20 @@ class CheckpointEvaluation(object):
                     raise FileNotFoundError("DAMSM encoder checkpoint not found: %s (cwd %s)" % (path, os.getcwd()))
             image_encoder.load_state_dict(torch.load(img_path, map_location='cpu'))
             print('Load image encoder from:', img_path)
-        for p in image_encoder.parameters():
-            p.requires_grad = False
-        return image_encoder.to(self.device).eval()
+        trunk_path = getattr(self, "trunk_path", None)
+        if trunk_path:
+            # after the construction, whose draws every seeded pass shuffles its loader behind (_load_seeded): the images of a pass
+            # under a trunk file are those of the pass without it.  One pass runs under one trunk: beside NET_E's pair the file
+            # must hold that pair's trunk.
+            from .fid import trunk_digest
+            from .inception import load_trunk_state
+            own = trunk_digest(image_encoder) if cfg.TRAIN.NET_E != '' else None
+            load_trunk_state(image_encoder, self._state_file(trunk_path), trunk_path)
+            print('Load Inception trunk from:', trunk_path)
+            if own is not None and trunk_digest(image_encoder) != own:
+                raise ValueError("--trunk %s holds another Inception trunk (digest %s...) than NET_E's image encoder (%s...): one "
+                                 "pass runs under one trunk" % (trunk_path, trunk_digest(image_encoder)[:12], own[:12]))
+        return image_encoder
 
     def _load_seeded(self, seed, trunk=True):
         """The networks of the seeded paths under torch.manual_seed(seed) (which fixes the random-init encoders of an empty
@@ -791,6 +821,111 @@ class CheckpointEvaluation(object):
             image, box = objects.objects()
             return out, {"real": real.cpu(), "fake": fake.cpu(), "image": image, "box": box}
         return out
+
+    def score_head(self, head_path=None):
+        """The classifier head of inception_score(): (weight (C, D), bias (C), the file's state dict, its path) from `head_path`, or
+        from the trainer's trunk file where none is given.  ValueError where there is no such file or it holds no fc.weight /
+        fc.bias: a random head is never drawn."""
+        from . import inception_score as IS
+        path = head_path or getattr(self, "trunk_path", None)
+        if not path:
+            raise ValueError("inception_score: no head -- the score needs a file with fc.weight (C, D) and fc.bias (C), --is_head or a "
+                             "--trunk file that holds them (torchvision's inception_v3 file does); a random head is never drawn")
+        state = self._state_file(path)
+        head = IS.read_head(state, path)
+        if head is None:
+            raise ValueError("inception_score: no head -- %s holds no fc.weight / fc.bias; a random head is never drawn" % path)
+        return head[0], head[1], state, path
+
+    def head_trunk_digest(self, state, where):
+        """fid.trunk_digest of the pass's own image encoder (_host_image_encoder: constructed, NET_E, the trunk file) after the trunk
+        that the state dict `state` holds is loaded over it (ValueError where it holds it in part only): equal to the pass's digest
+        exactly when every trunk parameter and buffer of `state` has the pass's bits.  BatchNorm's step counters, which the digest
+        covers too, stay the pass's own, so they decide nothing.  The global generator's state is put back."""
+        from .fid import trunk_digest
+        from .inception import load_trunk_state
+        kept = torch.get_rng_state()
+        try:
+            encoder = self._host_image_encoder()
+        finally:
+            torch.set_rng_state(kept)
+        load_trunk_state(encoder, state, where)
+        return trunk_digest(encoder)
+
+    def inception_score(self, split_dir, num_samples=30000, seed=100, head_path=None, splits=10, real=False, codes=None,
+                        return_codes=False):
+        """Inception Score (Salimans et al. 2016; attngan/inception_score.py has the definition) of the checkpoint
+        TRAIN.NET_G: the softmax of a classifier head over the Inception pool codes of one generated image per caption -- exactly the
+        images and codes fid() sees under `seed` --, exp of the mean KL(p_i || mean p) over `splits` contiguous splits of the pass
+        (lowered to the number of images where there are fewer), their mean and population standard deviation, and the figure over
+        all rows.  The head: `fc.weight` (C, D) / `fc.bias` (C) of `head_path`, by default of the trainer's trunk file
+        (main.py --trunk); where that file holds a trunk as well it must be the pass's, bit for bit ("head of another trunk").
+        With real=True the same figures for the real images under "real" -- the ceiling the data itself gets -- and kl_marginals =
+        KL(mean p of the generated || mean p of the real images).  A mode of its own, not a row of SCORES.  ONE pass over the data
+        loader (pool_codes), or the `codes` a caller hands over; the codes stay on the device, hip/ops.softmax_head_sums gives
+        sum_y p log p per row and the sum of p per split in one call per side without the (image, class) matrix ever being formed,
+        one read-back per side, and the figures are finished on the host by math.fsum.  Writes
+        <NET_G minus .pth>/<split>/inception_score.json and returns its content; with return_codes also a dict of the two code
+        matrices on the host, "real" (None unless real) and "fake"."""
+        from . import inception_score as IS
+        from .inception import holds_trunk_keys
+        if net_g_missing():
+            return None
+        weight, bias, state, head_file = self.score_head(head_path)
+        verified = holds_trunk_keys(state)
+
+        def want_real(digest, D):
+            if weight.shape[1] != D:
+                raise ValueError("inception_score: the head of %s is %d wide, the pool codes %d" % (head_file, weight.shape[1], D))
+            if verified and self.head_trunk_digest(state, head_file) != digest:
+                raise ValueError("inception_score: head of another trunk -- %s holds an Inception trunk beside its head, and it is not "
+                                 "the one this pass runs under (digest %s...)" % (head_file, str(digest)[:12]))
+            return bool(real)
+        self._state_read = (head_file, state)                  # the pass's own loader reads the same file where it is the trunk file
+        try:
+            c = PooledCodes(self, "inception_score", split_dir, num_samples, seed, codes, want_real, " and real=True asks for it")
+        finally:
+            del self._state_read
+            state = None                                       # 100 MB that nothing below needs
+        n = c.n
+        if n < 1:
+            raise ValueError("inception_score: the data loader gave no batch")
+        S = IS.effective_splits(n, splits)
+        w, b = torch.from_numpy(weight).to(self.device), torch.from_numpy(bias).to(self.device)
+        sides = {}
+        for side, x in (("fake", c.fake), ("real", c.real)):
+            if x is None:
+                continue
+            row_h, psum = ops.softmax_head_sums(x.contiguous(), w, b, S)
+            back = torch.cat([row_h, psum.flatten()]).cpu().numpy()                       # the one read-back of a side
+            row_h, psum = back[:n], back[n:].reshape(S, -1)
+            bad = np.flatnonzero(~np.isfinite(row_h))
+            if bad.size:
+                raise ValueError("inception_score: row %d of the %s codes gives a non-finite sum (%r): non-finite codes or head"
+                                 % (int(bad[0]), "generated" if side == "fake" else side, float(row_h[bad[0]])))
+            sides[side] = (IS.finish(row_h, psum, n), psum)
+        out = dict(sides["fake"][0])
+        if "real" in sides:
+            out["real"] = sides["real"][0]
+            out["kl_marginals"] = IS.kl_marginals(IS.all_rows(sides["fake"][1]), n, IS.all_rows(sides["real"][1]), n)
+        out.update({"classes": int(weight.shape[0]), "head_digest": IS.head_digest(weight, bias), "head": head_file})
+        note = ("Inception Score: exp of the mean KL(p(y|x) || p(y)) of a classifier head over Inception pool codes, per contiguous "
+                "split of the pass, mean and population standard deviation over the splits, and over all rows "
+                "(inception_score_all).  Under torchvision's ImageNet Inception-v3 weights -- trunk and fc head -- this is the score "
+                "under torchvision's network, not the TF-ported one of the published figures, and with 1000 outputs against its "
+                "1008; under any other trunk or head it is comparable between checkpoints under the same trunk_digest and "
+                "head_digest only.  The figure depends on the number of images per split.")
+        if not verified:
+            note += " The head file holds no trunk: the head was not verified against the trunk the codes were taken under."
+        if S < int(splits):
+            note += " splits lowered from %d to %d: there are only %d images." % (splits, S, n)
+            print("Inception Score: %d images -- %d splits instead of %d (the JSON records it)" % (n, S, splits))
+        out = c.write(out, n if "real" in sides else 0, n, note)
+        print("Inception Score (%d generated images, %d classes, %d splits): %.4f +- %.4f, all rows %.4f%s -> %s/inception_score.json"
+              % (n, out["classes"], S, out["inception_score"], out["inception_score_std"], out["inception_score_all"],
+                 "" if "real" not in sides else "; real images %.4f +- %.4f, KL of the marginals %.6f"
+                 % (out["real"]["inception_score"], out["real"]["inception_score_std"], out["kl_marginals"]), c.save_dir))
+        return c.result(out, return_codes)
 
     def layout_shift(self, split_dir, num_samples=30000, seed=100, min_shift=None, min_side=1, show=16, image_sink=None):
         """Layout control of the checkpoint TRAIN.NET_G by moving ONE box (attngan/layoutshift.py has the

@@ -1106,3 +1106,66 @@ def frozen_trunk(enc, x299):
         ft = enc._frozen_trunk = cls(enc)
         enc._frozen_trunk_key = key
     return _FrozenTrunkFn.apply(x299, ft)
+
+
+# ======================================================================================================================
+# A trunk from a local file: torchvision's `inception_v3_google-*.pth` (its key names are the trunk's), or any DAMSM
+# `image_encoder*.pth`, of which the trunk part is read.
+TRUNK_FILE_IGNORED = ("AuxLogits", "fc", "emb_features", "emb_cnn_code")      # first name components that are no part of the trunk
+COUNTER = ".num_batches_tracked"                                               # absent from old torchvision files; never read
+
+
+def read_state_file(path):
+    """the state dict of a torch.load-able file, on the host; ValueError where the file holds something else"""
+    state = torch.load(path, map_location='cpu')
+    if not isinstance(state, dict) or not all(isinstance(k, str) and torch.is_tensor(v) for k, v in state.items()):
+        raise ValueError("%s holds no state dict (name -> tensor)" % path)
+    return state
+
+
+def trunk_entries(encoder):
+    """name -> tensor of the encoder's trunk: every parameter and buffer but the heads' and BatchNorm's step counters"""
+    heads = tuple(getattr(encoder, "HEADS", ()))
+    return {k: v for k, v in encoder.state_dict().items() if k.split(".")[0] not in heads and not k.endswith(COUNTER)}
+
+
+def check_trunk_state(encoder, state, where="the file"):
+    """name -> the file's tensor for every trunk entry of `encoder`.  ValueError naming the first trunk key that `state` lacks or
+    holds in another shape or dtype, or the first key of `state` that is neither the trunk's nor one of AuxLogits.*, fc.*,
+    *.num_batches_tracked, emb_features.*, emb_cnn_code.* -- another architecture's file does not half-load."""
+    own = trunk_entries(encoder)
+    for key in state:
+        if key not in own and key.split(".")[0] not in TRUNK_FILE_IGNORED and not key.endswith(COUNTER):
+            raise ValueError("%s: unknown key %s -- not an Inception-v3 state dict" % (where, key))
+    for key, t in own.items():
+        if key not in state:
+            raise ValueError("%s: the trunk's %s is missing" % (where, key))
+        if tuple(state[key].shape) != tuple(t.shape) or state[key].dtype != t.dtype:
+            raise ValueError("%s: %s is %s %s, the trunk's is %s %s" % (where, key, state[key].dtype, tuple(state[key].shape),
+                                                                       t.dtype, tuple(t.shape)))
+    return {key: state[key] for key in own}
+
+
+def load_trunk_file(encoder, path):
+    """Loads the Inception trunk of `encoder` (a CNN_ENCODER) from the state dict in `path`: a complete torchvision inception_v3
+    file, old or new layout, or a DAMSM image_encoder checkpoint.  Everything is checked before anything is copied
+    (check_trunk_state); the heads and the step counters keep what they had.  Returns the file's state dict."""
+    state = read_state_file(path)
+    load_trunk_state(encoder, state, path)
+    print('Load Inception trunk from:', path)
+    return state
+
+
+def load_trunk_state(encoder, state, where="the file"):
+    """load_trunk_file's copy from a state dict already read"""
+    picked = check_trunk_state(encoder, state, where)
+    own = trunk_entries(encoder)
+    with torch.no_grad():
+        for key, t in picked.items():
+            own[key].copy_(t)
+
+
+def holds_trunk_keys(state):
+    """whether a state dict names any layer of the trunk"""
+    names = {name for name, _ in TRUNK}
+    return any(key.split(".")[0] in names for key in state)

@@ -6,7 +6,8 @@ COCO pickles are not present.  One process per GPU: launch with
 
 Evaluation (TRAIN.FLAG False): every score of evaluate.SCORES has a flag of its name, `asked_scores` maps the flags to each score's
 keywords, and CheckpointEvaluation.run_scores gives any number of them from one pass.  A new score adds its flags and its entry there.
---layout_shift (CheckpointEvaluation.layout_shift) is a mode of its own beside --sampling and --r_precision."""
+--layout_shift (CheckpointEvaluation.layout_shift) and --inception_score (CheckpointEvaluation.inception_score) are modes of their own
+beside --sampling and --r_precision.  --trunk PATH loads the image encoder's Inception trunk from a torchvision file."""
 import argparse
 import datetime
 import os
@@ -137,13 +138,36 @@ def parse_args(argv=None):
                         help='with --layout_shift: leave out boxes whose shorter side is below PX pixels')
     parser.add_argument('--ls_show', type=int, default=16, metavar='N',
                         help='with --layout_shift: the N pairs that followed the edit least are listed and drawn (0: no layout_grid.png)')
+    parser.add_argument('--trunk', type=str, default=None, metavar='PATH',
+                        help='evaluation (TRAIN.FLAG False): load the image encoder\'s Inception trunk from this file -- torchvision\'s '
+                             'inception_v3_google-*.pth (old or new layout) or any image_encoder*.pth -- so that with NET_E: \'\' the '
+                             'scores on pool codes run under ImageNet features; the generated images are those of a pass without it; '
+                             'beside a NET_E the file must hold that pair\'s trunk')
+    parser.add_argument('--inception_score', action='store_true',
+                        help='evaluation (TRAIN.FLAG False): Inception Score of TRAIN.NET_G\'s images -- the softmax of a classifier '
+                             'head over their Inception pool codes (condGANTrainer.inception_score) -> <NET_G minus .pth>/<split>/'
+                             'inception_score.json; a mode of its own: not together with --sampling, --r_precision, --layout_shift or '
+                             'any score flag')
+    parser.add_argument('--is_head', type=str, default=None, metavar='PATH',
+                        help='with --inception_score: the file with the head, fc.weight (C, D) and fc.bias (C); by default the '
+                             '--trunk file.  A trunk in the same file must be the one the pass runs under')
+    parser.add_argument('--is_splits', type=int, default=10, metavar='N',
+                        help='with --inception_score: contiguous splits of the pass (lowered to the number of images where fewer)')
+    parser.add_argument('--is_real', action='store_true',
+                        help='with --inception_score: the same figures for the real images (the ceiling the data gets) and the KL '
+                             'divergence between the two marginals')
     args = parser.parse_args(argv)
-    for name in list(SCORES) + ['layout_shift']:
+    for name in list(SCORES) + ['layout_shift', 'inception_score']:
         if getattr(args, name) and (args.sampling or args.r_precision):
             parser.error('--%s cannot be combined with --sampling or --r_precision' % name)
     for name in SCORES:
         if getattr(args, name) and args.layout_shift:
             parser.error('--%s cannot be combined with --layout_shift' % name)
+    for name in list(SCORES) + ['layout_shift']:
+        if getattr(args, name) and args.inception_score:
+            parser.error('--%s cannot be combined with --inception_score' % name)
+    if args.is_splits < 1:
+        parser.error('--is_splits must be 1 at least')
     if args.ls_show < 0 or (args.ls_min_shift is not None and args.ls_min_shift < 1):
         parser.error('--ls_show must not be negative and --ls_min_shift must be 1 at least')
     if not 0 <= args.ls_min_side < float('inf'):                      # NaN fails both comparisons
@@ -179,6 +203,9 @@ def main(argv=None):
         cfg.TRAIN.MAX_EPOCH = args.max_epoch
     if args.batch_size is not None:
         cfg.TRAIN.BATCH_SIZE = args.batch_size
+    if args.trunk and cfg.TRAIN.FLAG:
+        raise SystemExit("--trunk is an evaluation flag (TRAIN.FLAG False): training takes its image encoder from TRAIN.NET_E, and "
+                         "pretrain_DAMSM.py --trunk starts a DAMSM pair from the file")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if cfg.TRAIN.FLAG and not torch.cuda.is_initialized():
@@ -217,7 +244,7 @@ def main(argv=None):
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
     asked = asked_scores(args)
-    with_bbox = evaluate and not (args.sampling or args.r_precision or asked or args.layout_shift)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or asked or args.layout_shift or args.inception_score)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -233,7 +260,9 @@ def main(argv=None):
     loader = torch.utils.data.DataLoader(dataset, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True,
                                          shuffle=sampler is None, sampler=sampler,
                                          num_workers=min(int(cfg.WORKERS), 8 if args.synthetic else int(cfg.WORKERS)))
-    algo = trainer(output_dir, loader, dataset.n_words, dataset.ixtoword, args.resume, distributed=world > 1)
+    # the trunk file reaches the trainer only where the flag is given: a trainer without the keyword serves every other run
+    extra = {'trunk': args.trunk} if args.trunk else {}
+    algo = trainer(output_dir, loader, dataset.n_words, dataset.ixtoword, args.resume, distributed=world > 1, **extra)
     if cfg.TRAIN.FLAG:
         algo.train()
     elif args.sampling:
@@ -242,6 +271,8 @@ def main(argv=None):
         algo.r_precision(split_dir, seed=args.manualSeed, real=args.real)
     elif args.layout_shift:
         algo.layout_shift(split_dir, seed=args.manualSeed, min_shift=args.ls_min_shift, min_side=args.ls_min_side, show=args.ls_show)
+    elif args.inception_score:
+        algo.inception_score(split_dir, seed=args.manualSeed, head_path=args.is_head, splits=args.is_splits, real=args.is_real)
     elif asked:
         # any number of scores from ONE pass over the loader (evaluate.SCORES says what each takes from it); one score alone runs
         # its own method, which may then leave out what a shared pass needs (the trunk, the real images' codes)

@@ -212,6 +212,11 @@ class CNN_ENCODER(nn.Module):
     def trunk_parameters(self):
         return [p for n, p in self.named_parameters() if n.split(".")[0] not in self.HEADS]
 
+    def load_trunk_file(self, path):
+        """the trunk from a torchvision inception_v3 file or a DAMSM image_encoder checkpoint on disk (inception.load_trunk_file:
+        ValueError for a missing, mis-shaped or unknown key; the heads keep what they had); returns the file's state dict"""
+        return inception.load_trunk_file(self, path)
+
     def _frozen(self):
         """the fast frozen trunk: eval mode and no TRUNK parameter asks for a gradient; the two heads may (DAMSM pre-training:
         they then run under autograd on the trunk's outputs)"""

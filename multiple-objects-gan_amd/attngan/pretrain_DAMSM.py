@@ -187,7 +187,9 @@ class DAMSMEngine:
         return paths
 
 
-def build_encoders(n_words, device):
+def build_encoders(n_words, device, trunk=None):
+    """`trunk`: a torchvision inception_v3 file (or an image_encoder checkpoint) whose Inception trunk replaces the random-init one
+    -- after construction, so the draws from torch's global generator are those of a run without it -- and after NET_E's pair."""
     text_encoder = RNN_ENCODER(n_words, nhidden=cfg.TEXT.EMBEDDING_DIM)
     image_encoder = CNN_ENCODER(cfg.TEXT.EMBEDDING_DIM, pretrained=False)
     if cfg.TRAIN.NET_E != '':                                   # continue from an earlier pair
@@ -195,6 +197,8 @@ def build_encoders(n_words, device):
         text_encoder.load_state_dict(torch.load(cfg.TRAIN.NET_E, map_location='cpu'))
         image_encoder.load_state_dict(torch.load(img_path, map_location='cpu'))
         print('Load text / image encoder from:', cfg.TRAIN.NET_E, img_path)
+    if trunk:
+        image_encoder.load_trunk_file(trunk)
     return text_encoder.to(device), image_encoder.to(device)
 
 
@@ -208,6 +212,9 @@ def parse_args(argv=None):
     parser.add_argument('--max_epoch', type=int, default=None)
     parser.add_argument('--batch_size', type=int, default=None)
     parser.add_argument('--output_dir', type=str, default='')
+    parser.add_argument('--trunk', type=str, default=None, metavar='PATH',
+                        help='start the frozen Inception trunk from this file instead of a random one: torchvision\'s '
+                             'inception_v3_google-*.pth (old or new layout), or any image_encoder*.pth, of which the trunk is read')
     return parser.parse_args(argv)
 
 
@@ -246,7 +253,7 @@ def main(argv=None):
     workers = 0 if args.synthetic else int(cfg.WORKERS)
     loader = torch.utils.data.DataLoader(dataset, batch_size=B, drop_last=True, shuffle=True, num_workers=workers)
     loader_val = torch.utils.data.DataLoader(dataset_val, batch_size=B, drop_last=True, shuffle=False, num_workers=workers)
-    text_encoder, image_encoder = build_encoders(dataset.n_words, device)
+    text_encoder, image_encoder = build_encoders(dataset.n_words, device, trunk=args.trunk)
     engine = DAMSMEngine(text_encoder, image_encoder)
     interval = max(1, int(cfg.TRAIN.SNAPSHOT_INTERVAL))
     epoch = -1

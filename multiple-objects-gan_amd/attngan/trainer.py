@@ -1409,7 +1409,8 @@ class condGANTrainer(CheckpointEvaluation):
     """Same constructor and public methods as the reference class (trainer.py:29-366); the methods that evaluate a finished
     checkpoint (sampling, sample, r_precision, pool_codes, fid, kid, prdc) are inherited from evaluate.CheckpointEvaluation."""
 
-    def __init__(self, output_dir, data_loader, n_words, ixtoword, resume, distributed=False, use_graph=False):
+    def __init__(self, output_dir, data_loader, n_words, ixtoword, resume, distributed=False, use_graph=False, trunk=None):
+        self.trunk_path = trunk                   # evaluation: the Inception trunk's file (CheckpointEvaluation._load_image_encoder)
         if cfg.TRAIN.FLAG:
             self.model_dir = os.path.join(output_dir, 'Model')
             self.image_dir = os.path.join(output_dir, 'Image')

@@ -170,6 +170,8 @@ SIGNATURES = {
     "mogan_radial_power_ws_bytes": [I, I],
     "mogan_radial_power_f64": [P, I, I, I, P, P, P, P, I, P, P, Z, P],
     "mogan_box_shift_sums_f64": [P, P, L, I, I, P, P, I, P, P, P],
+    "mogan_softmax_head_ws_bytes": [L, I, I],
+    "mogan_softmax_head_f64": [P, L, I, P, P, I, I, P, P, P, P, Z, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }
@@ -201,7 +203,7 @@ _RESTYPE = {"mogan_bn_ws_bytes": Z, "mogan_upconv3x3_ws_bytes": Z, "mogan_pk_wei
             "mogan_wino_prep_bytes": Z, "mogan_conv_prep_bytes": Z, "mogan_poly3_mmd_ws_bytes": Z,
             "mogan_knn_sqdist_ws_bytes": Z, "mogan_ball_count_ws_bytes": Z, "mogan_swd_moments_ws_bytes": Z,
             "mogan_ssim_level_ws_bytes": Z, "mogan_knn_cross_ws_bytes": Z, "mogan_radial_power_ws_bytes": Z,
-            "mogan_knn_label_ws_bytes": Z}
+            "mogan_knn_label_ws_bytes": Z, "mogan_softmax_head_ws_bytes": Z}
 _ERRORS = {-1: "MOGAN_ERR_SHAPE", -2: "MOGAN_ERR_LAUNCH", -3: "MOGAN_ERR_WS"}
 
 _lib = None

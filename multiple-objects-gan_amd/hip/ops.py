@@ -1979,6 +1979,41 @@ def knn_label(q, qlabel, p, plabel, K):
     return d2, idx, same_d2, same_idx, other_d2, other_idx
 
 
+SOFTMAX_HEAD_MAX_CLASSES = 1 << 20
+SOFTMAX_HEAD_MAX_SPLITS = 65535
+
+
+def softmax_head_sums(x, w, bias, splits=1, want_lse=False):
+    """The sums the Inception Score is formed from (mogan_softmax_head_f64: fp64 MFMA, fixed summation order, no (row, class) matrix
+    written): for fp32 codes x (n, D), a head w (C, D) and bias (C), with z = x w^T + bias, p = softmax(z) per row and the rows cut
+    into `splits` contiguous splits [floor(s n / S), floor((s + 1) n / S)): (row_h (n) = sum_y p log p, psum (S, C) = sum of p over
+    each split's rows), both fp64 on the device; with want_lse (row_lse (n), row_h, psum).  A row's figures depend on the row and the
+    head only; psum[s] is bit for bit that of the S = 1 call on the split's rows.  No gradient.  Nothing is converted or copied for
+    the caller: a wrong dtype or rank, a non-contiguous input, another device, a width mismatch, splits outside 1..min(n, 65535) or
+    more than 2^20 classes are a ValueError."""
+    _codes("softmax_head_sums", (("x", x), ("w", w)))
+    if not torch.is_tensor(bias) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] != w.shape[0] or \
+            not bias.is_contiguous():
+        raise ValueError("softmax_head_sums: a dense fp32 bias (%d,) expected, got %s %s"
+                         % (w.shape[0], getattr(bias, "dtype", type(bias)), tuple(getattr(bias, "shape", ()))))
+    if bias.device != x.device:
+        raise ValueError("softmax_head_sums: the bias must be on the codes' device (%s, %s)" % (x.device, bias.device))
+    n, D, C, S = x.shape[0], x.shape[1], w.shape[0], int(splits)
+    if S < 1 or S > min(n, SOFTMAX_HEAD_MAX_SPLITS) or C > SOFTMAX_HEAD_MAX_CLASSES:
+        raise ValueError("softmax_head_sums: 1 <= splits <= min(n, %d) and at most %d classes expected, got splits = %d for %d "
+                         "rows, %d classes" % (SOFTMAX_HEAD_MAX_SPLITS, SOFTMAX_HEAD_MAX_CLASSES, S, n, C))
+    x, w, bias = x.detach(), w.detach(), bias.detach()
+    px, pw, pb = ptr(x), ptr(w), ptr(bias)
+    ws, ws_bytes, own = _scratch(x.device, int(lib.load().mogan_softmax_head_ws_bytes(n, C, S)))
+    row_lse = torch.empty((n,), dtype=torch.float64, device=x.device) if want_lse else None
+    row_h = torch.empty((n,), dtype=torch.float64, device=x.device)
+    psum = torch.empty((S, C), dtype=torch.float64, device=x.device)
+    call("mogan_softmax_head_f64", px, n, D, pw, pb, C, S, ptr(row_lse), ptr(row_h), ptr(psum), ws, ws_bytes, stream_ptr())
+    if own is not None:
+        own.record_stream(torch.cuda.current_stream(x.device))
+    return (row_lse, row_h, psum) if want_lse else (row_h, psum)
+
+
 def ball_counts(q, p, r2, side="support"):
     """count (M, R) int32 on the device, count[j, c] = #{ i : d2(q_j, p_i) <= r2[., c] } for fp32 queries q (M, D), fp32 support
     points p (N, D) and fp64 squared radii r2 (mogan_ball_count_f64; the distances are knn_sqdist's, bit for bit).  side
