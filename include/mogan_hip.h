@@ -1046,6 +1046,39 @@ size_t mogan_softmax_head_ws_bytes(long long n, int C, int S);
 int mogan_softmax_head_f64(const float* x, long long n, int D, const float* w, const float* bias, int C, int S, double* row_lse,
                            double* row_h, double* psum, void* ws, size_t ws_bytes, hipStream_t stream);
 
+/* The attention sheets of a generated image: what miscc/vis.build_super_images2 does per word on the host, on the device (DESIGN.md
+ * section 9p; csrc/mogan_attn_sheet.hip; attngan/attnsheet.py has the whole definition and the numpy oracle).  attn (B, T, att,
+ * att) fp32 >= 0, the generator's word attention; cap_lens (B) int32; img (B, 3, vis, vis) fp32 in [-1, 1]; table (vis, att) fp64,
+ * the bilinear upscaling followed by the reflecting Gaussian as ONE matrix M the host builds (attnsheet.table; the kernel never
+ * sees sigma); pick (P, 2) int32 = (sample, word).  All dense, all on the device.  Everything after the fp32 loads in fp64; both
+ * thresholds are compared in fp32, t = (float) (2.0 / len):
+ *     conf[b][t]  = sum a [a > 2 t]  for t < cap_lens[b], 0.0 otherwise          (the reference's conf_score / 3: its top-K order)
+ *     A           = a [a > t]                          S = M A M^T               (vis, vis)
+ *     lo = min S, hi = max S                           v = (S - lo) / (hi - lo) * 255        q = (u8) floor(v)
+ *     image byte  = (u8) clamp(((x + 1) / 2) * 255, 0, 255)   in fp32, the roundings of the host's vis._to_uint8_range
+ *     sheet[p][y][x][c] = Pillow's paste of q over the image byte through the constant mask alpha:
+ *                         t = image (255 - alpha) + q alpha + 128, ((t >> 8) + t) >> 8
+ *   sheet (P, vis, vis, 3) u8; stats (P, 2) fp64 = (lo, hi); flags (P) int32: 0 a sheet, 1 a flat map (hi == lo: q = 0 everywhere;
+ *   the reference divides 0 by 0), 2 a map that holds a non-finite value (answered as a flat map with stats (0, 0)), 3 a pick that
+ *   should never be sent.
+ *   conf: one workgroup per (sample, word), partials added in LDS in a fixed tree.  sheet: one workgroup per pick; U = M A in strips
+ *   of 32 output rows, S = U M^T in registers, every sum one fma per term in index order, the product walked twice in the same
+ *   order (min and max, then quantise and blend); no atomics, no workspace, the (vis, vis) fp64 map never reaches memory:
+ *     (a) the same inputs give the same bits on every call;
+ *     (b) a pick's sheet, stats and flag depend on its own map, caption length, image and the table only -- the same bits alone
+ *         and at any position of any pick list, for any B;
+ *     (c) the bits do not depend on the alignment of attn or img beyond 4 bytes;
+ *     (d) a map where nothing passes the threshold gives q == 0 everywhere, lo == hi == 0.0 bitwise and flag 1;
+ *     (e) with the identity table S is A exactly: the sheet is the oracle's byte for byte.
+ *   Safe by construction: a pick whose sample is outside [0, B), whose word is outside [0, T) or >= cap_lens[sample] reads nothing
+ *   but its own pick row and that length, and gets a zero sheet, zero stats and flag 3.  Every element of the outputs is written.
+ *   B >= 1, 1 <= T <= 32, 2 <= att <= 128, vis a multiple of att, att <= vis <= 256, 0 <= alpha <= 255, P >= 1,
+ *   B T att att, 3 B vis vis and 3 P vis vis <= 2^31 - 1.
+ * MOGAN_ERR_SHAPE before any HIP call: a NULL pointer, a table or stats that is not 8-byte aligned, any value outside the ranges. */
+int mogan_attn_conf_f64(const float* attn, const int* cap_lens, int B, int T, int att, double* conf, hipStream_t stream);
+int mogan_attn_sheet_f64(const float* attn, const int* cap_lens, const float* img, const double* table, const int* pick, int P, int B,
+                         int T, int att, int vis, int alpha, unsigned char* sheet, double* stats, int* flags, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,10 @@ layout (`draw_noise`, `generate_from`, `moved_matrices`), which no shared pass d
 
 `inception_score` is a mode of its own too: it needs a classifier head from a file (`score_head`), which no row of
 `SCORES` does, and reads the pooled codes through `PooledCodes` as the table's "codes" scores do.  A trainer's `trunk_path`, where set,
-makes `_load_image_encoder` load the Inception trunk from a torchvision file after the encoder's construction."""
+makes `_load_image_encoder` load the Inception trunk from a torchvision file after the encoder's construction.
+
+`scenes` is the one path whose captions and layouts do not come from the data loader: it draws the scenes of a
+file the user wrote (attngan/scenes.py) and the attention sheets of their words (`attention_sheets`; attngan/attnsheet.py)."""
 import json
 import os
 from collections import namedtuple
@@ -974,6 +977,137 @@ class CheckpointEvaluation(object):
               "%s, locality %s at area share %s -> %s/layout_shift.json%s"
               % (out["n_pairs"], out["n_images"], out["no_objects"], out["immovable"], out["unchanged"], out["flat"], out["min_shift"],
                  shown(f), shown(loc), shown(out["area_share"]), save_dir, "" if out["grid"] is None else " and %s" % out["grid"]))
+        return out
+
+    def _sheet_table(self, att, vis):
+        """attnsheet.table(att, vis / att) on the device, built once per shape"""
+        from .attnsheet import table
+        cache = self.__dict__.setdefault("_sheet_tables", {})
+        if (att, vis) not in cache:
+            cache[(att, vis)] = torch.from_numpy(table(att, vis // att)).to(self.device)
+        return cache[(att, vis)]
+
+    def attention_sheets(self, fake_imgs, att_maps, captions, topk=5, vis_size=256):
+        """The attention sheets of one generator batch whose captions all have captions.shape[1] words: per
+        attention stage k one launch of ops.attn_conf, the reference's top-K choice on the host, one launch of ops.attn_sheet for
+        every picked (sample, word) of the batch over fake_imgs[k + 1] -- brought to vis_size by F.interpolate on the device where
+        smaller, as miscc/vis does on the host -- and the caption strip of vis.drawCaption on top.
+        -> (sheets[k][sample]: uint8 (FONT_MAX + vis, K (vis + 2), 3), records[k][sample]: dict(words, conf, lo, hi, flag))"""
+        import torch.nn.functional as F
+        from .attnsheet import ALPHA, top_words
+        from .miscc import vis
+        n, T = captions.shape
+        lens = torch.full((n,), T, dtype=torch.int32)
+        strip = np.ones([n * vis.FONT_MAX, T * (vis_size + 2), 3], dtype=np.uint8)
+        strip = np.asarray(vis.drawCaption(strip, captions, self.ixtoword, vis_size, off1=0)[0]).astype(np.uint8)
+        pad = np.zeros((vis_size, 2, 3), dtype=np.uint8)
+        sheets, records = [], []
+        for k, attn in enumerate(att_maps):
+            attn = attn.detach().float().contiguous()
+            img = fake_imgs[k + 1].detach().float()
+            if img.shape[-1] != vis_size:
+                img = F.interpolate(img, size=(vis_size, vis_size), mode='bilinear', align_corners=False)
+            conf = ops.attn_conf(attn, lens).cpu().numpy()
+            order = [top_words(conf[s], T, topk) for s in range(n)]
+            pick = torch.tensor([(s, w) for s in range(n) for w in order[s]], dtype=torch.int32)
+            sheet, stats, flags = ops.attn_sheet(attn, lens, img.contiguous(), self._sheet_table(attn.shape[-1], vis_size), pick, ALPHA)
+            sheet, stats, flags = sheet.cpu().numpy(), stats.cpu().numpy(), flags.cpu().numpy()
+            K = len(order[0])
+            sheets.append([])
+            records.append([])
+            for s in range(n):
+                txt = [strip[s * vis.FONT_MAX:(s + 1) * vis.FONT_MAX, w * (vis_size + 2):(w + 1) * (vis_size + 2)] for w in order[s]]
+                row = [np.concatenate([sheet[s * K + i], pad], 1) for i in range(K)]
+                sheets[k].append(np.concatenate([np.concatenate(txt, 1), np.concatenate(row, 1)], 0))
+                records[k].append({"words": order[s], "conf": [float(conf[s, w]) for w in order[s]],
+                                   "lo": [float(v) for v in stats[s * K:(s + 1) * K, 0]], "hi": [float(v) for v in stats[s * K:(s + 1) * K, 1]],
+                                   "flag": [int(v) for v in flags[s * K:(s + 1) * K]]})
+        return sheets, records
+
+    def scenes(self, path, seed=100, samples=4, topk=5, attention=True, classes=None, image_sink=None):
+        """Images from written scenes (attngan/scenes.py has the file's rules): for every scene of the JSON
+        file `path` -- a caption, up to three boxes with labels -- `samples` images of TRAIN.NET_G under the scene's own seeded
+        generator, each scene a generator batch of its own, so a scene's images do not depend on what else the file holds; where the
+        scene asks for a sweep, sample 0's draws again with only the swept slot's matrix replaced, in batches of the samples' shape,
+        step 0 being sample 0 itself.  The data loader's dataset gives the vocabulary only.  Writes <NET_G minus .pth>/scenes/<name>/
+        s<k>_g<stage>.png, s<k>_a<stage>.png (the attention sheets, where `attention`), samples.png and sweep.png, and the record
+        scenes.json beside the scene directories; returns the record.  `image_sink`, where given, is called once per scene with
+        (scene, the three stages' images, the attention maps, the sweep's 256 x 256 images or None).  The file is checked before any checkpoint is read."""
+        import torch.nn.functional as F
+        from PIL import Image
+        from . import scenes as SC
+        from . import synthetic
+        if net_g_missing():
+            return None
+        topk = int(topk)
+        if not 1 <= topk <= 8:
+            raise ValueError("scenes: topk must be in 1..8, got %d" % topk)
+        if attention and cfg.TEXT.WORDS_NUM > 32:
+            raise ValueError("scenes: attention sheets take captions of 32 words at the most, TEXT.WORDS_NUM is %d" % cfg.TEXT.WORDS_NUM)
+        todo = SC.load(path, SC.vocabulary(self.data_loader.dataset), cfg.TEXT.WORDS_NUM, synthetic.N_CLASSES, samples, classes, seed)
+        netG, text_encoder, _, _ = self._load_seeded(seed, trunk=False)
+        root = eval_save_dir('scenes')
+        u8 = lambda t: t.add(1.0).mul(127.5).clamp(0, 255).byte().permute(0, 2, 3, 1).cpu().numpy()       # sampling()'s rule
+        shown = lambda t: t if t.shape[-1] == 256 else F.interpolate(t, size=(256, 256), mode='nearest')
+        record = []
+        for sc in todo:
+            save_dir = '%s/%s' % (root, sc.name)
+            mkdir_p(save_dir)
+            n, T = sc.samples, len(sc.tokens)
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(sc.seed)
+            captions = torch.tensor([sc.tokens] * n, dtype=torch.int64, device=self.device)
+            with torch.no_grad():
+                words_embs, sent_emb, mask = encode_text(text_encoder, captions, torch.full((n,), T, dtype=torch.int64, device=self.device))
+                noise, eps = draw_noise(gen, sent_emb)
+                tmi = ops.bbox_to_theta(torch.from_numpy(sc.boxes).to(self.device))[1][None].repeat(n, 1, 1, 1)
+                label = synthetic.one_hot_labels(sc.labels)[None].repeat(n, 1, 1).to(self.device)
+                fake_imgs, att_maps, _, _ = netG(noise, sent_emb, words_embs, mask, tmi, label, eps=eps)
+                stages = [u8(t) for t in fake_imgs]
+                for k in range(n):
+                    for g, st in enumerate(stages):
+                        Image.fromarray(st[k]).save('%s/s%d_g%d.png' % (save_dir, k, g))
+                entry = {"name": sc.name, "caption": sc.caption, "words": sc.words, "tokens": sc.tokens, "dropped": sc.dropped,
+                         "truncated": sc.truncated, "boxes_px": sc.pixel_boxes(256), "labels": [int(v) for v in sc.labels[:sc.n_objects]],
+                         "seed": sc.seed, "samples": n, "sweep": sc.sweep, "sheets": []}
+                if attention:
+                    sheets, recs = self.attention_sheets(fake_imgs, att_maps, captions, topk)
+                    for k in range(n):
+                        for a in range(len(sheets)):
+                            Image.fromarray(sheets[a][k]).save('%s/s%d_a%d.png' % (save_dir, k, a))
+                            entry["sheets"].append(dict(recs[a][k], sample=k, stage=a))
+                drawn = torch.from_numpy(sc.drawn_boxes())
+                layout = draw_bbox_lines(torch.full((n, 3, 256, 256), -1.0, device=self.device), drawn, 256)
+                rows = [layout] + [draw_bbox_lines(shown(t.float()).clone(), drawn, 256) for t in fake_imgs]
+                Image.fromarray(np.concatenate([np.concatenate(list(r), 0) for r in map(u8, rows)], 1)).save('%s/samples.png' % save_dir)
+                swept = None
+                if sc.sweep is not None:
+                    path_boxes = torch.from_numpy(sc.sweep_boxes())
+                    steps, slot = path_boxes.shape[0], sc.sweep["object"]
+                    first = lambda t: t[:1].repeat((n,) + (1,) * (t.dim() - 1))
+                    out = []
+                    for at in range(0, steps, n):
+                        rows = list(range(at, min(at + n, steps)))
+                        table = {"row": torch.arange(len(rows)), "slot": torch.full((len(rows),), slot, dtype=torch.int64)}
+                        out.append(generate_from(netG, first(noise), first(eps), words_embs, sent_emb, mask,
+                                                 moved_matrices(tmi, table, path_boxes[rows]), label)[:len(rows)])
+                    swept = torch.cat(out)
+                    strip = swept.float().clone()
+                    for k in range(steps):
+                        draw_bbox_lines(strip[k:k + 1], torch.from_numpy(SC.clamp_box(path_boxes[k].numpy()))[None], 256)
+                    Image.fromarray(np.concatenate(list(u8(strip)), 1)).save('%s/sweep.png' % save_dir)
+            if image_sink is not None:
+                image_sink(sc, fake_imgs, att_maps, swept)
+            record.append(entry)
+        out = {"scenes": record, "file": str(path), "topk": topk, "attention": bool(attention)}
+        write_score('scenes', "scenes", out, seed,
+                    "Images of TRAIN.NET_G from written scenes: per scene `samples` images under the scene's own seed (s<k>_g<stage>.png, "
+                    "samples.png: layout | 64 | 128 | 256), the attention sheets of the two attention stages (s<k>_a<stage>.png: the top-K "
+                    "words by thresholded attention mass conf, each word's map thresholded at 2 / len, upscaled, smoothed and normalised "
+                    "by its own lo and hi, pasted over the stage's image; flag 1: a flat map, 2: a non-finite one) and, where asked for, "
+                    "one object walked across the image under sample 0's noise (sweep.png).")
+        print("Scenes (%d scenes, %d images%s) -> %s" % (len(todo), sum(sc.samples for sc in todo),
+                                                       ", attention sheets of the top %d words" % topk if attention else "", root))
         return out
 
     def train_split(self):

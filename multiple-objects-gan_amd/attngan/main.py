@@ -7,7 +7,8 @@ COCO pickles are not present.  One process per GPU: launch with
 Evaluation (TRAIN.FLAG False): every score of evaluate.SCORES has a flag of its name, `asked_scores` maps the flags to each score's
 keywords, and CheckpointEvaluation.run_scores gives any number of them from one pass.  A new score adds its flags and its entry there.
 --layout_shift (CheckpointEvaluation.layout_shift) and --inception_score (CheckpointEvaluation.inception_score) are modes of their own
-beside --sampling and --r_precision.  --trunk PATH loads the image encoder's Inception trunk from a torchvision file."""
+beside --sampling and --r_precision, and so is --scenes FILE (CheckpointEvaluation.scenes): images from captions, boxes and labels the
+user wrote.  --trunk PATH loads the image encoder's Inception trunk from a torchvision file."""
 import argparse
 import datetime
 import os
@@ -156,10 +157,27 @@ def parse_args(argv=None):
     parser.add_argument('--is_real', action='store_true',
                         help='with --inception_score: the same figures for the real images (the ceiling the data gets) and the KL '
                              'divergence between the two marginals')
+    parser.add_argument('--scenes', type=str, default=None, metavar='FILE',
+                        help='evaluation (TRAIN.FLAG False): images of TRAIN.NET_G from written scenes -- a JSON file {"scenes": [{"name", '
+                             '"caption", "objects": [{"label", "box": [x, y, w, h]}], "samples"?, "sweep"?: {"object", "to": [x, y], '
+                             '"steps"}}]} (attngan/scenes.py; condGANTrainer.scenes) -> <NET_G minus .pth>/scenes/<name>/ with the three '
+                             'stages of every sample, the attention sheets of the top words, samples.png and sweep.png, and scenes.json; '
+                             'a mode of its own: not together with --sampling, --r_precision, --layout_shift, --inception_score or any '
+                             'score flag')
+    parser.add_argument('--scene_samples', type=int, default=4, metavar='N', help='with --scenes: images per scene where the scene does not say (1..64)')
+    parser.add_argument('--scene_topk', type=int, default=5, metavar='K', help='with --scenes: words per attention sheet (1..8)')
+    parser.add_argument('--scene_no_attention', action='store_true', help='with --scenes: write no attention sheets')
+    parser.add_argument('--scene_classes', type=str, default=None, metavar='FILE',
+                        help='with --scenes: one class name per line; a label may then be a name of this file')
     args = parser.parse_args(argv)
-    for name in list(SCORES) + ['layout_shift', 'inception_score']:
+    for name in list(SCORES) + ['layout_shift', 'inception_score', 'scenes']:
         if getattr(args, name) and (args.sampling or args.r_precision):
             parser.error('--%s cannot be combined with --sampling or --r_precision' % name)
+    for name in list(SCORES) + ['layout_shift', 'inception_score']:
+        if getattr(args, name) and args.scenes:
+            parser.error('--%s cannot be combined with --scenes' % name)
+    if not 1 <= args.scene_samples <= 64 or not 1 <= args.scene_topk <= 8:
+        parser.error('--scene_samples must be in 1..64 and --scene_topk in 1..8')
     for name in SCORES:
         if getattr(args, name) and args.layout_shift:
             parser.error('--%s cannot be combined with --layout_shift' % name)
@@ -244,7 +262,7 @@ def main(argv=None):
     # main.py:117-121: evaluation reads the test split and the dataset hands the scaled boxes along
     split_dir, evaluate = ('train', False) if cfg.TRAIN.FLAG else ('test', True)
     asked = asked_scores(args)
-    with_bbox = evaluate and not (args.sampling or args.r_precision or asked or args.layout_shift or args.inception_score)
+    with_bbox = evaluate and not (args.sampling or args.r_precision or asked or args.layout_shift or args.inception_score or args.scenes)
     if args.synthetic > 0:
         dataset = SyntheticTextDataset(args.synthetic, seed=args.manualSeed, eval=with_bbox)   # one dataset, partitioned below
     else:
@@ -273,6 +291,10 @@ def main(argv=None):
         algo.layout_shift(split_dir, seed=args.manualSeed, min_shift=args.ls_min_shift, min_side=args.ls_min_side, show=args.ls_show)
     elif args.inception_score:
         algo.inception_score(split_dir, seed=args.manualSeed, head_path=args.is_head, splits=args.is_splits, real=args.is_real)
+    elif args.scenes:
+        from .scenes import read_classes
+        algo.scenes(args.scenes, seed=args.manualSeed, samples=args.scene_samples, topk=args.scene_topk,
+                    attention=not args.scene_no_attention, classes=read_classes(args.scene_classes) if args.scene_classes else None)
     elif asked:
         # any number of scores from ONE pass over the loader (evaluate.SCORES says what each takes from it); one score alone runs
         # its own method, which may then leave out what a shared pass needs (the trunk, the real images' codes)
@@ -280,9 +302,9 @@ def main(argv=None):
     elif cfg.B_VALIDATION:
         algo.sample(split_dir, num_samples=25, draw_bbox=True)                      # main.py:158
     else:
-        # main.py:160 gen_example: not callable in the reference either (it passes num_samples to a two-argument
-        # function and trainer.gen_example calls G_NET without boxes and labels) -- nothing to mirror
-        raise SystemExit("gen_example (custom captions) is not supported: set B_VALIDATION: True")
+        # main.py:160 gen_example: not callable in the reference (it passes num_samples to a two-argument function and
+        # trainer.gen_example calls G_NET without boxes and labels); --scenes is this project's form of it
+        raise SystemExit("custom captions come from a scene file: --scenes FILE (or set B_VALIDATION: True)")
     if world > 1:
         dist.destroy_process_group()
 

@@ -172,6 +172,8 @@ SIGNATURES = {
     "mogan_box_shift_sums_f64": [P, P, L, I, I, P, P, I, P, P, P],
     "mogan_softmax_head_ws_bytes": [L, I, I],
     "mogan_softmax_head_f64": [P, L, I, P, P, I, I, P, P, P, P, Z, P],
+    "mogan_attn_conf_f64": [P, P, I, I, I, P, P],
+    "mogan_attn_sheet_f64": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P],
     "mogan_scalar_sum": [P, P, I, P, P],
     "mogan_scalar_scale": [P, P, I, P, P],
 }

@@ -2331,6 +2331,90 @@ def box_shift_sums(a, b, edit, others):
     return sums, counts
 
 
+def _attn_maps(who, attn, cap_lens):
+    """the checks the two attention-sheet ops share: attn (B, 1..32, att, att) fp32 with att in 2..128, cap_lens (B) a HOST int32
+    tensor with every length in 1..T -> (attn detached, B, T, att)"""
+    attn = _dense_f32(who, "attn", attn, 4)
+    B, T, att, att2 = attn.shape
+    if att != att2 or att < 2 or att > 128 or T > 32 or attn.numel() > 2 ** 31 - 1:
+        raise ValueError("%s: attn (B, 1..32, att, att) with att in 2..128 and fewer than 2^31 elements expected, got %s"
+                         % (who, tuple(attn.shape)))
+    if not torch.is_tensor(cap_lens) or cap_lens.dtype != torch.int32 or cap_lens.device.type != "cpu":
+        raise ValueError("%s: cap_lens must be a host tensor of torch.int32, got %s %s"
+                         % (who, getattr(cap_lens, "dtype", type(cap_lens)), getattr(cap_lens, "device", "")))
+    if cap_lens.dim() != 1 or cap_lens.shape[0] != B or not cap_lens.is_contiguous():
+        raise ValueError("%s: cap_lens must be a contiguous (%d,) tensor, got %s with strides %s"
+                         % (who, B, tuple(cap_lens.shape), tuple(cap_lens.stride())))
+    if int(cap_lens.min()) < 1 or int(cap_lens.max()) > T:
+        raise ValueError("%s: every caption length must lie in 1..%d, got %d..%d" % (who, T, int(cap_lens.min()), int(cap_lens.max())))
+    if attn.device.type == "meta":
+        raise ValueError("%s: attn is a meta tensor" % who)
+    return attn, B, T, att
+
+
+def attn_conf(attn, cap_lens):
+    """The thresholded attention mass per word, the quantity the attention sheets' top-K choice sorts by (mogan_attn_conf_f64;
+    DESIGN.md section 9p; attngan/attnsheet.py has the definition): fp32 attn (B, T, att, att) on the device with T <= 32 and att in
+    2..128; cap_lens (B) a HOST int32 tensor, every length in 1..T -- checked here, then uploaded -- -> conf (B, T) fp64 on attn's
+    device, conf[b, t] = sum a [a > 4 / len_b] for t < len_b and 0 otherwise.  No gradient.  Nothing is converted or copied for the
+    caller: a wrong type, dtype, rank, stride, device or range is a ValueError."""
+    attn, B, T, att = _attn_maps("attn_conf", attn, cap_lens)
+    pa = ptr(attn)                                             # (a host tensor raises here, before anything is uploaded)
+    lens = cap_lens.to(attn.device)
+    conf = torch.empty((B, T), dtype=torch.float64, device=attn.device)
+    call("mogan_attn_conf_f64", pa, ptr(lens), B, T, att, ptr(conf), stream_ptr())
+    return conf
+
+
+def attn_sheet(attn, cap_lens, img, table, pick, alpha=180):
+    """The attention sheets of the picked (sample, word) pairs in one launch (mogan_attn_sheet_f64; DESIGN.md section 9p;
+    attngan/attnsheet.py has the definition): fp32 attn (B, T, att, att) and img (B, 3, vis, vis) and the fp64 table (vis, att) of
+    attnsheet.table on one device, vis a multiple of att and <= 256; cap_lens (B) and pick (P, 2) = (sample, word) are HOST int32
+    tensors -- checked here, then uploaded -- -> (sheet (P, vis, vis, 3) uint8, stats (P, 2) fp64 = (lo, hi), flags (P) int32) on
+    attn's device.  No gradient.  Nothing is converted or copied for the caller: a wrong type, dtype, rank, stride, device or range
+    is a ValueError, and so is a pick outside the batch or at or past its caption's length."""
+    attn, B, T, att = _attn_maps("attn_sheet", attn, cap_lens)
+    img = _dense_f32("attn_sheet", "img", img, 4)
+    if not torch.is_tensor(table) or table.dtype != torch.float64 or table.dim() != 2 or not table.is_contiguous():
+        raise ValueError("attn_sheet: table must be a contiguous fp64 (vis, %d) tensor, got %s %s"
+                         % (att, getattr(table, "dtype", type(table)), tuple(getattr(table, "shape", ()))))
+    vis = int(table.shape[0])
+    if table.shape[1] != att or vis < att or vis > 256 or vis % att:
+        raise ValueError("attn_sheet: table (vis, %d) with vis a multiple of %d and <= 256 expected, got %s" % (att, att, tuple(table.shape)))
+    if tuple(img.shape) != (B, 3, vis, vis):
+        raise ValueError("attn_sheet: img %s expected, got %s" % ((B, 3, vis, vis), tuple(img.shape)))
+    if img.device != attn.device or table.device != attn.device:
+        raise ValueError("attn_sheet: attn, img and table must be on one device (%s, %s, %s)" % (attn.device, img.device, table.device))
+    if not torch.is_tensor(pick) or pick.dtype != torch.int32 or pick.device.type != "cpu":
+        raise ValueError("attn_sheet: pick must be a host tensor of torch.int32, got %s %s"
+                         % (getattr(pick, "dtype", type(pick)), getattr(pick, "device", "")))
+    if pick.dim() != 2 or pick.shape[0] < 1 or pick.shape[1] != 2 or not pick.is_contiguous():
+        raise ValueError("attn_sheet: pick must be a contiguous (P >= 1, 2) tensor, got %s with strides %s"
+                         % (tuple(pick.shape), tuple(pick.stride())))
+    alpha = int(alpha)
+    if alpha < 0 or alpha > 255:
+        raise ValueError("attn_sheet: alpha in 0..255 expected, got %d" % alpha)
+    P = int(pick.shape[0])
+    if 3 * P * vis * vis > 2 ** 31 - 1 or img.numel() > 2 ** 31 - 1:
+        raise ValueError("attn_sheet: (%d, %d, %d, 3) has 2^31 elements or more" % (max(P, B), vis, vis))
+    # the legality of a pick, as attnsheet.pick_ok (the oracle) and the kernel's own guard (csrc/mogan_attn_sheet.hip) state it
+    s, w = pick[:, 0].to(torch.int64), pick[:, 1].to(torch.int64)
+    bad = ~((s >= 0) & (s < B) & (w >= 0) & (w < T))
+    bad |= w >= cap_lens.to(torch.int64)[s.clamp(0, B - 1)]
+    if bool(bad.any()):
+        r = int(bad.nonzero()[0])
+        raise ValueError("attn_sheet: pick row %d, (sample %d, word %d), is outside the batch of %d or at or past its caption's length"
+                         % (r, int(pick[r, 0]), int(pick[r, 1]), B))
+    pa, pi, pt = ptr(attn), ptr(img), ptr(table)               # (a host tensor raises here, before anything is uploaded)
+    both = torch.cat([cap_lens, pick.reshape(-1)]).to(attn.device)              # one upload: 4 B + 8 P bytes
+    sheet = torch.empty((P, vis, vis, 3), dtype=torch.uint8, device=attn.device)
+    stats = torch.empty((P, 2), dtype=torch.float64, device=attn.device)
+    flags = torch.empty((P,), dtype=torch.int32, device=attn.device)
+    call("mogan_attn_sheet_f64", pa, ptr(both), pi, pt, ptr(both) + 4 * B, P, B, T, att, vis, alpha, ptr(sheet), ptr(stats),
+         ptr(flags), stream_ptr())
+    return sheet, stats, flags
+
+
 _twiddles = {}
 
 
