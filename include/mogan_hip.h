@@ -316,9 +316,17 @@ int mogan_deep_conv_bn_act_bwd(const float* dz, const float* y, const float* sta
  *   mogan_pk_group          n <= 8 independent GEMMs in one launch: forward (dgrad = 0: rows = Cout, K = KH*KW*Cp, tap-major) or
  *                           stride-1 data gradient (dgrad = 1: rows = Cin, K = KH*KW*Cp over the dY panel).  raw receives
  *                           nsplit slabs of (B, M, outH, outW) fp32; nsplit is in/out (asked for / written).
- *   mogan_panel_tail_group  n <= 8 slices: v = sum of the sources' slabs; [box: 3x3 mean, zero padding, divisor 9];
- *                           [v = v * scale[c] + shift[c]]; [relu]; [v += add]; [v = 0 where mask <= 0]; -> dst (fp32, nullable)
- *                           and the panel slice (nullable; channels n .. roundup32(n) are written as zeros). */
+ *   mogan_panel_tail_group  n <= 8 slices: v = sum of the sources' slabs; [box, below]; [v = v * scale[c] + shift[c]]; [relu];
+ *                           [v += add]; [v = 0 where mask <= 0]; -> dst (fp32, nullable) and the panel slice (nullable;
+ *                           channels n .. roundup32(n) are written as zeros).
+ *                           box = 0: none.  box = 1: 3x3 sum with zero padding, x 1/9 (F.avg_pool2d(x, 3, 1, 1)).
+ *                           box = 2: 3x3 sum over the taps inside the map, divided (a true fp32 division) by their number, 1, 2,
+ *                           3, 4, 6 or 9 (count_include_pad=False; still a per-pixel linear map, so it commutes with a 1x1
+ *                           convolution as box = 1 does).  box = 3: maximum over the taps inside the map (F.max_pool2d(x, 3, 1, 1);
+ *                           NaN inputs undefined): exactly one source of one slab, else MOGAN_ERR_SHAPE; it does not commute
+ *                           with a convolution.  Any other value is MOGAN_ERR_SHAPE.  Groups whose members all have box <= 1
+ *                           run the kernels they always ran; box 2 / 3 are the pool branches of the published FID network
+ *                           (attngan/inception.py, variant "fid"), forward only. */
 typedef struct MoganPkArgs {
     const void* wpk; const void* panel; float* raw;
     int B, M;                 /* images, rows of the result */

@@ -160,8 +160,24 @@ def moved_matrices(tmi, table, boxes=None):
     return out
 
 
-def trunk_note(what, figure, unit):
+FID_NETWORK_NOTE = ("the trunk's weights are run as the published FID Inception network (trunk_variant fid: the PyTorch port of the 2015 "
+                    "TensorFlow graph, pt_inception-2015-12-05 -- the pool branches of Mixed_5b..7b average the taps inside the "
+                    "map, Mixed_7c's takes their maximum), so with that network's weights file the codes are the published kind; "
+                    "the protocol remains this project's: fp32 images that are not quantised to 8 bits, and this data "
+                    "pipeline's resize.")
+
+
+def trainer_variant(trainer):
+    """the trunk variant a trainer's passes run under (main.py --trunk_variant): "torchvision" unless it says otherwise"""
+    return getattr(trainer, "trunk_variant", None) or "torchvision"
+
+
+def trunk_note(what, figure, unit, variant="torchvision"):
     """the note of fid.json / kid.json / prdc.json: what the score is under an ImageNet trunk and under a random-init one"""
+    if variant != "torchvision":
+        return ("%s of Inception pool codes under the trunk file's weights: %s  %s under that network if the file holds its "
+                "weights, %s in other features -- comparable between checkpoints under this trunk_digest only -- if it does not."
+                % (what, FID_NETWORK_NOTE, figure, unit))
     return ("%s of Inception pool codes under the trunk of NET_E's image encoder: %s under torchvision's "
             "Inception-v3 if that trunk holds ImageNet weights (published figures mostly use the TF-ported network), %s "
             "in random convolutional features -- comparable between checkpoints under this trunk only -- if it is random-init."
@@ -187,13 +203,16 @@ class PooledCodes:
             elif codes["real"] is None:
                 raise ValueError("%s: the codes handed over hold no real side%s" % (who, or_else))
         self.who, self.seed, self.n, self.digest, self.split_dir = who, int(seed), codes["n"], codes["trunk_digest"], split_dir
+        self.variant = trainer_variant(trainer)
         self.real = None if codes["real"] is None else codes["real"][:self.n]
         self.fake = codes["fake"][:self.n]
         self.save_dir = eval_save_dir(split_dir)
 
     def write(self, out, n_real, n_fake, note):
         """adds the common keys to `out`, writes <save_dir>/<who>.json and returns `out`"""
-        out.update({"n_real": int(n_real), "n_fake": int(n_fake), "trunk_digest": self.digest})
+        out.update({"n_real": None if n_real is None else int(n_real), "n_fake": int(n_fake), "trunk_digest": self.digest})
+        if self.variant != "torchvision":                      # the default's files keep their key set
+            out["trunk_variant"] = self.variant
         write_score(self.split_dir, self.who, out, self.seed, note)
         return out
 
@@ -305,9 +324,20 @@ class CheckpointEvaluation(object):
             # must hold that pair's trunk.
             from .fid import trunk_digest
             from .inception import load_trunk_state
-            own = trunk_digest(image_encoder) if cfg.TRAIN.NET_E != '' else None
-            load_trunk_state(image_encoder, self._state_file(trunk_path), trunk_path)
+            variant = trainer_variant(self)
+            own = trunk_digest(image_encoder) if cfg.TRAIN.NET_E != '' and variant == "torchvision" else None
+            state = self._state_file(trunk_path)
+            load_trunk_state(image_encoder, state, trunk_path)
             print('Load Inception trunk from:', trunk_path)
+            if variant != "torchvision":
+                # the pool-code scores touch no DAMSM head: beside NET_E's pair the file's trunk REPLACES that pair's (the check
+                # below is the default variant's), and the weights run as the variant's network
+                image_encoder.set_trunk_variant(variant)
+            elif "fc.weight" in state and state["fc.weight"].dim() == 2 and state["fc.weight"].shape[0] == 1008 \
+                    and not getattr(self, "_said_fid_file", False):
+                self._said_fid_file = True                     # once per trainer: a score may build its encoder twice
+                print("%s has a 1008-way head: it looks like the published FID Inception network's file, which runs as that network "
+                      "under --trunk_variant fid; this pass runs its weights with torchvision's pooling" % trunk_path)
             if own is not None and trunk_digest(image_encoder) != own:
                 raise ValueError("--trunk %s holds another Inception trunk (digest %s...) than NET_E's image encoder (%s...): one "
                                  "pass runs under one trunk" % (trunk_path, trunk_digest(image_encoder)[:12], own[:12]))
@@ -372,6 +402,9 @@ class CheckpointEvaluation(object):
         from .retrieval import SentenceBank, draw_mismatched, fold_stats
         if net_g_missing():
             return None
+        if trainer_variant(self) != "torchvision":
+            raise ValueError("r_precision: the score runs the DAMSM heads on torchvision's trunk; the trunk variant %r serves the "
+                             "scores on pool codes only" % trainer_variant(self))
         netG, text_encoder, image_encoder, gen = self._load_seeded(seed)
         save_dir = eval_save_dir(split_dir)
         bank = SentenceBank.from_dataset(text_encoder, self.data_loader.dataset, cfg.TEXT.WORDS_NUM, seed)
@@ -542,15 +575,25 @@ class CheckpointEvaluation(object):
         random convolutional features, comparable between checkpoints under the same trunk only.
         Writes <NET_G minus .pth>/<split>/fid.json and returns its content; with return_codes also a dict of the two code matrices
         on the host, "real" (None where the real side was loaded) and "fake"."""
-        from .fid import FeatureStats, frechet_distance
+        from .fid import FeatureStats, frechet_distance, is_external_stats, load_external_stats
         if net_g_missing():
             return None
         loaded = []
+        variant = trainer_variant(self)
 
         def want_real(digest, D):
             if stats_path is not None and os.path.isfile(stats_path):
-                loaded.append(FeatureStats.load(stats_path, digest, D))     # ValueError for another trunk's file
-                print('Load real-image statistics from: %s (%d images)' % (stats_path, loaded[0].n))
+                if is_external_stats(stats_path):
+                    # a TTUR / pytorch-fid file (mu, sigma): read under the published network only, never written
+                    if variant != "fid":
+                        raise ValueError("%s holds published statistics (mu, sigma): they are accepted under --trunk_variant fid only"
+                                         % stats_path)
+                    mu, sigma = load_external_stats(stats_path, D)
+                    loaded.append(FeatureStats(mu, sigma, 0, "external"))
+                    print('Load published real-image statistics from: %s (network and protocol unverified)' % stats_path)
+                else:
+                    loaded.append(FeatureStats.load(stats_path, digest, D))     # ValueError for another trunk's file
+                    print('Load real-image statistics from: %s (%d images)' % (stats_path, loaded[0].n))
             return not loaded
         c = PooledCodes(self, "fid", split_dir, num_samples, seed, codes, want_real, " and there is no statistics file")
         n, D = c.n, int(c.fake.shape[1])
@@ -565,15 +608,20 @@ class CheckpointEvaluation(object):
                 real_stats.save(stats_path)
                 print('Save real-image statistics to: %s' % stats_path)
         dist, terms = frechet_distance(real_stats.mean, real_stats.cov, fake_stats.mean, fake_stats.cov)
-        few = min(real_stats.n, fake_stats.n)
-        note = trunk_note("Frechet distance", "FID", "a distance")
+        external = bool(loaded) and loaded[0].trunk_digest == "external"
+        few = fake_stats.n if external else min(real_stats.n, fake_stats.n)
+        note = trunk_note("Frechet distance", "FID", "a distance", variant)
+        if external:
+            note += (" The real side is the published statistics file %s: the network and the protocol it was computed under are "
+                     "unverified, and the number of its images is unknown." % stats_path)
         if few < D:
             note += (" n = %d < %d features: the covariances are rank-deficient, so the figure is biased and only comparable "
                      "at equal n." % (few, D))
             print("FID: %d images for %d features -- the covariances are rank-deficient, the figure is biased and only comparable "
                   "at equal n (the JSON records it)" % (few, D))
-        out = c.write(dict(terms, fid=dist), real_stats.n, fake_stats.n, note)
-        print("FID (%d real, %d generated images): %.4f = |dmu|^2 %.4f + Tr S_real %.4f + Tr S_fake %.4f - 2 x %.4f -> %s/fid.json"
+        out = c.write(dict(terms, fid=dist, **({"real_stats": "external"} if external else {})),
+                      None if external else real_stats.n, fake_stats.n, note)
+        print("FID (%s real, %d generated images): %.4f = |dmu|^2 %.4f + Tr S_real %.4f + Tr S_fake %.4f - 2 x %.4f -> %s/fid.json"
               % (out["n_real"], out["n_fake"], dist, terms["mean_sq"], terms["tr_s1"], terms["tr_s2"], terms["tr_sqrt"], c.save_dir))
         return c.result(out, return_codes)
 
@@ -598,7 +646,7 @@ class CheckpointEvaluation(object):
         sums = ops.poly_mmd_sums(c.real, c.fake, ix, iy, gamma=gamma, coef0=KID.COEF0).cpu().numpy()   # the one read-back
         mean, std, _ = KID.kid_from_sums(sums, s)
         note = trunk_note("Kernel Inception distance (unbiased MMD^2 under the cubic polynomial kernel, mean over subset pairs)",
-                          "KID", "a distance")
+                          "KID", "a distance", c.variant)
         if s < int(subset_size):
             note += (" subset_size lowered from %d to %d: there are only %d images per side." % (subset_size, s, n))
             print("KID: %d images per side -- subsets of %d codes instead of %d (the JSON records it)" % (n, s, subset_size))
@@ -634,7 +682,7 @@ class CheckpointEvaluation(object):
         counts = torch.cat([fake_in_real, real_in_fake, real_own], dim=1).cpu().numpy()      # (n, 4): the one read-back
         scores = PRDC.scores_from_counts(counts[:, 0:2], counts[:, 2], counts[:, 3], kd)
         note = trunk_note("Improved precision / recall (k_pr nearest neighbours) and density / coverage (k_dc)",
-                          "the published scores", "scores")
+                          "the published scores", "scores", c.variant)
         note += " All four figures depend on the number of images and are comparable at equal n only."
         for name, asked, k in (("k_pr", k_pr, kp), ("k_dc", k_dc, kd)):
             if k < int(asked):
@@ -806,7 +854,7 @@ class CheckpointEvaluation(object):
         stats = [[t.cpu() for t in ops.feature_moments(codes)] for codes in (real, fake)]
         dist, terms = frechet_distance(stats[0][0], stats[0][1], stats[1][0], stats[1][1])
         note = trunk_note("Object-level Frechet distance (SceneFID: every object cut at its box and resized to the trunk's input)",
-                          "SceneFID", "a distance")
+                          "SceneFID", "a distance", trainer_variant(self))
         note += (" The boxes are the data's on both sides: the real and the generated image of a caption are cut at the same "
                  "ground-truth boxes; a box counts when its shorter side is at least min_side pixels.")
         if n < D:
@@ -816,6 +864,8 @@ class CheckpointEvaluation(object):
                   "comparable at equal n (the JSON records it)" % (n, D))
         out = dict(terms, scene_fid=dist)
         out.update({"n_objects": int(n), "n_images": int(objects.n_images), "min_side": objects.min_side, "trunk_digest": digest})
+        if trainer_variant(self) != "torchvision":
+            out["trunk_variant"] = trainer_variant(self)
         save_dir = write_score(split_dir, "scene_fid", out, seed, note)
         print("SceneFID (%d objects of %d images, real and generated): %.4f = |dmu|^2 %.4f + Tr S_real %.4f + Tr S_fake %.4f - 2 x %.4f "
               "-> %s/scene_fid.json" % (n, objects.n_images, dist, terms["mean_sq"], terms["tr_s1"], terms["tr_s2"], terms["tr_sqrt"],
@@ -918,6 +968,13 @@ class CheckpointEvaluation(object):
                 "under torchvision's network, not the TF-ported one of the published figures, and with 1000 outputs against its "
                 "1008; under any other trunk or head it is comparable between checkpoints under the same trunk_digest and "
                 "head_digest only.  The figure depends on the number of images per split.")
+        if c.variant != "torchvision":
+            note = ("Inception Score: exp of the mean KL(p(y|x) || p(y)) of a classifier head over Inception pool codes, per "
+                    "contiguous split of the pass, mean and population standard deviation over the splits, and over all rows "
+                    "(inception_score_all).  " + FID_NETWORK_NOTE[0].upper() + FID_NETWORK_NOTE[1:] + "  The head is the file's "
+                    "own (1008 outputs in the published file); under any other weights the figure is comparable between "
+                    "checkpoints under the same trunk_digest and head_digest only.  The figure depends on the number of images "
+                    "per split.")
         if not verified:
             note += " The head file holds no trunk: the head was not verified against the trunk the codes were taken under."
         if S < int(splits):
@@ -1248,7 +1305,7 @@ class CheckpointEvaluation(object):
                           "training image than that image's own nearest training neighbour, authenticity_heldout: the same share "
                           "of the evaluation split's real images; copying: the Mann-Whitney statistic of the generated images' "
                           "distances to the training set against the held-out real images', 0.5 = as far as unseen real images, "
-                          "towards 1 = closer)", "the papers' figures", "figures")
+                          "towards 1 = closer)", "the papers' figures", "figures", c.variant)
         note += " Every figure depends on n_bank: comparable at equal bank only."
         if bank.split == "synthetic-train":
             note += " Synthetic data: the bank is a second synthetic set with a seed of its own, not a split of real images."

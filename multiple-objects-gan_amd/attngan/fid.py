@@ -48,9 +48,14 @@ def frechet_distance(mu1, S1, mu2, S2):
 
 def trunk_digest(encoder):
     """SHA-256 (hex) over the parameters and buffers of the encoder's Inception trunk -- everything in its state_dict but the two
-    DAMSM heads -- in state_dict order: name, dtype, shape and bytes of each entry"""
+    DAMSM heads -- in state_dict order: name, dtype, shape and bytes of each entry.  Under another trunk variant than the default
+    (CNN_ENCODER.trunk_variant) a line naming it is hashed first: the same weights run as two networks give two digests, so
+    statistics, banks and heads of one are refused under the other"""
     heads = tuple(getattr(encoder, "HEADS", ()))
     h = hashlib.sha256()
+    variant = getattr(encoder, "trunk_variant", "torchvision")
+    if variant != "torchvision":
+        h.update(("trunk_variant %s\n" % variant).encode())
     for name, t in encoder.state_dict().items():
         if name.split(".")[0] in heads:
             continue
@@ -86,6 +91,37 @@ class FeatureStats:
         if mean.shape != (D,) or cov.shape != (D, D):
             raise ValueError("%s holds statistics of %s features, this encoder has %d" % (path, mean.shape, D))
         return cls(mean, cov, n, digest)
+
+
+def is_external_stats(path):
+    """whether `path` is a TTUR / pytorch-fid statistics file: an .npz holding exactly `mu` and `sigma`"""
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            return set(z.files) == {"mu", "sigma"}
+    except (OSError, ValueError):
+        return False
+
+
+def load_external_stats(path, D):
+    """(mu (D,), sigma (D, D)), fp64 host tensors, of a TTUR / pytorch-fid statistics file.  ValueError naming the file and the
+    fault where the arrays are not D wide, not finite or sigma is not symmetric.  Which network and protocol the file was computed
+    under cannot be checked; such a file is never written here."""
+    with np.load(path, allow_pickle=False) as z:
+        if set(z.files) != {"mu", "sigma"}:
+            raise ValueError("%s: exactly mu and sigma expected, found %s" % (path, sorted(z.files)))
+        mu, sigma = z["mu"], z["sigma"]
+    for name, a in (("mu", mu), ("sigma", sigma)):
+        if a.dtype.kind not in "fiu":
+            raise ValueError("%s: %s is %s, numbers expected" % (path, name, a.dtype))
+    mu, sigma = np.asarray(mu, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
+    if mu.shape != (D,) or sigma.shape != (D, D):
+        raise ValueError("%s: width -- mu %s and sigma %s, this encoder's codes are %d wide" % (path, mu.shape, sigma.shape, D))
+    if not np.isfinite(mu).all() or not np.isfinite(sigma).all():
+        raise ValueError("%s: non-finite values in %s" % (path, "mu" if not np.isfinite(mu).all() else "sigma"))
+    asym = float(np.abs(sigma - sigma.T).max())
+    if asym > 1e-6 * max(float(np.abs(sigma).max()), 1e-300):
+        raise ValueError("%s: sigma is not symmetric (max |sigma - sigma^T| = %.3e)" % (path, asym))
+    return _f64(mu), _f64(sigma)
 
 
 class NeighbourBank:

@@ -635,12 +635,19 @@ class FrozenTrunk:
 #     mask, gradient accumulation, fp32 copy, next panel);
 #   * the pool branch avg_pool(3,1,1) -> 1x1 conv is evaluated as 1x1 conv -> avg_pool (both linear, they commute): the 1x1 joins
 #     the block's first GEMM (one more row range) and the pool runs on 192 instead of 768 channels inside the tail; backward the
-#     same way round (box filter of the slice's gradient, then the shared data-gradient GEMM);
+#     same way round (box filter of the slice's gradient, then the shared data-gradient GEMM).  Under the variant "fid" (VARIANTS
+#     below) the mean is over the taps inside the map -- a per-pixel factor, it commutes as well (box = 2) -- and Mixed_7c's pool
+#     branch is a maximum, which does not: there the block input is pooled first (box = 3) and convolved afterwards;
 #   * the four stride-2 convolutions run forward on the packed kernel; their data gradients (odd maps, 3x3 stride 2) and the two
 #     max-pools keep the kernels FrozenTrunk uses, on the fp32 copies.
 # Same arithmetic as FrozenTrunk up to fp32 reassociation (pool/conv order, K-split order); checked against it and the CPU
 # restatement in tests/.
 PANEL_TRUNK = True
+# Which network the trunk's weights are run as.  "torchvision": torchvision's Inception-v3, what DAMSM trains under.  "fid": the
+# PyTorch port of the 2015 TensorFlow graph that published FID / IS figures are computed under (pt_inception-2015-12-05): the same
+# layers and key names, but the pool branch of Mixed_5b..5d, 6b..6e and 7b is avg_pool2d(x, 3, 1, 1, count_include_pad=False) and
+# Mixed_7c's is max_pool2d(x, 3, 1, 1).  Forward only, on the panel trunk only.
+VARIANTS = ("torchvision", "fid")
 # blocks a grouped GEMM launch aims at (K-split).  Measured in the B = 16 step: 256 / 128 / none 407 img/s, 512 404-405, 768 402 (alone
 # on the GPU the launches are fastest at 512: 3.0 vs 3.5 ms per step at 128)
 PANEL_TARGET = 256
@@ -832,13 +839,26 @@ def _f32src(s):
 class PanelTrunk(FrozenTrunk):
     """Stem as FrozenTrunk (wide maps, few channels: the streaming / Winograd kernels); Mixed_5b .. 7c on pixel panels."""
 
-    def __init__(self, enc):
+    def __init__(self, enc, variant="torchvision"):
+        if variant not in VARIANTS:
+            raise ValueError("unknown trunk variant %r (one of %s)" % (variant, ", ".join(VARIANTS)))
+        self.variant = variant
+        # box mode of the pool branch's tail member (mogan_panel_tail_group): the zero-padded mean, or the mean of the taps inside
+        self.box = 1 if variant == "torchvision" else 2
         self.stem = {n: _FrozenConv([getattr(enc, n)], names=[n]) for n in ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3",
                                                                "Conv2d_3b_1x1", "Conv2d_4a_3x3")}
         self.blocks = []
         for name, _ in TRUNK[5:]:
             blk = getattr(enc, name)
             g = lambda *names, **kw: _PConv([getattr(blk, n) for n in names], names=[name + "." + n for n in names], **kw)
+            if variant == "fid" and name == "Mixed_7c":
+                # the pool branch is a maximum, which does not commute with its convolution: the block input is pooled first
+                # (tail member, box = 3) and branch_pool is a convolution of its own over that panel, in the second GEMM
+                fcs = dict(g1=g("branch1x1", "branch3x3_1", "branch3x3dbl_1"), pool=g("branch_pool", dgrad=False),
+                           a=g("branch3x3_2a"), b=g("branch3x3_2b"), d2=g("branch3x3dbl_2"), da=g("branch3x3dbl_3a"),
+                           db=g("branch3x3dbl_3b"))
+                self.blocks.append((name, type(blk).__name__, fcs))
+                continue
             if isinstance(blk, InceptionA):
                 fcs = dict(g1=g("branch1x1", "branch5x5_1", "branch3x3dbl_1", "branch_pool"), b5=g("branch5x5_2"),
                            d2=g("branch3x3dbl_2"), d3=g("branch3x3dbl_3"))
@@ -884,7 +904,8 @@ class PanelTrunk(FrozenTrunk):
         xin = X.whole()
         if kind in ("InceptionA", "InceptionC", "InceptionE"):
             g1 = f["g1"]
-            n1, npool = g1.couts[0], g1.couts[3]
+            fpool = f.get("pool")                     # variant "fid", Mixed_7c: the max-pooled branch's own convolution
+            n1, npool = g1.couts[0], (fpool.couts[0] if fpool is not None else g1.couts[3])
             G = tp.new(g1.couts[1:3], H, W)
             if kind == "InceptionA":
                 O = tp.new([n1, 64, 96, npool], H, W)
@@ -896,8 +917,15 @@ class PanelTrunk(FrozenTrunk):
                 O = tp.new([320, 384, 384, 384, 384, 192], H, W)
                 ipool = 5
             (r,) = tp.gemm([(g1, 0, xin, hw)])
-            tp.tail([self._fwd(r, g1, 0, O.sl(0)), self._fwd(r, g1, 1, G.sl(0)), self._fwd(r, g1, 2, G.sl(1)),
-                     self._fwd(r, g1, 3, O.sl(ipool), box=1)])
+            first = [self._fwd(r, g1, 0, O.sl(0)), self._fwd(r, g1, 1, G.sl(0)), self._fwd(r, g1, 2, G.sl(1))]
+            if fpool is None:
+                tp.tail(first + [self._fwd(r, g1, 3, O.sl(ipool), box=self.box)])
+            else:
+                # max_pool2d(X, 3, 1, 1) of the fp32 copy -> panel only, in one member: Mixed_7b's slices fill their groups of 32,
+                # so the fp32 copy has no pad channels
+                assert all(n % 32 == 0 for n in X.sizes), X.sizes
+                P = tp.new(X.sizes, H, W, f32=False)
+                tp.tail(first + [dict(srcs=[_f32src(xin)], out=P.whole(), box=3)])
             if kind == "InceptionA":
                 U = tp.new([96], H, W)
                 ra, rb = tp.gemm([(f["b5"], 0, G.sl(0), hw), (f["d2"], 0, G.sl(1), hw)])
@@ -943,8 +971,10 @@ class PanelTrunk(FrozenTrunk):
                     tp.tail([self._final([rg], dX, xin)])
             else:
                 U = tp.new([384], H, W)
-                ra, rb, rc = tp.gemm([(f["a"], 0, G.sl(0), hw), (f["b"], 0, G.sl(0), hw), (f["d2"], 0, G.sl(1), hw)])
-                tp.tail([self._fwd(ra, f["a"], 0, O.sl(1)), self._fwd(rb, f["b"], 0, O.sl(2)), self._fwd(rc, f["d2"], 0, U.sl(0))])
+                second = [(f["a"], 0, G.sl(0), hw), (f["b"], 0, G.sl(0), hw), (f["d2"], 0, G.sl(1), hw)]
+                ra, rb, rc, *rp = tp.gemm(second + ([(fpool, 0, P.whole(), hw)] if fpool is not None else []))
+                tp.tail([self._fwd(ra, f["a"], 0, O.sl(1)), self._fwd(rb, f["b"], 0, O.sl(2)), self._fwd(rc, f["d2"], 0, U.sl(0))]
+                        + [self._fwd(p, fpool, 0, O.sl(5)) for p in rp])
                 ra, rb = tp.gemm([(f["da"], 0, U.sl(0), hw), (f["db"], 0, U.sl(0), hw)])
                 tp.tail([self._fwd(ra, f["da"], 0, O.sl(3)), self._fwd(rb, f["db"], 0, O.sl(4))])
 
@@ -1039,7 +1069,7 @@ class PanelTrunk(FrozenTrunk):
         pt = _PTape(x299.shape[0], x299.device)
         X = _PT(pt.B, pt.dev, [cur.C], cur.H, cur.W, f32=cur.t)
         pt.tail([dict(srcs=[_f32src(X.sl(0))], out=X.sl(0), f32=False)])
-        pt.stem_out, pt.chain = cur.t, []
+        pt.stem_out, pt.chain, pt.variant = cur.t, [], self.variant
         feats = None
         for name, kind, fcs in self.blocks:
             O, bwd = self._block(pt, kind, fcs, X)
@@ -1054,6 +1084,8 @@ class PanelTrunk(FrozenTrunk):
     def backward(tapes, gfeat, glast):
         """gradients of the two outputs (None = zero) -> gradient of x299"""
         tp, pt = tapes
+        if pt.variant != "torchvision":
+            raise RuntimeError("the trunk variant %r is forward only: no gradient goes through it" % pt.variant)
         for out, g in ((pt.last, glast), (pt.feats, gfeat)):
             d = pt.grad(out)
             if g is None:
@@ -1101,9 +1133,15 @@ def frozen_trunk(enc, x299):
     key = _versions(*[t for n, t in list(enc.named_parameters()) + list(enc.named_buffers())
                       if t.is_floating_point() and n.split(".")[0] not in heads])
     cls = PanelTrunk if PANEL_TRUNK else FrozenTrunk
+    variant = getattr(enc, "trunk_variant", "torchvision")
+    if variant != "torchvision":
+        if cls is not PanelTrunk:
+            raise RuntimeError("the trunk variant %r is built on the panel trunk only (inception.PANEL_TRUNK): FrozenTrunk and the "
+                               "module-by-module path run torchvision's network" % variant)
+        key = (variant, key)                       # the default's key is what it always was
     if ft is None or type(ft) is not cls or getattr(enc, "_frozen_trunk_key", None) != key \
             or ft.stem["Conv2d_1a_3x3"].w.device != x299.device:
-        ft = enc._frozen_trunk = cls(enc)
+        ft = enc._frozen_trunk = cls(enc) if variant == "torchvision" else cls(enc, variant)
         enc._frozen_trunk_key = key
     return _FrozenTrunkFn.apply(x299, ft)
 

@@ -8,7 +8,8 @@ Evaluation (TRAIN.FLAG False): every score of evaluate.SCORES has a flag of its 
 keywords, and CheckpointEvaluation.run_scores gives any number of them from one pass.  A new score adds its flags and its entry there.
 --layout_shift (CheckpointEvaluation.layout_shift) and --inception_score (CheckpointEvaluation.inception_score) are modes of their own
 beside --sampling and --r_precision, and so is --scenes FILE (CheckpointEvaluation.scenes): images from captions, boxes and labels the
-user wrote.  --trunk PATH loads the image encoder's Inception trunk from a torchvision file."""
+user wrote.  --trunk PATH loads the image encoder's Inception trunk from a torchvision file; --trunk_variant fid runs such a file's
+weights as the published FID Inception network."""
 import argparse
 import datetime
 import os
@@ -35,6 +36,9 @@ else:
     from .evaluate import SCORES
     from .trainer import condGANTrainer as trainer
     from ..hip import lib as hiplib
+
+
+POOL_CODE_MODES = ('fid', 'kid', 'prdc', 'scene_fid', 'memorisation', 'inception_score')     # what --trunk_variant serves
 
 
 def parse_args(argv=None):
@@ -144,6 +148,12 @@ def parse_args(argv=None):
                              'inception_v3_google-*.pth (old or new layout) or any image_encoder*.pth -- so that with NET_E: \'\' the '
                              'scores on pool codes run under ImageNet features; the generated images are those of a pass without it; '
                              'beside a NET_E the file must hold that pair\'s trunk')
+    parser.add_argument('--trunk_variant', type=str, default='torchvision', choices=('torchvision', 'fid'),
+                        help='with --trunk: the network the file\'s weights are run as -- torchvision\'s Inception-v3, or fid: the '
+                             'published FID Inception network (pt_inception-2015-12-05-*.pth, the PyTorch port of the 2015 TensorFlow '
+                             'graph; other pooling in the Mixed blocks\' pool branches), for --fid --kid --prdc --scene_fid '
+                             '--memorisation --inception_score; beside a NET_E the file\'s trunk then replaces that pair\'s; not '
+                             'together with --r_precision')
     parser.add_argument('--inception_score', action='store_true',
                         help='evaluation (TRAIN.FLAG False): Inception Score of TRAIN.NET_G\'s images -- the softmax of a classifier '
                              'head over their Inception pool codes (condGANTrainer.inception_score) -> <NET_G minus .pth>/<split>/'
@@ -184,6 +194,14 @@ def parse_args(argv=None):
     for name in list(SCORES) + ['layout_shift']:
         if getattr(args, name) and args.inception_score:
             parser.error('--%s cannot be combined with --inception_score' % name)
+    if args.trunk_variant != 'torchvision':
+        if not args.trunk:
+            parser.error('--trunk_variant %s runs the weights of a file: it needs --trunk' % args.trunk_variant)
+        if args.r_precision:
+            parser.error('--trunk_variant %s cannot be combined with --r_precision: that score runs the DAMSM heads' % args.trunk_variant)
+        if not any(getattr(args, name) for name in POOL_CODE_MODES):
+            parser.error('--trunk_variant %s serves the modes that read pool codes: one of %s'
+                         % (args.trunk_variant, ' '.join('--' + name for name in POOL_CODE_MODES)))
     if args.is_splits < 1:
         parser.error('--is_splits must be 1 at least')
     if args.ls_show < 0 or (args.ls_min_shift is not None and args.ls_min_shift < 1):
@@ -280,6 +298,8 @@ def main(argv=None):
                                          num_workers=min(int(cfg.WORKERS), 8 if args.synthetic else int(cfg.WORKERS)))
     # the trunk file reaches the trainer only where the flag is given: a trainer without the keyword serves every other run
     extra = {'trunk': args.trunk} if args.trunk else {}
+    if args.trunk_variant != 'torchvision':
+        extra['trunk_variant'] = args.trunk_variant
     algo = trainer(output_dir, loader, dataset.n_words, dataset.ixtoword, args.resume, distributed=world > 1, **extra)
     if cfg.TRAIN.FLAG:
         algo.train()

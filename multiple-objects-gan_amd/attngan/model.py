@@ -208,6 +208,15 @@ class CNN_ENCODER(nn.Module):
         self.emb_cnn_code.weight.data.uniform_(-0.1, 0.1)
 
     HEADS = ("emb_features", "emb_cnn_code")
+    # which network the trunk's weights are run as (inception.VARIANTS): "torchvision", what DAMSM trains under, or "fid", the
+    # published FID network's pooling (forward only, frozen fast path only).  No part of the state_dict.
+    trunk_variant = "torchvision"
+
+    def set_trunk_variant(self, name):
+        if name not in inception.VARIANTS:
+            raise ValueError("unknown trunk variant %r (one of %s)" % (name, ", ".join(inception.VARIANTS)))
+        self.trunk_variant = name
+        return self
 
     def trunk_parameters(self):
         return [p for n, p in self.named_parameters() if n.split(".")[0] not in self.HEADS]
@@ -224,6 +233,10 @@ class CNN_ENCODER(nn.Module):
 
     def _trunk_walk(self, x):
         """the one copy of the trunk walk: images -> (the 17 x 17 x 768 map, the pooled (B, 2048) vector)"""
+        if self.trunk_variant != "torchvision" and ((torch.is_grad_enabled() and x.requires_grad) or not self._frozen()):
+            raise RuntimeError("the trunk variant %r is forward only and runs on the frozen fast path only (eval mode, no trunk "
+                               "parameter asking for a gradient, an input without one): the module-by-module path and the "
+                               "backward pass run torchvision's network" % self.trunk_variant)
         x = ops.bilinear_resize(x, 299, 299)
         if self._frozen():
             # the train step's case (trainer.py:62-66): explicit forward/backward over the folded, grouped trunk

@@ -1409,7 +1409,14 @@ class condGANTrainer(CheckpointEvaluation):
     """Same constructor and public methods as the reference class (trainer.py:29-366); the methods that evaluate a finished
     checkpoint (sampling, sample, r_precision, pool_codes, fid, kid, prdc) are inherited from evaluate.CheckpointEvaluation."""
 
-    def __init__(self, output_dir, data_loader, n_words, ixtoword, resume, distributed=False, use_graph=False, trunk=None):
+    def __init__(self, output_dir, data_loader, n_words, ixtoword, resume, distributed=False, use_graph=False, trunk=None,
+                 trunk_variant=None):
+        from .inception import VARIANTS
+        if trunk_variant is not None and trunk_variant not in VARIANTS:
+            raise ValueError("unknown trunk variant %r (one of %s)" % (trunk_variant, ", ".join(VARIANTS)))
+        if trunk_variant not in (None, "torchvision") and not trunk:
+            raise ValueError("the trunk variant %r runs a trunk file's weights: it needs `trunk`" % trunk_variant)
+        self.trunk_variant = trunk_variant or "torchvision"    # evaluation: the network that file's weights are run as
         self.trunk_path = trunk                   # evaluation: the Inception trunk's file (CheckpointEvaluation._load_image_encoder)
         if cfg.TRAIN.FLAG:
             self.model_dir = os.path.join(output_dir, 'Model')

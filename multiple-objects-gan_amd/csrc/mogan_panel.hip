@@ -6,6 +6,9 @@
 //
 //     v = sum over the sources' K-split slabs            raw GEMM results (B, rows, H, W), or any fp32 NCHW slice
 //     v = mean of the 3x3 neighbourhood (zero padded)    the pool branch: F.avg_pool2d(x, 3, 1, 1) commutes with the 1x1 convolution
+//         box = 2: sum of the taps inside the map / their number (count_include_pad=False: a per-pixel factor, commutes as well)
+//         box = 3: maximum of the taps inside the map (F.max_pool2d(x, 3, 1, 1): does NOT commute -- one source, one slab, and
+//                  the caller pools the convolution's input)
 //     v = v * scale[c] + shift[c]; relu                  forward: eval-mode BatchNorm folded + ReLU
 //     v += add; v = 0 where mask <= 0                    backward: other contributors of the gradient, ReLU mask of the layer's input
 //     -> fp32 NCHW slice and / or pixel-panel slice      what the next GEMM (and the old-path kernels around the trunk) read
@@ -24,7 +27,9 @@ namespace {
 constexpr int PT_MAXG = 8;
 struct TailGroup { MoganTailArgs m[PT_MAXG]; unsigned end[PT_MAXG]; int n; };
 
-template <bool BOX>
+// BOX: 0 = no member has a box; 1 = members of box 0 / 1 (the train step's trunk); 2 = members of box 0 .. 3 (some member of
+// box 2 or 3: the published FID network's pool branches, forward only)
+template <int BOX>
 __global__ __launch_bounds__(256, 4) void panel_tail_kernel(const TailGroup g) {
     __shared__ float L[32][65];
     int mi = 0;
@@ -66,6 +71,30 @@ __global__ __launch_bounds__(256, 4) void panel_tail_kernel(const TailGroup g) {
                 for (int j = 0; j < 8; ++j) v[j] += t[j];
             }
         }
+    } else if (BOX == 2 && a.box == 3) {
+        const int W = a.W, H = a.H;
+        const int y = (int)pix / W, x = (int)pix - y * W;
+        const unsigned ib = img * (unsigned)a.src_bs[0];
+        const float* __restrict__ p = a.src[0];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = -INFINITY;
+#pragma unroll 1
+        for (int dy = -1; dy <= 1; ++dy) {
+            float t[3][8];
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int yy = y + dy, xx = x + dx;
+                const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
+                const int d = dy * W + dx;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float u = p[(ok[j] && in) ? ib + inner[j] + d : 0u];
+                    t[dx + 1][j] = in ? u : -INFINITY;                                 // padding never wins
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], fmaxf(fmaxf(t[0][j], t[1][j]), t[2][j]));
+        }
     } else {
         const int W = a.W, H = a.H;
         const int y = (int)pix / W, x = (int)pix - y * W;
@@ -92,8 +121,15 @@ __global__ __launch_bounds__(256, 4) void panel_tail_kernel(const TailGroup g) {
                 }
             }
         }
+        if (BOX == 2 && a.box == 2) {
+            // the taps inside the map: 1, 2, 3, 4, 6 or 9.  A true division: a constant map whose ninefold sum is exact stays constant
+            const float cnt = (float)(((y > 0) + 1 + (y < H - 1)) * ((x > 0) + 1 + (x < W - 1)));
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= (1.f / 9.f);
+            for (int j = 0; j < 8; ++j) v[j] = __fdiv_rn(v[j], cnt);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] *= (1.f / 9.f);
+        }
     }
     if (a.scale != nullptr) {
         float sc[8], sh[8];
@@ -156,8 +192,9 @@ int mogan_panel_tail_group(int n, const MoganTailArgs* args, hipStream_t stream)
     for (int i = 0; i < n; ++i) {
         const MoganTailArgs& a = args[i];
         if (a.B <= 0 || a.n <= 0 || a.H <= 0 || a.W <= 0 || a.nsrc <= 0 || a.nsrc > MOGAN_TAIL_MAXSRC || (!a.dst && !a.panel) ||
-            ((a.scale == nullptr) != (a.shift == nullptr)))
+            ((a.scale == nullptr) != (a.shift == nullptr)) || a.box < 0 || a.box > 3)
             return MOGAN_ERR_SHAPE;
+        if (a.box == 3 && (a.nsrc != 1 || a.src_nsplit[0] != 1)) return MOGAN_ERR_SHAPE;    // a maximum of sums is no sum of maxima
         const long long Q = (long long)a.B * a.H * a.W;
         if (Q >= (1ll << 31)) return MOGAN_ERR_SHAPE;
         const long long lim = 1ll << 31;           // 32-bit element offsets inside every tensor
@@ -172,10 +209,11 @@ int mogan_panel_tail_group(int n, const MoganTailArgs* args, hipStream_t stream)
         if (end > 0x7fffffff) return MOGAN_ERR_SHAPE;
         g.end[i] = (unsigned)end;
     }
-    bool box = false;
-    for (int i = 0; i < n; ++i) box = box || args[i].box != 0;
-    if (box) hipLaunchKernelGGL(panel_tail_kernel<true>, dim3((unsigned)end), dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL(panel_tail_kernel<false>, dim3((unsigned)end), dim3(256), 0, stream, g);
+    int box = 0;                                   // members of box 0 / 1 only: the two instantiations of the train step's trunk
+    for (int i = 0; i < n; ++i) box = args[i].box > box ? args[i].box : box;
+    if (box >= 2) hipLaunchKernelGGL(panel_tail_kernel<2>, dim3((unsigned)end), dim3(256), 0, stream, g);
+    else if (box) hipLaunchKernelGGL(panel_tail_kernel<1>, dim3((unsigned)end), dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL(panel_tail_kernel<0>, dim3((unsigned)end), dim3(256), 0, stream, g);
     return hipGetLastError() == hipSuccess ? 0 : MOGAN_ERR_LAUNCH;
 }
 
